@@ -8,10 +8,13 @@ SpatialNet-small (8 layers, H=96) forward -> inorm + iSTFT -> uPIT neg-SI-SDR ->
 Inputs are resident in HBM before the timed region.  One process per GPU (torchrun sets RANK / LOCAL_RANK /
 WORLD_SIZE), weak scaling: the per-GPU batch is fixed.
 
-Prints ONE JSON line (rank 0) with the contract keys plus
+Prints ONE JSON line (rank 0) with the contract keys (ms_per_step: wall time of one timed step).  A plain run sets up, warms up,
+times --steps steps and nothing else; --full adds
   roofline     : dominant kernel (largest share of GPU time), algorithmic HBM bytes per launch / its average
                  duration measured with HIP events on the launch stream during the timed steps, vs 8 TB/s
   cpu_baseline : the oracle (a CPU restatement of the reference's fp32 training step) timed on this host
+and the batch sweep, SpatialNet-large, the narrow-band archs and the per-kernel milliseconds of the profiled warm-up steps.
+--dump-outputs DIR writes what the last timed step computed (loss, updated parameters, Adam moments) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -24,6 +27,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parent
@@ -289,7 +293,8 @@ def self_launch(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(Path(__file__).resolve()), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--batch", str(args.batch)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--dry-run"] if args.dry_run else [])
+           "--batch", str(args.batch)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--dry-run"] if args.dry_run else []) + \
+          (["--full"] if args.full else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
     # HSA_ENABLE_IPC_MODE_LEGACY=0: the images this runs on export it (the host driver supports dmabuf IPC only; without it RCCL's
     # hipIpcGetMemHandle fails between processes) — inherited when set, defaulted for shells that lost it; nothing else is altered
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
@@ -371,14 +376,28 @@ def large_train_rate(lib, dev, batch=4, steps=2):
         return {"error": str(e)[:200]}
 
 
+def dump_outputs(out_dir, ts, loss):
+    """what a caller of the timed path holds after its last step: the loss it returned, the parameters it updated and the Adam moments
+    (flat fp32, the engine's parameter order; 3 x 4.8 MB at SpatialNet-small).  The gradient itself is not among them: the optimizer
+    kernel re-zeroes it for the next step, and the moments carry it."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, t in (("loss", loss), ("params", ts.e.params), ("exp_avg", ts.m), ("exp_avg_sq", ts.v)):
+        np.save(out / f"{name}.npy", t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    # headline batch 32 (SURVEY.md §8(d) names B/GPU in {2, 8, 32}); the line also carries a short sweep over the other two
+    # headline batch 32 (SURVEY.md §8(d) names B/GPU in {2, 8, 32}); with --full the line also carries a short sweep over the other two
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: the roofline line only (no in-order child run, sweep, "
+                    "SpatialNet-large, narrow-band archs or CPU baseline)")
+    ap.add_argument("--full", action="store_true", help="also the roofline / per-kernel figures, the batch sweep, SpatialNet-large, the "
+                    "narrow-band archs and the CPU baseline (a plain run measures the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only rehearsal of the multi-process launch + gradient exchange (gloo); no measurement")
     args = ap.parse_args()
 
@@ -419,22 +438,24 @@ def main():
             torch.distributed.barrier()
             torch.cuda.synchronize()
 
-    # ---- warm-up (untimed); the first two steps are fully profiled to find the dominant kernel -------
+    # ---- warm-up (untimed); with --full the steps from the second on are fully profiled to find the dominant kernel -------
     nk = lib.nbss_profile_kernels()
-    losses, prof, nprof = [], None, 0
-    for i in range(max(args.warmup, 2)):
-        if i == 1:  # step 0 pays the one-time code-object loads: profile from step 1 on
+    losses, prof, nprof = [], {}, 0
+    dominant = dom_id = None
+    for i in range(max(args.warmup, 2) if args.full else args.warmup):
+        if args.full and i == 1:  # step 0 pays the one-time code-object loads: profile from step 1 on
             torch.cuda.synchronize()
             lib.nbss_profile_enable((1 << nk) - 1)
         losses.append(ts.step(x, yr))
         if i >= 1:
             nprof += 1
     torch.cuda.synchronize()
-    prof = profile_read(lib)
-    lib.nbss_profile_enable(0)
-    cand = {k: v for k, v in prof.items() if algorithmic_bytes(k, B) and v[1] > 0}
-    dominant = max(cand, key=lambda k: cand[k][0]) if cand else None
-    dom_id = [i for i in range(nk) if lib.nbss_profile_name(i).decode() == dominant][0] if dominant else None
+    if args.full:
+        prof = profile_read(lib)
+        lib.nbss_profile_enable(0)
+        cand = {k: v for k, v in prof.items() if algorithmic_bytes(k, B) and v[1] > 0}
+        dominant = max(cand, key=lambda k: cand[k][0]) if cand else None
+        dom_id = [i for i in range(nk) if lib.nbss_profile_name(i).decode() == dominant][0] if dominant else None
 
     # ---- timed region: EXACTLY --steps steps, events only around the dominant kernel ------------------
     if dom_id is not None:
@@ -447,12 +468,15 @@ def main():
         loss = ts.step(x, yr)
     sync()
     dt = time.perf_counter() - t0
-    lib.nbss_profile_enable(0)
+    if dom_id is not None:
+        lib.nbss_profile_enable(0)
+    if args.dump_outputs and rank == 0:  # (before --full's sweep below takes more steps on the same parameters)
+        dump_outputs(args.dump_outputs, ts, loss)
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt)
-    timed_prof = profile_read(lib)
+    timed_prof = profile_read(lib) if args.full else {}
     final_loss = float(loss)
     comm_ms, worlds = None, [1]
     if world > 1:
@@ -502,8 +526,8 @@ def main():
             # include whatever the gradient stream's launches cost the dominant kernel while they overlap it
             try:
                 env = dict(os.environ, NBSS_SIDE_STREAM="0")
-                r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "3", "--batch", str(B), "--no-cpu-baseline"], env=env,
-                                   capture_output=True, text=True, timeout=240)
+                r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "3", "--batch", str(B), "--full", "--no-cpu-baseline"],
+                                   env=env, capture_output=True, text=True, timeout=240)
                 child = json.loads(r.stdout.strip().splitlines()[-1])
                 io = child["roofline"]["all_kernels"][dominant]
                 roof["frac_in_order"] = io["frac"]
@@ -513,7 +537,7 @@ def main():
             except Exception as e:  # reported, never fatal
                 roof["frac_in_order"] = None
                 roof["in_order_error"] = str(e)[:200]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # utterances/s at the other per-GPU batches of SURVEY.md §8(d) (short runs: 3 warm-up + 8 timed steps each — with 1 + 3 the first steps
             # at a new shape (workspace re-sizing, allocator) weighed on the figure: batch 8 read 562 here against 585 in a run of its own)
             sweep = {str(B): round(B * args.steps / dt, 1)}
@@ -543,10 +567,11 @@ def main():
             "config": {"workload": "SpatialNet-small 6ch->2spk, 4-s 8-kHz utterances (32000 samples), n_fft 256/hop 128 (F=129, T=251), 8 layers, "
                                    f"full train step (STFT..Adam), bf16 stream + fp32 master/stats, {B} utterances per GPU per step", "batch_per_gpu": B, "global_batch": B * world,
                        "parallelism": f"dp{world}", "final_loss": final_loss},
-            "roofline": roof, "cpu_baseline": base, "utt_per_s_by_batch": sweep, "utt_per_s_large": large, "nb_archs": nb,
             "rccl_world": worlds, "comm_ms_per_step": comm_ms,
-            "kernel_ms_per_step": {k: round(v[0] / max(nprof, 1), 4) for k, v in prof.items() if v[1] > 0},
         }
+        if args.full:
+            line.update({"roofline": roof, "cpu_baseline": base, "utt_per_s_by_batch": sweep, "utt_per_s_large": large, "nb_archs": nb,
+                         "kernel_ms_per_step": {k: round(v[0] / max(nprof, 1), 4) for k, v in prof.items() if v[1] > 0}})
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -15,9 +15,6 @@ ROOT = Path(__file__).resolve().parent.parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-REFERENCE = Path("/root/reference")
-
-
 os.environ.setdefault("NBSS_POISON_SCRATCH", "1")  # scratch buffers start as NaN bytes in every test (nbss_amd/ops.py: scratch)
 
 
@@ -74,8 +71,3 @@ def backend(request):
     if request.param == "emu":
         return Backend("emu", request.getfixturevalue("emu_lib"), torch.device("cpu"))
     return Backend("hip", request.getfixturevalue("hip_lib"), torch.device("cuda:0"))
-
-
-@pytest.fixture(scope="session")
-def reference_available():
-    return (REFERENCE / "models" / "arch" / "SpatialNet.py").exists()

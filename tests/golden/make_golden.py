@@ -138,7 +138,85 @@ def bf16_reference_errors():
     print("written: bf16_reference_errors.json; L8 case: y", c["y"], "worst grads", worst)
 
 
+SKETCH_SEED = 11
+
+
+def sketch(t):
+    """[..., C] -> [..., 1]: the product with a fixed seeded fp64 random vector (tests/test_oracle_vs_reference.py applies the same)"""
+    return t @ torch.randn(t.shape[-1], 1, generator=torch.Generator().manual_seed(SKETCH_SEED), dtype=torch.float64)
+
+
+def oracle_pins():
+    """What tests/test_oracle_vs_reference.py and tests/test_gpu_simulation.py compare against (`python tests/golden/make_golden.py
+    oraclepin`): fp64 outputs of the reference's SpatialNet (small: whole network and the four sub-block methods of layer 3; large at
+    257 frequencies; a 3-layer network carrying seed-3 weights), its state_dict keys / shapes and its numpy diffuse-noise generator.
+    Parameters are not stored: this repo's drop-in SpatialNet draws the same ones from the same seed (a checksum per case pins that).
+    The sub-block outputs [1, 129, 30, 96] are stored as their product with a seeded fp64 [96, 1] random vector (SKETCH_SEED; 31 KB
+    each instead of 3 MB): the relative L2 error of such a projection follows that of the whole tensor, and no deviation of the oracle
+    can vanish in it except on a set of measure zero."""
+    import importlib.util
+    for m in [k for k in sys.modules if k == "models" or k.startswith("models.")]:
+        del sys.modules[m]
+    sys.path.insert(0, str(REF))
+    from models.arch.SpatialNet import SpatialNet  # noqa: E402  (reference)
+    assert str(REF) in sys.modules["models.arch.SpatialNet"].__file__
+    torch.set_num_threads(4)
+
+    def checksum(net):
+        return np.array([sum(float(v.double().sum()) for v in net.state_dict().values()),
+                         sum(float(v.double().abs().sum()) for v in net.state_dict().values())])
+
+    out = {}
+    small = dict(dim_input=12, dim_output=4, num_layers=8, dim_hidden=96, dim_ffn=192, num_heads=4, kernel_size=(5, 3), conv_groups=(8, 8),
+                 norms=("LN", "LN", "GN", "LN", "LN", "LN"), dim_squeeze=8, num_freqs=129, full_share=0)
+    torch.manual_seed(0)
+    net = SpatialNet(**small).double()
+    x = torch.randn(1, 129, 30, 12, dtype=torch.float64)
+    h = torch.randn(1, 129, 30, 96, dtype=torch.float64)
+    lay = net.layers[3]
+    lay.need_weights = False
+    with torch.no_grad():
+        out.update({"small/checksum": checksum(net), "small/y": net(x).numpy(), "small/fconv1": sketch(h + lay._fconv(lay.fconv1, h)).numpy(),
+                    "small/full": sketch(h + lay._full(h)).numpy(), "small/mhsa": sketch(h + lay._tsa(h, None)[0]).numpy(),
+                    "small/tconvffn": sketch(h + lay._tconvffn(h)).numpy()})
+    torch.manual_seed(1)
+    net = SpatialNet(**dict(small, num_layers=12, dim_hidden=192, dim_ffn=384, dim_squeeze=16, num_freqs=257)).double()
+    x = torch.randn(1, 257, 12, 12, dtype=torch.float64)
+    with torch.no_grad():
+        out.update({"large/checksum": checksum(net), "large/y": net(x).numpy()})
+    kw = dict(small, num_layers=3)
+    torch.manual_seed(3)
+    seed3 = SpatialNet(**kw)  # (= the drop-in module's seed-3 draw)
+    refnet = SpatialNet(**kw)
+    refnet.load_state_dict(seed3.state_dict(), strict=True)
+    torch.manual_seed(4)
+    SpatialNet(**kw)
+    x = torch.randn(1, 129, 12, 12, dtype=torch.float64)
+    sd = refnet.state_dict()
+    with torch.no_grad():
+        out.update({"sd/checksum": checksum(seed3), "sd/keys": np.array(list(sd)), "sd/shapes": np.array([str(tuple(v.shape)) for v in sd.values()]),
+                    "sd/y": refnet.double()(x).numpy()})
+    # the reference's numpy diffuse-noise generator on the mixing matrices of this repo's data_loaders/gpu_simulation.py
+    sys.path.insert(0, str(HERE.parent.parent))
+    from data_loaders import gpu_simulation as gs  # noqa: E402
+    spec = importlib.util.spec_from_file_location("ref_diffuse_noise", REF / "data_loaders" / "utils" / "diffuse_noise.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    pos = torch.tensor([[0.0, 0, 0], [0.05, 0, 0], [0.2, 0, 0]])
+    _, Cs = gs.diffuse_mixing_matrices(pos, 8000)
+    g = torch.Generator().manual_seed(2)
+    torch.randn(3, 160000, generator=g, dtype=torch.float64)  # (what the test draws first)
+    noise = torch.randn(3 * 4000, generator=g, dtype=torch.float64)
+    out["diffuse/noise"] = mod.gen_diffuse_noise(noise.numpy(), 4000, Cs.numpy(), nfft=256, rng=np.random.default_rng(0))
+    out["diffuse/dsc"] = mod.gen_desired_spatial_coherence(pos.numpy(), 8000)[0]
+    np.savez_compressed(HERE / "oracle_pins.npz", **out)
+    print("written: oracle_pins.npz", sum(v.nbytes for v in out.values()) // 1024, "KB uncompressed")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "oraclepin":
+        assert REF.exists(), "the reference tree is needed to (re)generate the fixtures"
+        return oracle_pins()
     if len(sys.argv) > 1 and sys.argv[1] == "bf16ref":
         assert REF.exists(), "the reference tree is needed to (re)generate the fixtures"
         return bf16_reference_errors()

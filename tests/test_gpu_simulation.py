@@ -47,18 +47,14 @@ def test_diffuse_noise_coherence_and_reference():
     coh01 = ((X[0] * X[1].conj()).mean(-1) / torch.sqrt(psd[0] * psd[1])).real
     k = torch.arange(4, 60)
     assert (coh01[k] - dsc[0, 1, k]).abs().mean() < 0.05  # measured coherence of the close pair follows sinc(w d / c)
-    ref = Path("/root/reference/data_loaders/utils/diffuse_noise.py")
-    if ref.exists():  # the reference's own generator on the same noise and matrices (it cuts a random start: use exact-length noise)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("ref_diffuse_noise", ref)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        noise = torch.randn(3 * 4000, generator=g, dtype=torch.float64)
-        want = mod.gen_diffuse_noise(noise.numpy(), 4000, Cs.numpy(), nfft=256, rng=np.random.default_rng(0))
-        got = gs.gen_diffuse_noise(noise.reshape(3, 4000), 4000, Cs)
-        assert np.abs(got.numpy() - want).max() < 1e-8 * max(1.0, np.abs(want).max())
-        dsc_ref, Cs_ref = mod.gen_desired_spatial_coherence(pos.numpy(), 8000)
-        assert np.abs(dsc_ref - dsc.numpy()).max() < 1e-12
+    # the reference's own generator on the same noise and matrices (it cuts a random start: exact-length noise), as stored by
+    # tests/golden/make_golden.py oraclepin
+    pins = np.load(Path(__file__).resolve().parent / "golden" / "oracle_pins.npz")
+    noise = torch.randn(3 * 4000, generator=g, dtype=torch.float64)
+    want = pins["diffuse/noise"]
+    got = gs.gen_diffuse_noise(noise.reshape(3, 4000), 4000, Cs)
+    assert np.abs(got.numpy() - want).max() < 1e-8 * max(1.0, np.abs(want).max())
+    assert np.abs(pins["diffuse/dsc"] - dsc.numpy()).max() < 1e-12
 
 
 def test_loader_contract_and_determinism():

@@ -1,16 +1,17 @@
 #!/bin/bash
-# A short GPU-box call: the -m gpu suite, the default bench line, a rocprofv3 --stats summary and the PMC passes of a few kernels.
+# A short GPU-box call: the -m gpu suite, the bench.py --full line, a rocprofv3 --stats summary and the PMC passes of a few kernels.
 #   tools/gpu_quick.sh <tag> [pytest-args]      NBSS_PMC_KERNELS="tconvffn_bwd mhsa_bwd" selects the PMC passes ("" = none)
 TAG=${1:-r02q}
 shift
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-bench_out}; mkdir -p $OUT  # (the bench.py --full line)
 mkdir -p gpurun_out
 timeout 900 python -m pytest tests -m gpu -q -x "$@" > gpurun_out/${TAG}_pytest_gpu.log 2>&1; tail -3 gpurun_out/${TAG}_pytest_gpu.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-timeout 400 python bench.py 2> gpurun_out/${TAG}_bench.err | tail -1 > gpurun_out/${TAG}_bench.json; cut -c1-300 gpurun_out/${TAG}_bench.json
+timeout 400 python bench.py --full 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json; cut -c1-300 $OUT/${TAG}_bench.json
 python - <<PY
 import json
-b = json.loads(open("gpurun_out/${TAG}_bench.json").read())
+b = json.loads(open("$OUT/${TAG}_bench.json").read())
 print(b["value"], b["utt_per_s_by_batch"], b["cpu_baseline"] and b["cpu_baseline"]["value"])
 print(json.dumps(b["kernel_ms_per_step"]))
 PY

@@ -1,11 +1,12 @@
 #!/bin/bash
 # Round-5 collection at the final kernel sources, one GPU-box call:  NBSS_COMMIT=<short hash> tools/r05_final.sh <tag>
-#   default bench line (cpu_baseline, batch sweep and SpatialNet-large inside), kernel traces in order / two streams, batch sweep, the rows around
+#   bench.py --full line (cpu_baseline, batch sweep and SpatialNet-large inside), kernel traces in order / two streams, batch sweep, the rows around
 #   the path (simulator, online step, NBC2), the large step's trace, then — LAST (a bench after --pmc passes ran 12 % slower on this pool) — the PMC passes
 #   of every sub-block kernel, patched into the saved bench line
 TAG=${1:-r05f}
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-timeout 600 python bench.py 2> gpurun_out/${TAG}_bench.err | tail -1 > gpurun_out/${TAG}_bench.json; cut -c1-300 gpurun_out/${TAG}_bench.json
+OUT=${OUT:-bench_out}; mkdir -p $OUT  # (the bench.py --full line)
+timeout 600 python bench.py --full 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json; cut -c1-300 $OUT/${TAG}_bench.json
 bash tools/r05_trace.sh ${TAG} > /dev/null 2>&1; head -14 gpurun_out/${TAG}_rocprof_inorder.md | tail -6 | cut -c1-110
 for b in 2 4 8 16 31 32 48; do timeout 120 python bench.py --steps 5 --warmup 3 --batch $b --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(d['config']['batch_per_gpu'], round(d['value'],1), 'utt/s', round(d['ms_per_step'],2), 'ms/step')"; done | tee gpurun_out/${TAG}_batch_sweep.txt
@@ -19,7 +20,7 @@ bash tools/pmc_traffic.sh 32 > /dev/null 2>&1; python tools/pmc_traffic.py 32 | 
 bash tools/pmc_mfma.sh 32 > /dev/null 2>&1; python tools/pmc_mfma.py 32 | tail -12; rm -rf gpurun_out/mfma
 python - <<PY
 import json
-b = json.loads(open("gpurun_out/${TAG}_bench.json").read())
+b = json.loads(open("$OUT/${TAG}_bench.json").read())
 t = json.load(open("gpurun_out/pmc_traffic.json"))
 k = b["roofline"]["kernel"]
 if t.get("batch") == b["config"]["batch_per_gpu"] and k in t["kernels"]:
@@ -30,6 +31,6 @@ if t.get("batch") == b["config"]["batch_per_gpu"] and k in t["kernels"]:
 m = json.load(open("gpurun_out/pmc_mfma.json"))
 if k in m["kernels"]:
     b["roofline"]["mfma_util"] = m["kernels"][k]["mfma_busy_frac"]
-open("gpurun_out/${TAG}_bench.json", "w").write(json.dumps(b) + "\n")
+open("$OUT/${TAG}_bench.json", "w").write(json.dumps(b) + "\n")
 print("dominant", k, "frac", b["roofline"]["frac"], "traffic", b["roofline"]["traffic"], "stale", b["roofline"]["traffic_stale"])
 PY
