@@ -232,14 +232,8 @@ static size_t stream_bytes(const nbss_cfg& c) {
     return ws_align((size_t)c.B * c.F * c.T * c.H * (c.dtype == NBSS_BF16 ? 2 : 4));
 }
 
-// saved state of the whole network: [5L+1 block inputs | L attention saves | L T-ConvFFN saves (bf16 stream; NBSS_TCF_RECOMPUTE flavour: none)]
-static size_t tcf_save_bytes(const nbss_cfg& c) {
-#ifdef NBSS_TCF_RECOMPUTE
-    return 0;
-#else
-    return ws_align(tconvffn_save_bytes(c));
-#endif
-}
+// saved state of the whole network: [5L+1 block inputs | L attention saves | L T-ConvFFN saves (bf16 stream)]
+static size_t tcf_save_bytes(const nbss_cfg& c) { return ws_align(tconvffn_save_bytes(c)); }
 static size_t acts_tcf_offset(const nbss_cfg& c) { return (size_t)(5 * c.L + 1) * stream_bytes(c) + (size_t)c.L * mhsa_save_bytes(c); }
 
 int64_t nbss_acts_bytes(const nbss_cfg* cfg) {
@@ -262,7 +256,6 @@ struct SideState {
     int state = 0;  // 0 = not tried, 1 = ready, -1 = unavailable / switched off (NBSS_SIDE_STREAM=0): in order
     int device = -1;
     Side sd;
-    hipStream_t gs_low;  // the gradient stream of small grids
     hipEvent_t done[BWD_KINDS], join;
     int ncu = 256;
 };
@@ -284,12 +277,9 @@ static SideState* side_state(hipStream_t st = nullptr) {
         s.device = dev;
         const char* env = getenv("NBSS_SIDE_STREAM");
         if (env && env[0] == '0') return nullptr;
-        // two gradient streams: default priority, and the LOWEST one for small grids (below 8 rounds of row-kernel workgroups) — measured on one
-        // box, default vs lowest: batch 2 342 -> 346 utt/s, batch 8 528 -> 534, batch 32 628 -> 617 (there the delayed folds end up behind the join)
-        int lo = 0, hi = 0;
-        const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi;
+        // the gradient stream runs at the default priority at every grid size (rounds 4-5 gave grids below 8 rounds of row-kernel workgroups a
+        // lowest-priority stream; round 6, same call, none: batch 2 373.5 / 375.6 -> 378.3 / 378.0 utt/s, batch 8 630.6 / 629.8 -> 632.6 / 634.4)
         bool ok = hipStreamCreateWithFlags(&s.sd.gs, hipStreamNonBlocking) == hipSuccess;
-        ok = ok && (prio ? hipStreamCreateWithPriority(&s.gs_low, hipStreamNonBlocking, lo) : hipStreamCreateWithFlags(&s.gs_low, hipStreamNonBlocking)) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.sd.ready, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.join, hipEventDisableTiming) == hipSuccess;
         for (int k = 0; ok && k < BWD_KINDS; ++k) ok = hipEventCreateWithFlags(&s.done[k], hipEventDisableTiming) == hipSuccess;
@@ -383,17 +373,7 @@ int nbss_spatialnet_bwd_range(const nbss_cfg* cfg, const float* params, float* g
     int e;
 #ifndef NBSS_EMU
     SideState* ss = side_state(st);
-    Side side;
-    if (ss) {
-        side = ss->sd;
-#ifndef NBSS_GSLOW_ROUNDS
-#define NBSS_GSLOW_ROUNDS 0  // the lowest-priority gradient stream for grids below this many rounds of row-kernel workgroups: none any more (rounds 4-5: 8 — then
-                            // +1 % at batch 2 / 8; round 6, same call, 8 -> 0: batch 2 373.5 / 375.6 -> 378.3 / 378.0 utt/s, batch 8 630.6 / 629.8 -> 632.6 / 634.4;
-                            // 8 -> 40: batch 16 and 32 unchanged)
-#endif
-        if (c.B * c.F < NBSS_GSLOW_ROUNDS * ss->ncu) side.gs = ss->gs_low;
-    }
-    const Side* sd = ss ? &side : nullptr;
+    const Side* sd = ss ? &ss->sd : nullptr;
     bool rec[BWD_KINDS] = {false, false, false, false, false};
     int reader[3] = {-1, -1, -1};  // kind whose gradient-stream launches read buffer b (as their dy)
     // before sub-block `kind` writes buffer `out`: its own workspace copy and that buffer must be free of gradient-stream readers
@@ -407,7 +387,7 @@ int nbss_spatialnet_bwd_range(const nbss_cfg* cfg, const float* params, float* g
     };
     auto after = [&](int kind, int in) {
         if (!ss) return;
-        ev_ok = ev_ok && hipEventRecord(ss->done[kind], side.gs) == hipSuccess;
+        ev_ok = ev_ok && hipEventRecord(ss->done[kind], sd->gs) == hipSuccess;
         rec[kind] = true;
         if (in >= 0) reader[in] = kind;  // (only the T-ConvFFN's W2 and the attention's out_proj problems contract against the upstream gradient)
     };
@@ -442,7 +422,7 @@ int nbss_spatialnet_bwd_range(const nbss_cfg* cfg, const float* params, float* g
     }
 #ifndef NBSS_EMU
     // join: the caller's next work on `st` (the gradient all-reduce of this range, the optimizer) sees every parameter gradient
-    if (ss && (hipEventRecord(ss->join, side.gs) != hipSuccess || hipStreamWaitEvent(st, ss->join, 0) != hipSuccess)) return NBSS_ELAUNCH;
+    if (ss && (hipEventRecord(ss->join, sd->gs) != hipSuccess || hipStreamWaitEvent(st, ss->join, 0) != hipSuccess)) return NBSS_ELAUNCH;
 #endif
     return layer_lo == 0 ? encoder_bwd_impl(c, grads, xin, gbuf(j), wsk(0), st) : NBSS_OK;
 }

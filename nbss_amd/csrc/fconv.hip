@@ -100,7 +100,7 @@ NBSS_DEV void ln_halfrow_inplace(T* row, const float* __restrict__ gamma, const 
 // MTF = frequency tiles the accumulators are sized for: 10 (F <= 160, the 8-kHz geometry) or 17 (F <= 272: 16 kHz, n_fft 512 -> 257 bins)
 // HH = dim_hidden (geom.h): 96 (12 channels per conv group, one 16-row output tile) or 192 (24 channels, two tiles)
 template <class T, int TT, int GPW, int MTF, int HH>
-// (launch bounds: threads, waves per SIMD — four = two 8-wave workgroups per CU, at most 128 VGPRs; -DNBSS_FCONV_DMA: A/B flavour, rounds 4-5's prologue)
+// (launch bounds: threads, waves per SIMD — four = two 8-wave workgroups per CU, at most 128 VGPRs)
 __global__ __launch_bounds__(64 * FC_G / GPW, GPW == 1 ? (MTF <= 10 && HH == 96 ? 4 : 2) : 1) void fconv_fwd_kernel(
                                                         nbss_cfg c, const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                         const float* __restrict__ cb, const float* __restrict__ slope,
@@ -124,14 +124,10 @@ __global__ __launch_bounds__(64 * FC_G / GPW, GPW == 1 ? (MTF <= 10 && HH == 96 
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
 
     // ---- phase 1: stage x (raw) into LDS rows f+2, zero halo / tail rows -------------------
-#ifdef NBSS_FCONV_DMA
-    constexpr bool DMA = sizeof(T) == 2, REGX = false;
-#else
-    constexpr bool DMA = false, REGX = sizeof(T) == 2;
-#endif
+    constexpr bool REGX = sizeof(T) == 2;
     // bf16 stream (round 6): the slab's rows come in through REGISTERS — every thread requests its 16-byte pieces up front (one round trip), copies
-    // them into the image, and KEEPS them: they are the residual of phase 4.  With the LDS-DMA prologue (no register stop) the image was normalised in
-    // place and the residual re-read from global memory — the kernel fetched 2.26 x the slab (PMC, round 5), on a kernel that runs at the HBM rate.
+    // them into the image, and KEEPS them: they are the residual of phase 4.  With rounds 4-5's LDS-DMA prologue (no register stop) the image was normalised
+    // in place and the residual re-read from global memory — the kernel fetched 2.26 x the slab (PMC, round 5), on a kernel that runs at the HBM rate.
     // (six rounds of the workgroup's threads = 3 072 of the 3 096 pieces of a 129-bin slab; the few pieces beyond them take the old path: copied in a
     //  load -> store loop and re-read in phase 4 — registers for the largest slab the instance admits would be 8 - 13 rounds, over the 128-VGPR budget)
     constexpr int NTHR = 64 * FC_G / GPW, NXR = REGX ? 6 : 1;
@@ -158,26 +154,6 @@ __global__ __launch_bounds__(64 * FC_G / GPW, GPW == 1 ? (MTF <= 10 && HH == 96 
             if (t0 + tt < T_) vec_copy(d, x + (((size_t)b * F + f) * T_ + t0) * HH + off);
             else vec_zero(d);
         }
-    } else if constexpr (DMA) {
-        // bf16 stream: the slab comes in as one burst of global -> LDS copies (16-byte pieces, no register stop; the copy loop below is a chain
-        // of load -> store round trips, seven per thread).  Piece q: row q / CPR (= f TT + tt), 16-byte column q % CPR (the last one is padding).
-        constexpr int CPR = HHP / 8, DPR = HH / 8;
-        const int wu = wave_id_u(), Q = F * TT * CPR, nw = nthr / 64;
-        for (int i = wu; i * 64 < Q; i += nw) {
-            const int q = i * 64 + lane, r = q / CPR, cc = q - r * CPR, f = r / TT, tt = r - f * TT;
-            if (q < Q && cc < DPR && t0 + tt < T_)
-                dma16_to_lds(reinterpret_cast<char*>(u + 2 * ROW) + (size_t)i * 1024, x + (((size_t)b * F + f) * T_ + t0 + tt) * HH + cc * 8);
-        }
-        for (int i = tid; i < (FP - F) * VPR; i += nthr) {  // halo rows (f = -2, -1) and the rows behind the last frequency
-            const int k = i / VPR, rr = k < 2 ? k : F + k, off = (i % VPR) * VN, tt = off / HH;
-            vec_zero(u + (size_t)rr * ROW + tt * HHP + (off - tt * HH));
-        }
-        if (t0 + TT > T_)  // a slab that ends the sequence: its missing frames are zero rows
-            for (int i = tid; i < F * VPR; i += nthr) {
-                const int f = i / VPR, off = (i % VPR) * VN, tt = off / HH;
-                if (t0 + tt >= T_) vec_zero(u + (size_t)(f + 2) * ROW + tt * HHP + (off - tt * HH));
-            }
-        dma_wait_all();
     } else {
     for (int i = tid; i < FP * VPR; i += nthr) {
         const int rr = i / VPR, off = (i % VPR) * VN, f = rr - 2, tt = off / HH;
@@ -297,33 +273,6 @@ __global__ __launch_bounds__(64 * FC_G / GPW, GPW == 1 ? (MTF <= 10 && HH == 96 
             for (int j = 0; j < 8; ++j) o[j] = xv[j] + yv[j];
             store8(reinterpret_cast<bf16_t*>(y) + go, o);
         }
-    } else if constexpr (DMA) {  // (VN == 8) the residual rows of up to eight iterations are requested together: one round trip per batch instead of one per row
-        constexpr int NB4 = 8;
-        for (int i0 = tid; i0 < F * VPR; i0 += NB4 * nthr) {
-            u32x4 xr4[NB4];
-#pragma unroll
-            for (int k = 0; k < NB4; ++k) {
-                const int i = i0 + k * nthr, ic = i < F * VPR ? i : F * VPR - 1, f = ic / VPR, off = (ic % VPR) * VN, tt = off / HH;
-                const int ttc = t0 + tt < T_ ? tt : 0;  // (clamped address: the value is not used)
-                xr4[k] = *reinterpret_cast<const u32x4*>(x + (((size_t)b * F + f) * T_ + t0 + ttc) * HH + (off - tt * HH));
-            }
-#pragma unroll
-            for (int k = 0; k < NB4; ++k) {
-                const int i = i0 + k * nthr;
-                if (i >= F * VPR) continue;
-                const int f = i / VPR, off = (i % VPR) * VN, tt = off / HH;
-                if (t0 + tt >= T_) continue;
-                const size_t go = (((size_t)b * F + f) * T_ + t0) * HH + off;
-                float yv[8], o[8];
-                load8(u + (size_t)f * ROW + tt * HHP + (off - tt * HH), yv);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[2 * j] = bf2f((bf16_t)(xr4[k][j] & 0xFFFF)) + yv[2 * j];
-                    o[2 * j + 1] = bf2f((bf16_t)(xr4[k][j] >> 16)) + yv[2 * j + 1];
-                }
-                store8(reinterpret_cast<bf16_t*>(y) + go, o);
-            }
-        }
     } else
     for (int i = tid; i < F * VPR; i += nthr) {
         const int f = i / VPR, off = (i % VPR) * VN, tt = off / HH;
@@ -367,18 +316,18 @@ NBSS_DEV void fconv_bfrag(Frag<T>& bq, const T* __restrict__ u, int rstride, int
     else frag_zero_hi(bq);
 }
 
-// NW = waves per workgroup: 8 (= the conv groups), or 9 when the row phases have a multiple of 9 units (F = 129: 9 frequency tiles x 2
-// frames = 18 units, which 8 waves take in 3 rounds with 6 of them idle in the last); the ninth wave sits out the group phases.
-// WGF: the conv weight gradient is contracted here too (bf16, TT = 2): between phase 1 and phase 2 both of its operands — dv and LN(x) — sit
+// One frame per workgroup (TT = 1), one wave per conv group (NW = 8).
+// WGF: the conv weight gradient is contracted here too (bf16, F <= 160): between phase 1 and phase 2 both of its operands — dv and LN(x) — sit
 // in the two LDS images as row-major [frequency][channel] arrays, which is what a token-contraction needs: transposing reads give MFMA
 // fragments with K = 32 frequencies, wave g accumulates dW[g][12 x 12] per tap (5 tiles) + the bias column sums, and the workgroup's partial
 // goes out as one row (the whole [96][12][5] weight + [96] bias in dW's own memory order) behind its affine sums; affine_reduce folds the rows.
 // The separate path wrote dv (S) and had wgrad.hip read dv + x (2 S) again: 0.6 GB per f-conv at batch 32 against 2 x 94 MB of partial rows.
-template <class T, int TT, int NW, bool WGF>
-__global__ __launch_bounds__(64 * NW, NW > 8 ? 3 : 2)  // (9 waves: one SIMD hosts three of them -> at most 168 VGPRs)
+template <class T, bool WGF>
+__global__ __launch_bounds__(64 * FC_G, 2)
 void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __restrict__ lnb, const float* __restrict__ cb,
                       const float* __restrict__ slope, float* __restrict__ part, const T* __restrict__ Wp, const T* __restrict__ WpT,
                       const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, float* __restrict__ stats, T* __restrict__ dvout, int flip) {
+    constexpr int TT = 1, NW = FC_G;
     NBSS_LDS(smem);
     const int F = c.F, T_ = c.T, ntt = cdiv(T_, TT);
     const int bid = flip_bid(flip);
@@ -393,19 +342,14 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
                                                  // added in wave order at the end (LDS float atomics made the partial row depend on the wave timing)
     PHASE_BEGIN(affw + NW * 2 * FC_H);
     const int tid = threadIdx.x, lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
-#ifdef NBSS_FCONV_NO_DMA  // (A/B flavour)
-    constexpr bool DMA = false;
-#else
     constexpr bool DMA = sizeof(T) == 2;  // bf16 stream: the slab arrives through global -> LDS copies (phase 0)
-#endif
 
     Frag<T> af[FC_KS], at[FC_KS];
 #pragma unroll
     for (int ks = 0; ks < FC_KS; ++ks) {
-        wfrag_load(af[ks], Wp, w < FC_G ? w : 0, FC_KS, ks);
+        wfrag_load(af[ks], Wp, w < FC_G ? w : 0, FC_KS, ks);  // (the clamp is a no-op that the compiler cannot see: kept, the code stays as measured)
         wfrag_load(at[ks], WpT, w < FC_G ? w : 0, FC_KS, ks);
     }
-    const bool gwave = NW == FC_G || w < FC_G;  // this wave owns a conv group in the group phases
     for (int i = tid; i < 3 * FC_H; i += blockDim.x) aff[i] = 0.f;
     for (int i = tid; i < NW * 2 * FC_H; i += blockDim.x) affw[i] = 0.f;
     for (int i = tid; i < 2 * FC_H; i += blockDim.x) lnp[i] = i < FC_H ? lnw[i] : lnb[i - FC_H];
@@ -478,8 +422,6 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
     };
     Frag<T> xr[BK_KS], dr[BK_KS];
     float rmean = 0.f, rrstd = 0.f;
-    constexpr bool PF = false;
-    Frag<T> xr2[BK_KS], dr2[BK_KS];
     if constexpr (DMA) {
         // bf16 stream: the whole slab of x and dy comes in as ONE burst of global -> LDS copies (16-byte pieces, no register stop), raw x into the
         // u image and dy into the dvb image — one memory round trip per workgroup instead of one per unit of a wave (a wave walks its two units
@@ -531,20 +473,12 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
         }
     } else {
     if (w < ntile) row_load(w, xr, dr);
-    // the wave's second unit is requested together with the first (bf16 stream: the row phases are bound by exposed HBM latency)
-    // (measured: 6.69 -> 7.18 ms/step with the prefetch on — 168 VGPRs and twice the loads in flight ahead of the LN phase; kept off)
-    if (PF && w + NW < ntile) row_load(w + NW, xr2, dr2);
     lds_barrier();  // lnp
     if (w < ntile) {
         row_stats(xr, rmean, rrstd);
         row_fwd(w, xr, dr, rmean, rrstd);
     }
-    if (PF && w + NW < ntile) {
-        float mean, rstd;
-        row_stats(xr2, mean, rstd);
-        row_fwd(w + NW, xr2, dr2, mean, rstd);
-    }
-    for (int ti = w + (PF ? 2 : 1) * NW; ti < ntile; ti += NW) {
+    for (int ti = w + NW; ti < ntile; ti += NW) {
         Frag<T> xq[BK_KS], dq[BK_KS];
         float mean, rstd;
         row_load(ti, xq, dq);
@@ -558,13 +492,13 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
 
     // ---- phase 1 (groups): conv forward recompute, PReLU', dv in place of dy ----
     const int ch = w * FC_CG + 4 * g4;  // this lane's 4 channels of group w (g4 == 3: padding rows)
-    const bool cvalid = g4 < 3 && gwave;
+    const bool cvalid = g4 < 3;
     float cbv[4] = {0.f, 0.f, 0.f, 0.f}, slv[4] = {0.f, 0.f, 0.f, 0.f}, dsl[4] = {0.f, 0.f, 0.f, 0.f};
     if (cvalid) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { cbv[r] = cb[ch + r]; slv[r] = slope[ch + r]; }
     }
-    for (int ti = 0; ti < (gwave ? ntile : 0); ++ti) {
+    for (int ti = 0; ti < ntile; ++ti) {
         const int ft = ti / TT, tt = ti % TT, f = ft * 16 + l15;
         f32x4 acc = F32X4_ZERO;
 #pragma unroll
@@ -598,58 +532,52 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
     constexpr int PROW = 4 * FC_H;  // floats per fp32 partial row: the three affine sums + the conv bias sums (layout.h NBSS_FC_PROW); the bf16 rows follow all of them
     if constexpr (WGF) {
         // ---- weight gradient of group w: dW[o][i][tap] = sum_{f,tt} dv[f][o] LN(x)[f + tap - 2][i], db[o] = sum dv[f][o] ----
-        if (gwave) {
-            f32x4 wacc[5], bsum = F32X4_ZERO;
+        f32x4 wacc[5], bsum = F32X4_ZERO;
 #pragma unroll
-            for (int tap = 0; tap < 5; ++tap) wacc[tap] = F32X4_ZERO;
-            Frag<T> ones;
+        for (int tap = 0; tap < 5; ++tap) wacc[tap] = F32X4_ZERO;
+        Frag<T> ones;
 #pragma unroll
-            for (int jq = 0; jq < 8; ++jq) frag_set(ones, jq, 1.0f);
-            const int nk = cdiv(mtf * 16, 32);
-            const bool odd = (mtf & 1) != 0;  // the last k-step has 16 real rows: the upper halves of the fragments are cleared
-            const int roff = (4 * g4 + (l15 >> 2)) * ROW + w * FC_CG + 4 * (l15 & 3);
-            for (int tt = 0; tt < TT; ++tt)
-                for (int ks = 0; ks < nk; ++ks) {
-                    const bool half = odd && ks == nk - 1;
-                    Frag<T> fa;
-                    frag_load_tr(fa, dvb + (size_t)(2 + 32 * ks) * ROW + tt * FC_LD + roff, ROW);
-                    if (half) frag_zero_hi(fa);
-                    bsum = mma(fa, ones, bsum);
-#pragma unroll
-                    for (int tap = 0; tap < 5; ++tap) {
-                        Frag<T> fb;
-                        frag_load_tr(fb, u + (size_t)(32 * ks + tap) * ROW + tt * FC_LD + roff, ROW);
-                        if (half) frag_zero_hi(fb);
-                        wacc[tap] = mma(fa, fb, wacc[tap]);
-                    }
-                }
-            // C tile: lane = input channel i (l15), rows = output channels 4 g4 + r; valid 12 x 12.  The workgroup's partial of the weight gradient leaves in
-            // bf16 as [tap][group][i][12 outputs] — a lane's four output channels are ONE 8-byte store and a wave's store instruction covers one contiguous
-            // 288-byte run (round 6; rounds 2-5: fp32 in dW's own [o][i][tap] order = twenty scattered 4-byte stores per lane, 68 of the launch's 335 us
-            // with the stores knocked out).  Only the per-slab partial is rounded (under the reference's autocast the weight gradient of a bf16 convolution
-            // IS a bf16 tensor); the sum over the B T slabs is fp32 (fconv_part_final_kernel).  The bias sums stay fp32, in the row's head.
-            bf16_t* prow16 = reinterpret_cast<bf16_t*>(part + (size_t)gridDim.x * PROW) + (size_t)bid * FC_P16;
-            float* pb = part + (size_t)bid * PROW + 3 * FC_H;
-#ifdef NBSS_FC_KO_PROW  // (timing knock-out, A/B flavour: no partial-row stores; the contraction stays: the compiler cannot see that `part` is never null)
-            if (part == nullptr) {
-#else
-            if (l15 < FC_CG && g4 < 3) {
-#endif
+        for (int jq = 0; jq < 8; ++jq) frag_set(ones, jq, 1.0f);
+        const int nk = cdiv(mtf * 16, 32);
+        const bool odd = (mtf & 1) != 0;  // the last k-step has 16 real rows: the upper halves of the fragments are cleared
+        const int roff = (4 * g4 + (l15 >> 2)) * ROW + w * FC_CG + 4 * (l15 & 3);
+        for (int tt = 0; tt < TT; ++tt)
+            for (int ks = 0; ks < nk; ++ks) {
+                const bool half = odd && ks == nk - 1;
+                Frag<T> fa;
+                frag_load_tr(fa, dvb + (size_t)(2 + 32 * ks) * ROW + tt * FC_LD + roff, ROW);
+                if (half) frag_zero_hi(fa);
+                bsum = mma(fa, ones, bsum);
 #pragma unroll
                 for (int tap = 0; tap < 5; ++tap) {
-                    const u32x2 v = {pack2bf(wacc[tap][0], wacc[tap][1]), pack2bf(wacc[tap][2], wacc[tap][3])};
-                    *reinterpret_cast<u32x2*>(prow16 + ((size_t)(tap * FC_G + w) * FC_CG + l15) * FC_CG + 4 * g4) = v;
+                    Frag<T> fb;
+                    frag_load_tr(fb, u + (size_t)(32 * ks + tap) * ROW + tt * FC_LD + roff, ROW);
+                    if (half) frag_zero_hi(fb);
+                    wacc[tap] = mma(fa, fb, wacc[tap]);
                 }
-                if (l15 == 0) {
+            }
+        // C tile: lane = input channel i (l15), rows = output channels 4 g4 + r; valid 12 x 12.  The workgroup's partial of the weight gradient leaves in
+        // bf16 as [tap][group][i][12 outputs] — a lane's four output channels are ONE 8-byte store and a wave's store instruction covers one contiguous
+        // 288-byte run (round 6; rounds 2-5: fp32 in dW's own [o][i][tap] order = twenty scattered 4-byte stores per lane, 68 of the launch's 335 us
+        // with the stores knocked out).  Only the per-slab partial is rounded (under the reference's autocast the weight gradient of a bf16 convolution
+        // IS a bf16 tensor); the sum over the B T slabs is fp32 (fconv_part_final_kernel).  The bias sums stay fp32, in the row's head.
+        bf16_t* prow16 = reinterpret_cast<bf16_t*>(part + (size_t)gridDim.x * PROW) + (size_t)bid * FC_P16;
+        float* pb = part + (size_t)bid * PROW + 3 * FC_H;
+        if (l15 < FC_CG && g4 < 3) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pb[w * FC_CG + 4 * g4 + r] = bsum[r];
-                }
+            for (int tap = 0; tap < 5; ++tap) {
+                const u32x2 v = {pack2bf(wacc[tap][0], wacc[tap][1]), pack2bf(wacc[tap][2], wacc[tap][3])};
+                *reinterpret_cast<u32x2*>(prow16 + ((size_t)(tap * FC_G + w) * FC_CG + l15) * FC_CG + 4 * g4) = v;
+            }
+            if (l15 == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pb[w * FC_CG + 4 * g4 + r] = bsum[r];
             }
         }
     }
 
     // ---- phase 2 (groups): transposed conv -> du into the u image; dv rows -> global ----
-    for (int ti = 0; ti < (gwave ? ntile : 0); ++ti) {
+    for (int ti = 0; ti < ntile; ++ti) {
         const int ft = ti / TT, tt = ti % TT, f = ft * 16 + l15;
         f32x4 acc = F32X4_ZERO;
 #pragma unroll
@@ -747,14 +675,8 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
             }
         }
     };
-    if (PF && w + NW < ntile) row_load(w + NW, xr2, dr2);  // requested before the first unit's LayerNorm backward
     if (w < ntile) row_bwd(w, xr, dr, rmean, rrstd);
-    if (PF && w + NW < ntile) {
-        float mean, rstd;
-        row_stats(xr2, mean, rstd);
-        row_bwd(w + NW, xr2, dr2, mean, rstd);
-    }
-    for (int ti = w + (PF ? 2 : 1) * NW; ti < ntile; ti += NW) {
+    for (int ti = w + NW; ti < ntile; ti += NW) {
         Frag<T> xq[BK_KS], dq[BK_KS];
         float mean, rstd;
         row_load(ti, xq, dq);
@@ -774,34 +696,29 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
 }
 PHASE_READER(nbss_phase_read_fconv_bwd)
 
-template <class T, int TT, int NW, bool WGF>
+template <class T, bool WGF>
 static int fconv_bwd_t(const nbss_cfg& c, const float* P, float* part, const void* packed, int layer, int which, const void* x, const void* dy, void* dx,
                        float* stats, void* dv, hipStream_t st) {
     const int mtf = cdiv(c.F, 16);
     if (mtf > FC_MTF_BIG) return NBSS_EUNSUPPORTED;
-    const size_t lds = (size_t)2 * (mtf * 16 + 4) * TT * FC_LD * sizeof(T) + (5 + 2 * NW) * FC_H * sizeof(float) + PHASE_LDS_BYTES;
+    const size_t lds = (size_t)2 * (mtf * 16 + 4) * FC_LD * sizeof(T) + (5 + 2 * FC_G) * FC_H * sizeof(float) + PHASE_LDS_BYTES;
     if (lds > 160 * 1024) return NBSS_EUNSUPPORTED;
     const int lw = which ? P_FC2_LN_W : P_FC1_LN_W, lb = which ? P_FC2_LN_B : P_FC1_LN_B, sl = which ? P_FC2_PRELU : P_FC1_PRELU;
     const T* pk = (const T*)packed;
-    int e = NBSS_SET_MAX_LDS((fconv_bwd_kernel<T, TT, NW, WGF>), lds);
+    int e = NBSS_SET_MAX_LDS((fconv_bwd_kernel<T, WGF>), lds);
     if (e) return e;
-    dim3 grid(c.B * cdiv(c.T, TT)), block(64 * NW);
+    dim3 grid(c.B * c.T), block(64 * FC_G);
     ProfScope ps(PK_FCONV_B, st);
-    NBSS_LAUNCH((fconv_bwd_kernel<T, TT, NW, WGF>), grid, block, lds, st, c, P + param_off(c, layer, lw), P + param_off(c, layer, lb),
+    NBSS_LAUNCH((fconv_bwd_kernel<T, WGF>), grid, block, lds, st, c, P + param_off(c, layer, lw), P + param_off(c, layer, lb),
                 P + param_off(c, layer, which ? P_FC2_B : P_FC1_B), P + param_off(c, layer, sl), part, pk + pack_off(c, layer, which ? K_FC2 : K_FC1),
                 pk + pack_off(c, layer, which ? K_FC2_T : K_FC1_T), (const T*)x, (const T*)dy, (T*)dx, stats, (T*)dv, walk_flip_next());
     return NBSS_CHECK_LAUNCH();
 }
 
-// frames per workgroup of the bf16 backward.  Round 5: ONE — the images are 62 KB, the 8-wave instance holds 122 VGPRs: two workgroups share a CU and one's
+// frames per workgroup of the backward.  Round 5: ONE — the images are 62 KB, the 8-wave instance holds 122 VGPRs: two workgroups share a CU and one's
 // prologue (the slab's memory round trip, a third of the wave time) overlaps the other's math: 403 -> 294 us per launch in order, the step 657 -> 688 utt/s
-// (same box).  (Rounds 1-4 ran two frames per workgroup, one per CU: measured 2.2x better in round 1, before the LDS-DMA prologue and the fused weight gradient;
-// -DNBSS_FC_TT2 builds that variant.)  Twice the partial rows for the fold (one [96][12][5] weight gradient per workgroup): 197 MB per launch at batch 32.
-#ifdef NBSS_FC_TT2
-#define FC_BWD_TT 2
-#else
-#define FC_BWD_TT 1
-#endif
+// (same box).  (Rounds 1-4 ran two frames per workgroup, one per CU: measured 2.2x better in round 1, before the LDS-DMA prologue and the fused weight
+// gradient.)  Twice the partial rows for the fold (one [96][12][5] weight gradient per workgroup): 197 MB per launch at batch 32.
 
 #define TV_RSL_MAX 64  // (tconvffn_s.hip: TV_RSL, the most slices part16_slices_launch writes)
 // tconvffn_s.hip: fp32 slice sums of bf16 partial rows [nrows][p16] (fixed order; *nsl = slices written)
@@ -819,30 +736,16 @@ int fconv_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* pack
     float* stats = (float*)ws;
     void* dv = (char*)ws + ws_align(N * 2 * sizeof(float));
     float* part = (float*)((char*)ws + ws_part_offset(c));
-#ifdef NBSS_FC_NW8
-    const bool nine = false;
-#else
-    // nine waves when the row phases have a multiple of nine units AND the instance is alone on its CU (two-frame slabs); one-frame slabs: two 8-wave
-    // workgroups per CU at <= 128 VGPRs (two of nine waves would not fit the register file)
-    const bool nine = FC_BWD_TT == 2 && (cdiv(c.F, 16) * FC_BWD_TT) % 9 == 0;
-#endif
-    // (F > 160, the 16-kHz geometry: the two images of a 2-frame slab no longer fit the LDS -> one frame per workgroup; the fp32 stream
-    //  images of even one frame are 229 KB at F = 257: fconv_bwd_t returns NBSS_EUNSUPPORTED there, fp32 TRAINING stops at F = 160)
+    // (F > 160, the 16-kHz geometry: the fp32 stream images of even one frame are 229 KB at F = 257: fconv_bwd_t returns NBSS_EUNSUPPORTED there,
+    //  fp32 TRAINING stops at F = 160)
     const bool big = c.F > 16 * FC_MTF_MAX;
-#ifdef NBSS_FC_NOWGF
-    const bool fused = false;
-#else
-    const bool fused = c.dtype == NBSS_BF16 && !big;  // the conv weight gradient is contracted inside the kernel (two-frame bf16 slabs)
-#endif
+    const bool fused = c.dtype == NBSS_BF16 && !big;  // the conv weight gradient is contracted inside the kernel (bf16 slabs)
     if (fused) part = (float*)((char*)ws + ws_fcpart_offset(c));
-    int e = c.dtype != NBSS_BF16 ? fconv_bwd_t<float, 1, 8, false>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
-            : big                ? fconv_bwd_t<bf16_t, 1, 8, false>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
-            : fused && nine      ? fconv_bwd_t<bf16_t, FC_BWD_TT, 9, true>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
-            : fused              ? fconv_bwd_t<bf16_t, FC_BWD_TT, 8, true>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
-            : nine               ? fconv_bwd_t<bf16_t, FC_BWD_TT, 9, false>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
-                                 : fconv_bwd_t<bf16_t, FC_BWD_TT, 8, false>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st);
+    int e = c.dtype != NBSS_BF16 ? fconv_bwd_t<float, false>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
+            : fused              ? fconv_bwd_t<bf16_t, true>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st)
+                                 : fconv_bwd_t<bf16_t, false>(c, P, part, packed, layer, which, x, dy, dx, stats, dv, st);
     if (e) return e;
-    const int nwg = c.dtype == NBSS_BF16 && !big ? c.B * cdiv(c.T, FC_BWD_TT) : c.B * c.T;
+    const int nwg = c.B * c.T;
     AffSegs sg;
     sg.off[0] = param_off(c, layer, which ? P_FC2_LN_W : P_FC1_LN_W); sg.cnt[0] = FC_H;
     sg.off[1] = param_off(c, layer, which ? P_FC2_LN_B : P_FC1_LN_B); sg.cnt[1] = FC_H;

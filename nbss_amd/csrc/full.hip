@@ -67,11 +67,7 @@
 
 // KSFM: LinearGroup k-steps the fragment arrays are sized for; HH / NSQ = dim_hidden / dim_squeeze (geom.h)
 template <class T, int KSFM, int HH, int NSQ, int TT>
-#ifdef NBSS_FULLF_NOCAP
-__global__ __launch_bounds__(FL_THREADS)
-#else
 __global__ __launch_bounds__(FL_THREADS, HH == 96 && TT == 8 ? 4 : 1)  // small geometry, full grids: <= 128 VGPRs, two workgroups per CU
-#endif
 void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                        const float* __restrict__ bs, const float* __restrict__ bfull,
                                                        const float* __restrict__ bu, const T* __restrict__ Wsq,
@@ -401,9 +397,7 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
                 rawc_get(dcur[mt], dv);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dyp[mt][r] = valid ? dv[r] * dsilu_f(acc[r] + bu[ch + r]) : 0.f;
-#ifndef FL_KO_OPS  // (timing knock-out, A/B flavour: no dy_pre operand)
                 if (valid) store4(dyp_out + n * FL_H + ch, dyp[mt][0], dyp[mt][1], dyp[mt][2], dyp[mt][3]);
-#endif
             }
             f32x4 dzt = F32X4_ZERO;
 #pragma unroll

@@ -11,7 +11,6 @@
 // gb_tap_gemm_lds_kernel (gbwd.hip) fed the MFMA from global memory one 16-row tile at a time: 102 TF/s over the large train step.
 #include "tapgemm.h"
 #include "layout.h"
-#include <cstdlib>
 
 #define GL_ROWS 128
 #define GL_OUTS 192
@@ -202,15 +201,8 @@ __global__ __launch_bounds__(256, 2) void gl_gemm_kernel(TapGemm p, int nrt, int
     }
 }
 
-static bool gl_disabled() {
-    static const bool off = [] {
-        const char* e = getenv("NBSS_GEMM_V1");
-        return e && e[0] == '1';
-    }();
-    return off;
-}
 bool gl_gemm_takes(const TapGemm& p) {
-    return !gl_disabled() && p.taps == 1 && p.groups == 1 && !p.xact && p.Kg == p.Kp && p.Kg >= 64 && p.Mg >= 64 && p.Mg % 8 == 0 && p.ldx % 8 == 0 && p.xcol % 8 == 0 &&
+    return p.taps == 1 && p.groups == 1 && !p.xact && p.Kg == p.Kp && p.Kg >= 64 && p.Mg >= 64 && p.Mg % 8 == 0 && p.ldx % 8 == 0 && p.xcol % 8 == 0 &&
            p.ldy % 8 == 0 && p.ycol % 8 == 0 && (!p.R || p.ldr % 4 == 0) && !(p.R && p.Dact) && p.Mp <= 1024;
 }
 int gl_gemm_bf16(const TapGemm& p, hipStream_t st) {

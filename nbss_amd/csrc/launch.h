@@ -15,12 +15,8 @@
     (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)) == hipSuccess ? 0 : -4)
 #endif
 
-// launches that only fold partial parameter gradients (timing knock-out, A/B flavour -DNBSS_KO_FOLDS: what would a step cost without them?)
-#ifdef NBSS_KO_FOLDS
-#define NBSS_FOLD_LAUNCH(kern, grid, block, lds, stream, ...) ((void)0)
-#else
+// launches that only fold partial parameter gradients
 #define NBSS_FOLD_LAUNCH(kern, grid, block, lds, stream, ...) NBSS_LAUNCH(kern, grid, block, lds, stream, __VA_ARGS__)
-#endif
 
 // Traversal direction of the walks' main-stream kernels (round 6).  At batch 32 a stream tensor is 199 MB and the Infinity Cache 256 MB: when every kernel
 // walks the utterances in the same order, what a kernel reads first is what its producer wrote first — long evicted.  Consecutive main-stream kernels of

@@ -205,11 +205,7 @@ NBSS_HD int64_t pack_total(const nbss_cfg& c) {
 // wgrad partial tiles: up to 512 workgroups x 112 tiles x (256 accumulators + 16 bias sums) floats
 #define WGPART_BYTES ((size_t)512 * 112 * 272 * sizeof(float))
 // backward workspace (caller-provided): per-token LN statistics + the widest set of wgrad operands
-#ifndef NBSS_WS_PAD
-#define NBSS_WS_PAD 0  // (A/B flavour: extra bytes behind every aligned region.  At batch 32 all regions start at multiples of 2 KB; 1 280 or 4 352 bytes of padding
-                       //  changed nothing — 727 / 728 / 727 utt/s in one call: the batch-31 / 32 / 33 steps of 738 / 730 / 718 are round counts, not address aliasing)
-#endif
-NBSS_HD size_t ws_align(size_t b) { return ((b + 255) & ~(size_t)255) + NBSS_WS_PAD; }
+NBSS_HD size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
 // sequence lengths: backward keeps a whole sequence per workgroup (LDS), forward has chunked variants beyond that
 #define NBSS_T_TRAIN_MAX 256
 // frequencies: the cross-band kernels keep the whole F axis of a slab on chip: 17 tiles of 16 (n_fft 512 -> F = 257; fp32 backward: F <= 160)
@@ -220,14 +216,10 @@ NBSS_HD size_t ws_align(size_t b) { return ((b + 255) & ~(size_t)255) + NBSS_WS_
 // [tap][group][input channel][outputs of the group] (round 6: 13 KB per workgroup instead of 24.6 KB of fp32; fconv.hip: fconv_part_final_kernel)
 #define NBSS_FC_PROW(c) (4 * (c).H)
 #define NBSS_FC_P16(c) ((c).H * ((c).H / (c).f_groups) * (c).f_ks)
-#ifdef NBSS_FC_TT2  // (A/B flavour: round 4's two-frame slabs)
-NBSS_HD size_t fc_part_bytes(const nbss_cfg& c) { return (size_t)c.B * ((c.T + 1) / 2) * (NBSS_FC_PROW(c) * sizeof(float) + NBSS_FC_P16(c) * 2); }
-#else
 NBSS_HD size_t fc_part_bytes(const nbss_cfg& c) { return (size_t)c.B * c.T * (NBSS_FC_PROW(c) * sizeof(float) + NBSS_FC_P16(c) * 2); }
-#endif
-// T-ConvFFN backward from saved pre-activations (tconvffn_s.hip: tconvffn_bwd_v_kernel; bf16 stream, small geometry): per sequence one fp32
-// partial row (GroupNorm affine sums 2 FFN + the three conv bias sums 3 FFN + W2's bias sums H) and one bf16 row (the three conv weight
-// gradients + the W2 weight gradient)
+// T-ConvFFN backward from saved pre-activations (tconvffn_s.hip: tconvffn_bwd_q_kernel; bf16 stream, small geometry): per sequence one fp32
+// partial row (GroupNorm affine sums 2 FFN + the three conv bias sums 3 FFN) and one bf16 row (the three conv weight gradients).  The region
+// keeps the size of the earlier four-group kernel's rows, which also carried W2's bias sums (H floats) and weight gradient (FFN H bf16)
 NBSS_HD size_t tc_part_bytes(const nbss_cfg& c) {
     return c.dtype == NBSS_BF16 && c.H == 96 && c.T <= 256
                ? (size_t)c.B * c.F * ((5 * c.FFN + c.H) * sizeof(float) + ((size_t)3 * c.FFN * (c.FFN / c.t_groups) * c.t_ks + (size_t)c.FFN * c.H) * 2)

@@ -297,11 +297,7 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 4 ? 2 : 1) void mhsa_fwd_kern
                     o1[r] *= inv;
                 }
                 frag_from_c2(of[si][hh], o0, o1);
-#ifdef MH_KO_SAVE  // (timing knock-out, A/B flavour: no saved attention output)
-                if (false) {
-#else
                 if (osave) {  // attention output before out_proj: the only extra activation backward needs
-#endif
                     const int t = (w * NSW + si) * 16 + l15;
                     if (t < T_) {
                         T* orow = osave + ((size_t)bf * T_ + t) * MH_H + (pass * HPP + hh) * MH_DH;

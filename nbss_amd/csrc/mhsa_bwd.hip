@@ -2,7 +2,8 @@
 //
 // One workgroup (8 waves, two 16-frame strips each) = one (b,f) sequence, one head at a time.
 // Recomputed per head: Q' = q * log2(e)/sqrt(dh), K, V (from LN(x)) and dO = Wo_h^T dy.  LDS holds
-// Q', K, V, dO row-major [T][24] and (fp32 stream only) Q', K transposed [24][T]; nothing else is staged.
+// Q', K, V, dO row-major [T][24] and Q', K transposed [24][T]; nothing else is staged.  This two-sweep kernel is the fp32
+// stream's; the bf16 stream takes the single-sweep mhsa_bwd_h_kernel below and tailw.hip's fused tail.
 //   pass 1 (wave owns QUERY strips):  S^T = K Q'^T, P, D = rowsum(dO * O), dS^T = P (dP^T - D),
 //                                     dQ^T = K^T dS^T              (O = saved forward attention output)
 //   pass 2 (wave owns KEY strips):    S = Q' K^T, P = exp2(S - m)/l from the stored row statistics,
@@ -75,7 +76,6 @@ NBSS_DEV void col_frag_tr(Frag<bf16_t>& f, const bf16_t* __restrict__ rowmajor, 
     f.v = __builtin_bit_cast(s16x8, v);
     // rows d >= 24 of the second half-tile pick up neighbouring data: finite, and every consumer discards those rows
 }
-NBSS_DEV void col_frag_tr(Frag<float>&, const float*, int, int, bool) {}
 
 template <class T>
 NBSS_DEV void col_frag(Frag<T>& f, const T* __restrict__ base, int tp, int half, int ks, bool hi_valid) {
@@ -125,35 +125,25 @@ template <> struct RawRow4<float> {
     NBSS_DEV void get(float (&o)[4]) const { o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3]; }
 };
 
-// FULL: T in (240, 256] — all 16 strips of every wave exist, so the strip / tile-existence tests are compile-time true and the
-// tile loops have constant trip counts (wave-uniform but dynamic branches kept the compiler from scheduling across them: the same
-// effect cost wgrad 24 %, profiles/README.md row 27)
-// XT (bf16): the tail — du = Win^T dqkv, LayerNorm backward, dx, LN-affine sums — runs in tailw.hip's fused tail / in_proj weight-gradient
-// kernel instead; this kernel then ends with the dqkv operand and writes the LayerNorm row statistics for it.
-template <class T, bool FULL, bool XT>
 __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs lp, const float* __restrict__ P, float* __restrict__ part, int layer,
-                                                       const T* __restrict__ Win, const T* __restrict__ WinT, const T* __restrict__ WoutT,
-                                                       const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ osave,
-                                                       const float* __restrict__ lse, T* __restrict__ dx, float* __restrict__ stats, T* __restrict__ dqkv) {
+                                                       const float* __restrict__ Win, const float* __restrict__ WinT, const float* __restrict__ WoutT,
+                                                       const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ osave,
+                                                       const float* __restrict__ lse, float* __restrict__ dx, float* __restrict__ stats, float* __restrict__ dqkv) {
+    typedef float T;
     NBSS_LDS(smem);
-    const int T_ = c.T, nst = FULL ? MB_NT : cdiv(T_, 16), tp = nst * 16, nkp = FULL ? MB_NT / 2 : cdiv(nst, 2);
+    const int T_ = c.T, nst = cdiv(T_, 16), tp = nst * 16, nkp = cdiv(nst, 2);
     T* Qr = reinterpret_cast<T*>(smem);
     T* Kr = Qr + (size_t)tp * MB_DH;
     T* Vr = Kr + (size_t)tp * MB_DH;
     T* dOr = Vr + (size_t)tp * MB_DH;
-    constexpr bool TR = sizeof(T) == 2;  // bf16: transposing LDS reads replace the transposed copies
     T* Qt = dOr + (size_t)tp * MB_DH;
     T* Kt = Qt + (size_t)tp * MB_DH;
-    float* m2s = reinterpret_cast<float*>(TR ? Qt : Kt + (size_t)tp * MB_DH);
+    float* m2s = Kt + (size_t)tp * MB_DH;
     float* lis = m2s + tp;
     float* Dds = lis + tp;
     float* aff = Dds + tp;  // [2H] per-workgroup LN weight | bias gradient sums
     float* lnp = aff + 2 * MB_H;  // [2H] LayerNorm gamma | beta
-    // bf16: every weight fragment of the module lives in LDS for the whole kernel (in_proj 72 + out_proj^T 24 fragments, 96 KB;
-    // replaced by the 54 fragments of in_proj^T for the du phase) — per-wave global fragment reads sat behind the dqkv stores
-    T* wl = reinterpret_cast<T*>(lnp + 2 * MB_H);
-    constexpr int WL_FR = TR ? 96 : 0;
-    PHASE_BEGIN(wl + (size_t)WL_FR * 512);
+    PHASE_BEGIN(lnp + 2 * MB_H);
     const size_t ntok = (size_t)c.B * c.F * T_;
     const int bf = blockIdx.x;
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
@@ -171,19 +161,13 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
     for (int si = 0; si < MB_NSW; ++si) {
         tt[si] = (w * MB_NSW + si) * 16 + l15;
         tv[si] = tt[si] < T_;
-        sact[si] = FULL || (w * MB_NSW + si) < nst;  // wave-uniform
+        sact[si] = (w * MB_NSW + si) < nst;  // wave-uniform
     }
-    // dqkv operand of the in_proj weight gradient.  bf16: group-major [12 (q|k|v x head)][N][24], a strip writes 768 contiguous
-    // bytes (48-byte pieces of 576-byte token rows were partial-line writes); fp32: token-major [N][3H]
-    auto dqkv_row = [&](int grp, size_t n) -> T* {
-        return TR ? dqkv + ((size_t)grp * ntok + n) * MB_DH : dqkv + n * (3 * MB_H) + grp * MB_DH;
-    };
-    // bf16: LN(x) and dy fragments of the wave's strips stay in registers for all four heads (48 VGPRs) instead of being re-read
-    // and re-normalised per head (PMC: the per-head re-reads of x, dy missed L2 — 3 GB fetched per launch for 0.6 GB of inputs)
-    constexpr bool DYREG = sizeof(T) == 2;
+    // dqkv operand of the in_proj weight gradient: token-major [N][3H]
+    auto dqkv_row = [&](int grp, size_t n) -> T* { return dqkv + n * (3 * MB_H) + grp * MB_DH; };
     Frag<T> uf[MB_NSW][MB_KS], dr[MB_NSW][MB_KS];
     float smean[MB_NSW], srstd[MB_NSW];
-    // saved attention output / log-sum-exp rows of the NEXT head, requested one head ahead (raw: no conversion, so nothing waits on them)
+    // saved attention output / log-sum-exp rows of the current head (raw: converted on use)
     RawRow4<T> onx0[MB_NSW], onx1[MB_NSW];
     float lsenx[MB_NSW];
     auto request_o1 = [&](int head, int si) {
@@ -192,107 +176,32 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
         onx1[si].load(ob + (size_t)tc * MB_H + head * MB_DH + 16 + 4 * (g4 & 1));
         lsenx[si] = lse[(n0 + tc) * MB_HEADS + head];
     };
-    auto request_o = [&](int head) {
+    for (int i = threadIdx.x; i < 2 * MB_H; i += blockDim.x) aff[i] = 0.f;
+    // Only the row statistics persist across the head loop: LN(x) and dy fragments are rebuilt per head and du is formed after
+    // the loop from the emitted dqkv operand (keeping them live spilled 336 B/lane in the first version).
+    for (int i = threadIdx.x; i < 2 * MB_H; i += blockDim.x) lnp[i] = i < MB_H ? lp.p[P_MH_LN_W][i] : lp.p[P_MH_LN_B][i - MB_H];
 #pragma unroll
-        for (int si = 0; si < MB_NSW; ++si) request_o1(head, si);
-    };
-    if constexpr (DYREG) {
-        // Prologue of the bf16 kernel: EVERY global request of the workgroup's start is issued before anything waits — x / dy fragments,
-        // the 96 weight fragments (12 16-byte pieces per thread, parked in registers), head 0's saved O rows.  (One workgroup per CU:
-        // nothing else hides this latency; the serial form — weights through a load/store loop, then the statistics' reads, then the
-        // fragment reads, then O — was 14 % + most of another 18 % of the kernel's wave time, profiles/r03a_phase_prof.txt.)
+    for (int si = 0; si < MB_NSW; ++si) {
+        float v[MB_KS][8], sum = 0.f;
 #pragma unroll
-        for (int si = 0; si < MB_NSW; ++si) {
-            const int tc = tv[si] ? tt[si] : T_ - 1;
+        for (int ks = 0; ks < MB_KS; ++ks) {
+            if (tv[si]) load8(xb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4, v[ks]);
+            else
 #pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
-                frag_load(uf[si][ks], xb + (size_t)tc * MB_H + ks * 32 + 8 * g4);
-                frag_load(dr[si][ks], dyb + (size_t)tc * MB_H + ks * 32 + 8 * g4);
-            }
+                for (int j = 0; j < 8; ++j) v[ks][j] = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sum += v[ks][j];
         }
-        constexpr int NWV = 96 * 64 / MB_NTHR;  // 16-byte pieces per thread
-        u32x4 wreg[NWV];
+        smean[si] = wave_sum16(sum) * (1.0f / MB_H);
+        float q = 0.f;
 #pragma unroll
-        for (int i = 0; i < NWV; ++i) {
-            const int v = threadIdx.x + i * MB_NTHR;
-            wreg[i] = v < 72 * 64 ? reinterpret_cast<const u32x4*>(Win)[v] : reinterpret_cast<const u32x4*>(WoutT)[v - 72 * 64];
-        }
-        request_o(0);
-        for (int i = threadIdx.x; i < 2 * MB_H; i += MB_NTHR) {
-            aff[i] = 0.f;
-            lnp[i] = i < MB_H ? lp.p[P_MH_LN_W][i] : lp.p[P_MH_LN_B][i - MB_H];
-        }
+        for (int ks = 0; ks < MB_KS; ++ks)
 #pragma unroll
-        for (int i = 0; i < NWV; ++i) reinterpret_cast<u32x4*>(wl)[threadIdx.x + i * MB_NTHR] = wreg[i];
-        // LayerNorm statistics from the fragments already in registers, then LN(x) in place
-#pragma unroll
-        for (int si = 0; si < MB_NSW; ++si) {
-            float sum = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sum += frag_get(uf[si][ks], j);
-            smean[si] = wave_sum16(sum) * (1.0f / MB_H);
-            float q = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float d = frag_get(uf[si][ks], j) - smean[si];
-                    q += d * d;
-                }
-            srstd[si] = rsqrtf(wave_sum16(q) * (1.0f / MB_H) + 1e-5f);
-            if (XT && tv[si] && g4 == 0) {
-                stats[(n0 + tt[si]) * 2] = smean[si];
-                stats[(n0 + tt[si]) * 2 + 1] = srstd[si];
-            }
-        }
-#pragma unroll
-        for (int si = 0; si < MB_NSW; ++si)
-#pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
-                float gm[8], bt[8];
-                load8(lp.p[P_MH_LN_W] + ks * 32 + 8 * g4, gm);
-                load8(lp.p[P_MH_LN_B] + ks * 32 + 8 * g4, bt);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    frag_set(uf[si][ks], j, tv[si] ? (frag_get(uf[si][ks], j) - smean[si]) * srstd[si] * gm[j] + bt[j] : bt[j]);
-                if (!tv[si]) frag_zero(dr[si][ks]);
-            }
-        lds_barrier();  // weights, lnp, aff are in LDS
-        PHASE(0);
-    } else {
-        for (int i = threadIdx.x; i < 2 * MB_H; i += blockDim.x) aff[i] = 0.f;
-        // Only the row statistics persist across the head loop: LN(x) and dy fragments are rebuilt per head and du is formed after
-        // the loop from the emitted dqkv operand (keeping them live spilled 336 B/lane in the first version).
-        for (int i = threadIdx.x; i < 2 * MB_H; i += blockDim.x) lnp[i] = i < MB_H ? lp.p[P_MH_LN_W][i] : lp.p[P_MH_LN_B][i - MB_H];
-#pragma unroll
-        for (int si = 0; si < MB_NSW; ++si) {
-            float v[MB_KS][8], sum = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
-                if (tv[si]) load8(xb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4, v[ks]);
-                else
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[ks][j] = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sum += v[ks][j];
-            }
-            smean[si] = wave_sum16(sum) * (1.0f / MB_H);
-            float q = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) q += (v[ks][j] - smean[si]) * (v[ks][j] - smean[si]);
-            srstd[si] = rsqrtf(wave_sum16(q) * (1.0f / MB_H) + 1e-5f);
-            if (XT && tv[si] && g4 == 0) {
-                stats[(n0 + tt[si]) * 2] = smean[si];
-                stats[(n0 + tt[si]) * 2 + 1] = srstd[si];
-            }
-        }
-        lds_barrier();  // lnp is read below
-        PHASE(0);
+            for (int j = 0; j < 8; ++j) q += (v[ks][j] - smean[si]) * (v[ks][j] - smean[si]);
+        srstd[si] = rsqrtf(wave_sum16(q) * (1.0f / MB_H) + 1e-5f);
     }
+    lds_barrier();  // lnp is read below
+    PHASE(0);
     for (int head = 0; head < MB_HEADS; ++head) {
         Frag<T> qf[MB_NSW], dof[MB_NSW];
         float Dv[MB_NSW];
@@ -303,7 +212,6 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
         for (int si = 0; si < MB_NSW; ++si) {
 #pragma unroll
             for (int ks = 0; ks < MB_KS; ++ks) {
-                if (DYREG) continue;
                 if (tv[si]) {
                     frag_load(uf[si][ks], xb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4);
                     frag_load(dr[si][ks], dyb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4);
@@ -312,8 +220,8 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
                     frag_zero(dr[si][ks]);
                 }
             }
-            // this head's saved O / log2-sum-exp rows: bf16 — requested one head ago; fp32 — requested here (no registers to park them)
-            if (!DYREG) request_o1(head, si);
+            // this head's saved O / log2-sum-exp rows
+            request_o1(head, si);
             onx0[si].get(o0[si]);
             onx1[si].get(o1[si]);
 #pragma unroll
@@ -323,12 +231,10 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
             }
             lsev[si] = tv[si] ? lsenx[si] : 1e30f;  // padding frame: P = exp2(S - lse) = 0
         }
-        if (DYREG) request_o(head + 1 < MB_HEADS ? head + 1 : head);  // (last head: a harmless re-read, keeps the loop body uniform)
 #pragma unroll
         for (int si = 0; si < MB_NSW; ++si)
 #pragma unroll
             for (int ks = 0; ks < MB_KS; ++ks) {  // LN(x) in place of x (rebuilt per head from the row statistics)
-                if (DYREG) continue;
                 float gm[8], bt[8];
                 load8(lnp + ks * 32 + 8 * g4, gm);
                 load8(lnp + MB_H + ks * 32 + 8 * g4, bt);
@@ -346,9 +252,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
                 Frag<T> a[2];
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    const int fi = which < 3 ? ((which * MB_HEADS + head) * 2 + half) * MB_KS + ks : 72 + (head * 2 + half) * MB_KS + ks;
-                    if (TR) frag_load(a[half], wl + ((size_t)fi * 64 + lane) * 8);
-                    else if (which < 3) wfrag_load(a[half], Win, (which * MB_HEADS + head) * 2 + half, MB_KS, ks);
+                    if (which < 3) wfrag_load(a[half], Win, (which * MB_HEADS + head) * 2 + half, MB_KS, ks);
                     else wfrag_load(a[half], WoutT, head * 2 + half, MB_KS, ks);
                 }
 #pragma unroll
@@ -382,10 +286,10 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
                 if (which == 0) {
                     frag_from_c2(qf[si], ct[si][0], ct[si][1]);
                     store_row24<T>(Qr + (size_t)t * MB_DH, ct[si][0], ct[si][1]);
-                    if (!TR) store_col24<T>(Qt, tp, t, ct[si][0], ct[si][1]);
+                    store_col24<T>(Qt, tp, t, ct[si][0], ct[si][1]);
                 } else if (which == 1) {
                     store_row24<T>(Kr + (size_t)t * MB_DH, ct[si][0], ct[si][1]);
-                    if (!TR) store_col24<T>(Kt, tp, t, ct[si][0], ct[si][1]);
+                    store_col24<T>(Kt, tp, t, ct[si][0], ct[si][1]);
                 } else if (which == 2) {
                     store_row24<T>(Vr + (size_t)t * MB_DH, ct[si][0], ct[si][1]);
                 } else {
@@ -429,10 +333,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
                     }
                 }
 #pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    if (TR) col_frag_tr(akt[half], Kr, half, jp, hi_valid);
-                    else col_frag<T>(akt[half], Kt, tp, half, jp, hi_valid);
-                }
+                for (int half = 0; half < 2; ++half) col_frag<T>(akt[half], Kt, tp, half, jp, hi_valid);
 #pragma unroll
                 for (int si = 0; si < MB_NSW; ++si) {
                     if (!sact[si]) continue;
@@ -503,13 +404,8 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
                 }
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    if (TR) {
-                        col_frag_tr(ado[half], dOr, half, jp, hi_valid);
-                        col_frag_tr(aq[half], Qr, half, jp, hi_valid);
-                    } else {
-                        col_frag_rm<T>(ado[half], dOr, half, jp, hi_valid);
-                        col_frag<T>(aq[half], Qt, tp, half, jp, hi_valid);
-                    }
+                    col_frag_rm<T>(ado[half], dOr, half, jp, hi_valid);
+                    col_frag<T>(aq[half], Qt, tp, half, jp, hi_valid);
                 }
 #pragma unroll
                 for (int si = 0; si < MB_NSW; ++si) {
@@ -553,18 +449,10 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
         PHASE(9);
     }
 
-    if constexpr (XT) {
-        PHASE_END();
-        return;
-    }
     // du = Win^T dqkv from the [N][3H] operand this workgroup has just written (full barrier: the other waves' stores are
     // complete, and these lines were never read before, so no stale L1 copies exist)
     __syncthreads();
     PHASE(10);
-    if (TR) {  // in_proj^T fragments (54) replace the forward weights in LDS; everyone is past the head loop
-        for (int v = threadIdx.x; v < 54 * 64; v += blockDim.x) reinterpret_cast<u32x4*>(wl)[v] = reinterpret_cast<const u32x4*>(WinT)[v];
-        lds_barrier();
-    }
     f32x4 du[MB_NSW][BK_MT];
 #pragma unroll
     for (int si = 0; si < MB_NSW; ++si) {
@@ -582,8 +470,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
 #pragma unroll
             for (int mt = 0; mt < BK_MT; ++mt) {
                 Frag<T> a;
-                if (TR) frag_load(a, wl + ((size_t)(mt * (3 * MB_H / 32) + k9) * 64 + lane) * 8);
-                else wfrag_load(a, WinT, mt, 3 * MB_H / 32, k9);
+                wfrag_load(a, WinT, mt, 3 * MB_H / 32, k9);
                 du[si][mt] = mma(a, df[k9], du[si][mt]);
             }
         }
@@ -625,9 +512,9 @@ PHASE_READER(nbss_phase_read_mhsa_bwd)
 // The four heads of a sequence are four workgroups on the same XCD (x / dy rows come from its L2); the saved attention output, the
 // log2-sum-exp rows and this head's 24 weight fragments (staged in the LDS region that becomes the dS image) are read per head.
 // Padding frames (T not a multiple of 16): K rows are zero and lse = 1e30, so they contribute nothing anywhere.
-#ifndef MHB_KO
-#define MHB_KO 0   // timing knock-outs (A/B flavours, results wrong): 1 = no dqkv stores, 2 = every wave reads the sequence's first x / dy strip
-#endif
+// FULL: T in (240, 256] — every strip exists, so the strip / tile-existence tests are compile-time true and the tile loops have constant
+// trip counts (wave-uniform but dynamic branches kept the compiler from scheduling across them: the same effect cost wgrad 24 %,
+// profiles/README.md row 27)
 #define MH_QC 64   // queries per dS chunk
 #define MH_RS 68   // dS image row stride (elements): rows 34 dwords apart — the 16 key rows of a b64 store hit 16 distinct bank pairs
 #define MH_TP 256
@@ -644,11 +531,7 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
     typedef bf16_t T;
     NBSS_LDS(smem);
     // blocks b, b + 8, b + 16, b + 24 (same XCD, dispatched back to back) = the four heads of one sequence
-#ifdef MHB_FLAT_MAP  // (A/B flavour: four consecutive blocks = the four heads of a sequence, on four XCDs)
-    const int head = blockIdx.x & 3, bf0 = blockIdx.x >> 2;
-#else
     const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, head = bi & 3, bf0 = (bi >> 2) * 8 + xcd;
-#endif
     if (bf0 >= nseq) return;
     const int bf = flip ? nseq - 1 - bf0 : bf0;  // (launch.h: consecutive kernels of a walk traverse the utterances in opposite order)
     const int T_ = c.T, nst = FULL ? MB_NT : cdiv(T_, 16), nkp = FULL ? MB_NT / 2 : cdiv(nst, 2);
@@ -713,27 +596,19 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
                                       : bin + ((t - 48) / 6) * MB_H + head * MB_DH + 4 * ((t - 48) % 6);
             if (t < 66) ppc = *reinterpret_cast<const f32x4*>(src);
         }
-        // Global rows are read as 16-byte pieces of CONTIGUOUS runs (a strip of x / dy is 3 KB, a strip of this head's O columns 16 x 48 B) and
-        // turned into MFMA fragments through a wave-private LDS round trip: the direct fragment form (lane = token l15, piece g4) makes the four
-        // lanes of every quad touch four different rows — 64 cache-line lookups per wave instruction instead of 8, and the vector memory pipe,
-        // not VALU or MFMA, was what this kernel waited for (TCP_TOTAL_CACHE_ACCESSES: 12 bytes per access, profiles/README.md round 4).
-        u32x4 xc[2][MB_KS], dc[2][MB_KS], oc[2];
+        // x / dy fragments come straight from global memory (lane = token l15, piece g4).  This head's O columns (a strip is 16 x 48 B) are read as
+        // 16-byte pieces of CONTIGUOUS runs and turned into row pieces through a wave-private LDS round trip: the direct form makes the four lanes of
+        // every quad touch four different rows — 64 cache-line lookups per wave instruction instead of 8 (TCP_TOTAL_CACHE_ACCESSES: 12 bytes per
+        // access, profiles/README.md round 4).
+        u32x4 oc[2];
         const int tlast = T_ - 1;
 #pragma unroll
         for (int si = 0; si < 2; ++si) {
-            const int t0 = (w * 2 + si) * 16;
 #pragma unroll
             for (int i = 0; i < MB_KS; ++i) {
-#ifdef MH_STAGE_X  // piece p = 64 i + lane of the strip's 192: row p / 12, 16-byte column p % 12
-                const int pc = i * 64 + lane, r = pc / 12, cc = pc - r * 12;
-                const int tr = t0 + r < tlast ? t0 + r : tlast;  // clamped: the padding frames' values are replaced on use
-                xc[si][i] = *reinterpret_cast<const u32x4*>(xb + (tr * MB_H + cc * 8));
-                dc[si][i] = *reinterpret_cast<const u32x4*>(dyb + (tr * MB_H + cc * 8));
-#else  // fragments straight from global memory (lane = token l15, piece g4)
-                const int tc = (MHB_KO & 2) ? l15 : tv[si] ? tt[si] : tlast;
+                const int tc = tv[si] ? tt[si] : tlast;
                 frag_load(uf[si][i], xb + (tc * MB_H + i * 32 + 8 * g4));
                 frag_load(dr[si][i], dyb + (tc * MB_H + i * 32 + 8 * g4));
-#endif
             }
         }
 #pragma unroll
@@ -751,27 +626,9 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
         for (int i = 0; i < 3; ++i) reinterpret_cast<u32x4*>(wl)[threadIdx.x + i * 512] = wreg[i];
         PHASE(9);
         if (threadIdx.x < 66) *reinterpret_cast<f32x4*>(lnp + 4 * threadIdx.x) = ppc;
-        // wave-private staging: this wave's own rows of the Q' | K images (2 x 1.5 KB = one strip of x or dy) and of the dO image (O rows);
-        // nobody else touches them before the barrier that follows the projections
+        // wave-private staging: this wave's own rows of the dO image (O rows); nobody else touches them before the barrier that follows the projections
         {
-            T* sA = Qr + w * 32 * MB_DH;
-            T* sB = Kr + w * 32 * MB_DH;
             T* sO = dOr + w * 32 * MB_DH;
-            auto stg = [&](int pc) -> T* { return (pc < 96 ? sA : sB - 96 * 8) + pc * 8; };  // piece pc of a strip
-            auto fr = [&](int ks) -> const T* { const int pc = l15 * 12 + ks * 4 + g4; return (pc < 96 ? sA : sB - 96 * 8) + pc * 8; };
-#ifdef MH_STAGE_X
-#pragma unroll
-            for (int which = 0; which < 2; ++which)
-#pragma unroll
-                for (int si = 0; si < 2; ++si) {
-#pragma unroll
-                    for (int i = 0; i < MB_KS; ++i) *reinterpret_cast<u32x4*>(stg(i * 64 + lane)) = which ? dc[si][i] : xc[si][i];
-                    wave_lds_sync();
-#pragma unroll
-                    for (int ks = 0; ks < MB_KS; ++ks) frag_load(which ? dr[si][ks] : uf[si][ks], fr(ks));
-                    wave_lds_sync();
-                }
-#endif
 #pragma unroll
             for (int si = 0; si < 2; ++si)
                 if (lane < 48) *reinterpret_cast<u32x4*>(sO + si * 16 * MB_DH + lane * 8) = oc[si];
@@ -971,7 +828,7 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
         PHASE(6);
         {   // the chunk's dQ rows are one 3 KB run of the group-major operand: 24 16-byte pieces per wave
             const int pc = w * 24 + lane, tq = ch * MH_QC + pc / 3;
-            if (lane < 24 && tq < T_ && !(MHB_KO & 1 && nseq > 0)) {
+            if (lane < 24 && tq < T_) {
                 const u32x4 v = *reinterpret_cast<const u32x4*>(dqs + pc * 8);
                 store16_nt(dq_seq + (dqkv_off(head, ch * MH_QC) + pc * 8), v);
             }
@@ -996,7 +853,7 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // 96 pieces per tensor: row pc / 3
             const int pc = i * 64 + lane, t = w * 32 + pc / 3;
-            if (pc < 96 && t < T_ && !(MHB_KO & 1 && nseq > 0)) {  // (padding keys only ever produced their own, discarded, rows)
+            if (pc < 96 && t < T_) {  // (padding keys only ever produced their own, discarded, rows)
                 const u32x4 vk = *reinterpret_cast<const u32x4*>(sK + pc * 8), vv = *reinterpret_cast<const u32x4*>(sV + pc * 8);
                 store16_nt(dq_seq + (dqkv_off(1 * MB_HEADS + head, w * 32) + pc * 8), vk);
                 store16_nt(dq_seq + (dqkv_off(2 * MB_HEADS + head, w * 32) + pc * 8), vv);
@@ -1010,21 +867,20 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
 int tailw_mhsa(const nbss_cfg& c, const LayerPtrs& lp, const void* packed, int layer, const void* x, const void* dy, void* dx, float* stats,
                const void* dqkv, float* wgpart, float* G, hipStream_t st, const Side* sd, hipStream_t* gs);
 
-template <class T, bool FULL, bool XT>
-static int mhsa_bwd_t(const nbss_cfg& c, const float* P, float* part, const void* packed, int layer, const void* x, const void* dy, const void* osave,
-                      void* dx, float* stats, void* dqkv, hipStream_t st) {
+static int mhsa_bwd_f32(const nbss_cfg& c, const float* P, float* part, const void* packed, int layer, const void* x, const void* dy, const void* osave,
+                        void* dx, float* stats, void* dqkv, hipStream_t st) {
     const LayerPtrs lp = layer_ptrs(c, P, layer);
     const int tp = cdiv(c.T, 16) * 16;
     if (tp > 256) return NBSS_EUNSUPPORTED;
-    const size_t lds = (size_t)(sizeof(T) == 2 ? 4 : 6) * tp * MB_DH * sizeof(T) + (size_t)(3 * tp + 4 * MB_H) * sizeof(float) + 64 + (sizeof(T) == 2 ? (size_t)96 * 512 * sizeof(T) : 0) + PHASE_LDS_BYTES;
+    const size_t lds = (size_t)6 * tp * MB_DH * sizeof(float) + (size_t)(3 * tp + 4 * MB_H) * sizeof(float) + 64 + PHASE_LDS_BYTES;
     if (lds > 160 * 1024) return NBSS_EUNSUPPORTED;
-    const T* pk = (const T*)packed;
-    int e = NBSS_SET_MAX_LDS((mhsa_bwd_kernel<T, FULL, XT>), lds);
+    const float* pk = (const float*)packed;
+    int e = NBSS_SET_MAX_LDS(mhsa_bwd_kernel, lds);
     if (e) return e;
-    dim3 grid(c.B * c.F), block(MB_NTHR);  // (timed by the caller's ProfScope, together with the fused tail kernel when there is one)
-    NBSS_LAUNCH((mhsa_bwd_kernel<T, FULL, XT>), grid, block, lds, st, c, lp, P, part, layer, pk + pack_off(c, layer, K_INP), pk + pack_off(c, layer, K_INP_TN),
-                pk + pack_off(c, layer, K_OUTP_T), (const T*)x, (const T*)dy, (const T*)osave, (const float*)((const char*)osave + mhsa_lse_offset(c)),
-                (T*)dx, stats, (T*)dqkv);
+    dim3 grid(c.B * c.F), block(MB_NTHR);  // (timed by the caller's ProfScope)
+    NBSS_LAUNCH(mhsa_bwd_kernel, grid, block, lds, st, c, lp, P, part, layer, pk + pack_off(c, layer, K_INP), pk + pack_off(c, layer, K_INP_TN),
+                pk + pack_off(c, layer, K_OUTP_T), (const float*)x, (const float*)dy, (const float*)osave, (const float*)((const char*)osave + mhsa_lse_offset(c)),
+                (float*)dx, stats, (float*)dqkv);
     return NBSS_CHECK_LAUNCH();
 }
 
@@ -1053,28 +909,16 @@ int mhsa_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* packe
     void* dqkv = (char*)ws + ws_align(N * 2 * sizeof(float));
     float* part = (float*)((char*)ws + ws_part_offset(c));
     const bool full = cdiv(c.T, 16) == MB_NT;
-#if defined(NBSS_NO_TAILW) || defined(NBSS_NO_TAILW_MHSA)
-    const bool xt = false;
-#else
     const bool xt = c.dtype == NBSS_BF16;  // tail + in_proj weight gradient in tailw.hip
-#endif
-#ifndef NBSS_MHSA_BWD_V1
     // single-sweep kernel: the LayerNorm row statistics are the forward pass's (save buffer), for it and for the tail kernel
     if (xt) stats = (float*)((char*)osave + mhsa_stat_offset(c));
-#endif
     int e;
     hipStream_t gs = st;  // parameter-gradient launches (side.h)
     FoldScope fs(st, (char*)ws + ws_wgpart_offset(c), WGPART_BYTES, N);  // (fold.h: the sub-block's folds leave as one launch per stage, on the gradient stream)
     {
     ProfScope ps(PK_MHSA_B, st);  // ONE profiler interval per nbss_mhsa_bwd call: data-gradient kernel (+ fused tail / in_proj wgrad kernel)
-    e = c.dtype != NBSS_BF16 ? mhsa_bwd_t<float, false, false>(c, P, part, packed, layer, x, dy, osave, dx, stats, dqkv, st)
-#ifndef NBSS_MHSA_BWD_V1  // (A/B flavour: the two-sweep kernel of rounds 1-3)
-            : xt ? (full ? mhsa_bwd_h_t<true>(c, P, packed, layer, x, dy, osave, stats, dqkv, st) : mhsa_bwd_h_t<false>(c, P, packed, layer, x, dy, osave, stats, dqkv, st))
-#endif
-            : xt ? (full ? mhsa_bwd_t<bf16_t, true, true>(c, P, part, packed, layer, x, dy, osave, dx, stats, dqkv, st)
-                         : mhsa_bwd_t<bf16_t, false, true>(c, P, part, packed, layer, x, dy, osave, dx, stats, dqkv, st))
-            : full ? mhsa_bwd_t<bf16_t, true, false>(c, P, part, packed, layer, x, dy, osave, dx, stats, dqkv, st)
-                   : mhsa_bwd_t<bf16_t, false, false>(c, P, part, packed, layer, x, dy, osave, dx, stats, dqkv, st);
+    e = !xt ? mhsa_bwd_f32(c, P, part, packed, layer, x, dy, osave, dx, stats, dqkv, st)
+            : full ? mhsa_bwd_h_t<true>(c, P, packed, layer, x, dy, osave, stats, dqkv, st) : mhsa_bwd_h_t<false>(c, P, packed, layer, x, dy, osave, stats, dqkv, st);
     if (e) return e;
     if (xt && (e = tailw_mhsa(c, lp, packed, layer, x, dy, dx, stats, dqkv, (float*)((char*)ws + ws_wgpart_offset(c)), G, st, sd, &gs))) return e;
     }
@@ -1098,7 +942,6 @@ int mhsa_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* packe
     if (xt) return fs.end();
     // in_proj: dWin[3H][H] = dqkv^T LN(x) ; dbin = colsum(dqkv)
     a.A = dqkv; a.lda = 3 * MB_H; a.MA = 3 * MB_H; a.B = x; a.ldb = MB_H; a.NB = MB_H;
-    if (c.dtype == NBSS_BF16) { a.a_gw = MB_DH; a.a_gs = (int)(N * MB_DH); }  // group-major dqkv
     a.stats = stats; a.gamma = lp.p[P_MH_LN_W]; a.beta = lp.p[P_MH_LN_B];
     a.dW = G + param_off(c, layer, P_INP_W); a.dbias = G + param_off(c, layer, P_INP_B);
     if ((e = wgrad_launch(a, c.dtype, gs))) return e;

@@ -30,13 +30,10 @@
 #ifndef TW288_NTW
 #define TW288_NTW 4
 #endif
-// timing knock-outs (A/B flavours only, results wrong): bit 0 = no weight-gradient contraction, bit 1 = no tail tiles: what is left is the staging
 #ifndef TW_TAIL_UNROLL
 #define TW_TAIL_UNROLL 2
 #endif
-#ifndef TW_KO
-#define TW_KO 0
-#endif
+#define TW_NBUF 2  // chunk images in LDS: the next chunk is stashed while the waves still read the current one
 
 struct TailArgs {
     const bf16_t* A;      // [MA/24][Ntok][24]  pre-activation gradient (group-major)
@@ -59,7 +56,7 @@ struct TailArgs {
 // 108 tiles are 18 per wave then instead of 27, which did not fit the register file)
 // PD = chunks requested ahead (register sets of the staging): 1; 2 was built for W1 (223 + 24 VGPRs, 6 of them spilled) and measured SLOWER in round 6,
 // 281 -> 345 us per launch: the set that rotates into the stash set has to have arrived right behind the barrier, one more wait in the chunk's critical path
-template <int MA, int NBUF, int NTW, int PD>
+template <int MA, int NTW, int PD>
 __global__ __launch_bounds__(TW_THREADS, 2) void tailw_kernel(TailArgs a) {
     constexpr int LDA = MA + 16;                    // image row strides == 16 (mod 32) elements: wgrad.hip tr_ld()
     constexpr int LDX = 112;                        // 96 + 16
@@ -74,10 +71,10 @@ __global__ __launch_bounds__(TW_THREADS, 2) void tailw_kernel(TailArgs a) {
     static_assert(LDA % 32 == 16, "image stride");
     NBSS_LDS(smem);
     bf16_t* base = reinterpret_cast<bf16_t*>(smem);
-    bf16_t* wl = base + (size_t)NBUF * IMG;                       // W^T fragments
+    bf16_t* wl = base + (size_t)TW_NBUF * IMG;                    // W^T fragments
     float* lnp = reinterpret_cast<float*>(wl + 6 * KSW * 512);    // LayerNorm gamma (du is scaled by it in the tail)
     const int tid = threadIdx.x, lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id_u();
-    for (int i = tid; i < NBUF * IMG / 2; i += TW_THREADS) reinterpret_cast<uint32_t*>(base)[i] = 0u;
+    for (int i = tid; i < TW_NBUF * IMG / 2; i += TW_THREADS) reinterpret_cast<uint32_t*>(base)[i] = 0u;
     for (int i = tid; i < 6 * KSW * 64; i += TW_THREADS) reinterpret_cast<u32x4*>(wl)[i] = reinterpret_cast<const u32x4*>(a.WT)[i];
     for (int i = tid; i < TW_H; i += TW_THREADS) lnp[i] = a.gamma[i];
 
@@ -174,7 +171,7 @@ __global__ __launch_bounds__(TW_THREADS, 2) void tailw_kernel(TailArgs a) {
             frag_load_tr(fa[0], buf + off_a(0), LDA);
             frag_load_tr(fb[0], buf + off_b(0), LDX);
 #pragma unroll
-            for (int i = 0; i < ((TW_KO & 1) ? 1 : NSW * 2); ++i) {
+            for (int i = 0; i < NSW * 2; ++i) {
                 const int s = i / 2, cur = i & 1;
                 if (i + 1 < NSW * 2) {
                     const int s1 = (i + 1) / 2, kh1 = (i + 1) % 2;
@@ -184,8 +181,7 @@ __global__ __launch_bounds__(TW_THREADS, 2) void tailw_kernel(TailArgs a) {
                 acc[s] = mma(fa[cur], fb[cur], acc[s]);
                 if (s < BSW) bacc[s < BSW ? s : 0] = mma(fa[cur], ones, bacc[s < BSW ? s : 0]);
             }
-            if (NBUF == 1) lds_barrier();
-            else b ^= 1;
+            b ^= 1;
         }
         // partial tiles in fragment order + bias sums (wgrad_tr3_kernel's layout: wgrad_reduce_kernel folds them into dW / db)
         const size_t wg = blockIdx.x;
@@ -263,9 +259,8 @@ __global__ __launch_bounds__(TW_THREADS, 2) void tailw_kernel(TailArgs a) {
                 for (int i = 0; i < TPW; ++i) tail_load(nxt, w + i * NTW, xn[i], dn[i]);
             }
 #pragma unroll
-            for (int i = 0; i < ((TW_KO & 2) ? 0 : TPW); ++i) tail_tile(buf, ch, w + i * NTW, xc[i], dc[i]);
-            if (NBUF == 1) lds_barrier();
-            else b ^= 1;
+            for (int i = 0; i < TPW; ++i) tail_tile(buf, ch, w + i * NTW, xc[i], dc[i]);
+            b ^= 1;
         }
     }
 }
@@ -293,14 +288,14 @@ __global__ __launch_bounds__(192) void tailw_affine_kernel(const float* __restri
     fk_tailw_affine(part, MTA, dgamma, dbeta);
 }
 
-template <int MA, int NBUF, int NTW, int PD>
+template <int MA, int NTW, int PD>
 static int tailw_go(const TailArgs& t, int grid, hipStream_t st) {
     constexpr int LDA = MA + 16;
-    const size_t lds = (size_t)NBUF * TW_KC * (LDA + 112) * sizeof(bf16_t) + (size_t)6 * (MA / 32) * 512 * sizeof(bf16_t) + TW_H * sizeof(float);
+    const size_t lds = (size_t)TW_NBUF * TW_KC * (LDA + 112) * sizeof(bf16_t) + (size_t)6 * (MA / 32) * 512 * sizeof(bf16_t) + TW_H * sizeof(float);
     if (lds > 160 * 1024) return NBSS_EUNSUPPORTED;
-    int e = NBSS_SET_MAX_LDS((tailw_kernel<MA, NBUF, NTW, PD>), lds);
+    int e = NBSS_SET_MAX_LDS((tailw_kernel<MA, NTW, PD>), lds);
     if (e) return e;
-    NBSS_LAUNCH((tailw_kernel<MA, NBUF, NTW, PD>), dim3(grid), dim3(TW_THREADS), lds, st, t);
+    NBSS_LAUNCH((tailw_kernel<MA, NTW, PD>), dim3(grid), dim3(TW_THREADS), lds, st, t);
     return NBSS_CHECK_LAUNCH();
 }
 
@@ -330,12 +325,8 @@ int tailw_launch(int MA, const TailArgs& t0, float* wgpart, size_t wgpart_bytes,
 #ifndef TW192_PD
 #define TW192_PD 1  // (A/B: 2 = two chunks in flight for W1 — measured 281 -> 345 us per launch, see the kernel's note)
 #endif
-    int e = MA == 192 ? tailw_go<192, 2, 4, TW192_PD>(t, grid, st)
-#ifdef NBSS_TW288_NBUF1
-            : MA == 288 ? tailw_go<288, 1, 2, 1>(t, grid, st)
-#else
-            : MA == 288 ? tailw_go<288, 2, TW288_NTW, 1>(t, grid, st)  // both buffers + the 54 W^T fragments: 162 176 of 163 840 bytes
-#endif
+    int e = MA == 192 ? tailw_go<192, 4, TW192_PD>(t, grid, st)
+            : MA == 288 ? tailw_go<288, TW288_NTW, 1>(t, grid, st)  // both buffers + the 54 W^T fragments: 162 176 of 163 840 bytes
             : NBSS_EUNSUPPORTED;
     if (e) return e;
     const hipStream_t gs = side_fork(sd, st);

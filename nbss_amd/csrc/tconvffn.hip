@@ -937,159 +937,20 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
 }
 PHASE_READER(nbss_phase_read_tconvffn_bwd)
 
-// ---------------------------------------------------------------------------------------------
-// Tail of the backward pass as its own kernel — since tailw.hip fused it with the W1 weight gradient, built only into the A/B flavour
-// (-DNBSS_NO_TAILW) that the fusion was measured against (bf16 stream, after tconvffn_s.hip's data-gradient kernel): du = W1^T da1 over all
-// FFN channels from the group-major [G][N][24] operand, LayerNorm backward + residual in registers, row statistics for the weight-
-// gradient kernel, and the LayerNorm affine partial sums of the workgroup (entries [2 FFN, 2 FFN + 2 H) of its `part` row; the
-// GroupNorm entries are written by the data-gradient kernel).  One workgroup = one (b,f) sequence, 16 waves x one 16-frame strip
-// (4 waves per SIMD, <= 128 VGPRs: the first version ran 8 waves x 2 strips at 256 VGPRs with 181 spilled registers).
-template <class T>
-__global__ __launch_bounds__(1024) void tconvffn_du_kernel(nbss_cfg c, LayerPtrs lp, float* __restrict__ part, const T* __restrict__ W1tn,
-                                                           const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx,
-                                                           float* __restrict__ stats, const T* __restrict__ da1) {
-    NBSS_LDS(smem);
-    T* wl = reinterpret_cast<T*>(smem);  // the 36 W1^T fragments, once per workgroup
-    float* aff = reinterpret_cast<float*>(wl + 36 * 512);  // [2H] LN weight | bias gradient sums of this workgroup
-    float* lnl = aff + 2 * TF_H;                            // [H] LN weight (24 per-lane values: through LDS, the kernel sits at its 128-VGPR budget)
-    const int T_ = c.T;
-    const int bf = blockIdx.x;
-    const int tid = threadIdx.x, lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
-    const size_t n0 = (size_t)bf * T_, ntok = (size_t)c.B * c.F * T_;
-    const T* xb = x + n0 * TF_H;
-    const T* dyb = dy + n0 * TF_H;
-    T* dxb = dx + n0 * TF_H;
-    const float* lnw = lp.p[P_TF_LN_W];
-    {
-        constexpr int NV = 36 * 512 * (int)sizeof(T) / 16;
-        for (int v = tid; v < NV; v += 1024) reinterpret_cast<u32x4*>(wl)[v] = reinterpret_cast<const u32x4*>(W1tn)[v];
-    }
-    for (int i = tid; i < 3 * TF_H; i += blockDim.x) aff[i] = i < 2 * TF_H ? 0.f : lnw[i - 2 * TF_H];
-    // this wave's first strip: every global read issued before the barrier
-    for (int s16 = w; s16 * 16 < T_ || s16 == w; s16 += 16) {
-        const int tt = s16 * 16 + l15;
-        const bool tv = tt < T_;
-        const int tc = tv ? tt : T_ - 1;
-        Frag<T> df[TF_FFN / 32];
-        u32x2 xr[TF_H / 16], dr[TF_H / 16];
-#pragma unroll
-        for (int k6 = 0; k6 < TF_FFN / 32; ++k6) {  // 8-channel pieces never straddle a 24-channel group
-            const int ch = k6 * 32 + 8 * g4;
-            frag_load(df[k6], da1 + ((size_t)(ch / TF_CG) * ntok + n0 + tc) * TF_CG + ch % TF_CG);
-        }
-#pragma unroll
-        for (int mt = 0; mt < TF_H / 16; ++mt) {
-            xr[mt] = *reinterpret_cast<const u32x2*>(xb + (size_t)tc * TF_H + 16 * mt + 4 * g4);
-            dr[mt] = *reinterpret_cast<const u32x2*>(dyb + (size_t)tc * TF_H + 16 * mt + 4 * g4);
-        }
-        if (s16 == w) lds_barrier();  // the fragments are in LDS, aff is zeroed (every wave passes here exactly once)
-        f32x4 du[TF_H / 16];
-#pragma unroll
-        for (int mt = 0; mt < TF_H / 16; ++mt) du[mt] = F32X4_ZERO;
-#pragma unroll
-        for (int k6 = 0; k6 < TF_FFN / 32; ++k6)
-#pragma unroll
-            for (int mt = 0; mt < TF_H / 16; ++mt) {
-                Frag<T> a;
-                frag_load(a, wl + ((size_t)(mt * (TF_FFN / 32) + k6) * 64 + lane) * 8);
-                du[mt] = mma(a, df[k6], du[mt]);
-            }
-        float xv[TF_H / 16][4];
-        float sum = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < TF_H / 16; ++mt) {
-            xv[mt][0] = bf2f((bf16_t)(xr[mt][0] & 0xFFFF)); xv[mt][1] = bf2f((bf16_t)(xr[mt][0] >> 16));
-            xv[mt][2] = bf2f((bf16_t)(xr[mt][1] & 0xFFFF)); xv[mt][3] = bf2f((bf16_t)(xr[mt][1] >> 16));
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sum += xv[mt][r];
-        }
-        const float mean = wave_sum16(sum) * (1.0f / TF_H);
-        float q = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < TF_H / 16; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xv[mt][r] -= mean;
-                q += xv[mt][r] * xv[mt][r];
-            }
-        const float rstd = rsqrtf(wave_sum16(q) * (1.0f / TF_H) + 1e-5f);
-        if (tv && g4 == 0) {
-            stats[(n0 + tt) * 2] = mean;
-            stats[(n0 + tt) * 2 + 1] = rstd;
-        }
-        float m1 = 0.f, m2 = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < TF_H / 16; ++mt) {
-            float gq4[4];
-            load4(lnl + 16 * mt + 4 * g4, gq4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xv[mt][r] *= rstd;  // \hat x
-                du[mt][r] = keep_if(tv, du[mt][r]);
-                const float gq = du[mt][r] * gq4[r];
-                m1 += gq;
-                m2 += gq * xv[mt][r];
-            }
-        }
-        m1 = wave_sum16(m1) * (1.0f / TF_H);
-        m2 = wave_sum16(m2) * (1.0f / TF_H);
-        if (tv) {
-#pragma unroll
-            for (int mt = 0; mt < TF_H / 16; ++mt) {
-                const float dd[4] = {bf2f((bf16_t)(dr[mt][0] & 0xFFFF)), bf2f((bf16_t)(dr[mt][0] >> 16)), bf2f((bf16_t)(dr[mt][1] & 0xFFFF)),
-                                     bf2f((bf16_t)(dr[mt][1] >> 16))};
-                float o[4], gq4[4];
-                load4(lnl + 16 * mt + 4 * g4, gq4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = dd[r] + rstd * (du[mt][r] * gq4[r] - m1 - xv[mt][r] * m2);
-                store4(dxb + (size_t)tt * TF_H + 16 * mt + 4 * g4, o[0], o[1], o[2], o[3]);
-            }
-        }
-        // LayerNorm affine gradients of the strip: reduced over its 16 frames, added to the workgroup sums
-#pragma unroll
-        for (int mt = 0; mt < TF_H / 16; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float a = sum_l15(du[mt][r] * xv[mt][r]), b = sum_l15(du[mt][r]);
-                if (l15 == 0) {
-                    atomicAdd(aff + 16 * mt + 4 * g4 + r, a);
-                    atomicAdd(aff + TF_H + 16 * mt + 4 * g4 + r, b);
-                }
-            }
-    }
-    lds_barrier();
-    for (int i = tid; i < 2 * TF_H; i += blockDim.x) part[(size_t)blockIdx.x * TF_AFF + 2 * TF_FFN + i] = aff[i];
-}
-
 int tconvffn_bwd_s_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* x, const void* dy,
                           void* const* opsv, float* stats, int pstride, hipStream_t st);
 struct TailArgs;
 int tailw_tconvffn(const nbss_cfg& c, const LayerPtrs& lp, const void* packed, int layer, const void* x, const void* dy, void* dx, float* stats,
                    const void* da1, float* wgpart, float* G, const float* P, hipStream_t st, const Side* sd, hipStream_t* gs);
 
-// the tail (du, LayerNorm backward, dx) runs inside the W1 weight-gradient kernel (tailw.hip) unless built with -DNBSS_NO_TAILW (A/B flavour)
-#ifdef NBSS_NO_TAILW
-#define TF_FUSED_TAIL 0
-#else
-#define TF_FUSED_TAIL 1
-#endif
-
-// bf16 stream: data-gradient kernel of tconvffn_s.hip + the tail (same operand tensors, same `part` rows as the group-serial kernel)
+// bf16 stream: data-gradient kernel of tconvffn_s.hip + the tail (du, LayerNorm backward, dx) inside the W1 weight-gradient kernel (tailw.hip)
 static int tconvffn_bwd_bf16(const nbss_cfg& c, const float* P, float* G, float* part, const void* packed, int layer, const void* x, const void* dy, void* dx,
                              float* stats, void* const* opsv, float* wgpart, hipStream_t st, const Side* sd, hipStream_t* gs) {
     const LayerPtrs lp = layer_ptrs(c, P, layer);
     ProfScope ps(PK_TCF_B, st);  // both kernels of the sub-block: ONE profiler interval per nbss_tconvffn_bwd call
-    if (TF_FUSED_TAIL) {
-        int e = tconvffn_bwd_s_launch(c, lp, part, packed, layer, x, dy, opsv, stats, 2 * TF_FFN, st);
-        if (e) return e;
-        return tailw_tconvffn(c, lp, packed, layer, x, dy, dx, stats, opsv[4], wgpart, G, P, st, sd, gs);
-    }
-    int e = tconvffn_bwd_s_launch(c, lp, part, packed, layer, x, dy, opsv, nullptr, TF_AFF, st);
+    int e = tconvffn_bwd_s_launch(c, lp, part, packed, layer, x, dy, opsv, stats, 2 * TF_FFN, st);
     if (e) return e;
-    const bf16_t* pk = (const bf16_t*)packed;
-    NBSS_LAUNCH((tconvffn_du_kernel<bf16_t>), dim3(c.B * c.F), dim3(1024), 36 * 512 * sizeof(bf16_t) + 3 * TF_H * sizeof(float), st, c, lp, part, pk + pack_off(c, layer, K_TF_W1_TN),
-                (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, stats, (const bf16_t*)opsv[4]);
-    return NBSS_CHECK_LAUNCH();
+    return tailw_tconvffn(c, lp, packed, layer, x, dy, dx, stats, opsv[4], wgpart, G, P, st, sd, gs);
 }
 
 template <class T>
@@ -1114,30 +975,14 @@ static int tconvffn_bwd_t(const nbss_cfg& c, const float* P, float* part, const 
     return NBSS_CHECK_LAUNCH();
 }
 
-int tconvffn_bwd_v_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* dy, void* tsave, void* op_da1,
-                          hipStream_t st);
 float* tconvffn_save_ln_stats(const nbss_cfg& c, void* tsave);
-int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, float* G, const long long* offs, bool with_w2, hipStream_t st);
+int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, float* G, const long long* offs, hipStream_t st);
 int tconvffn_bwd_q_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* dy, void* tsave, void* op_h5, void* op_da1,
                           hipStream_t st);
-#ifndef NBSS_TCF_BWD_DEFAULT_Q
-#define NBSS_TCF_BWD_DEFAULT_Q 1
-#endif
-// which data-gradient kernel of tconvffn_s.hip: 1 = tconvffn_bwd_q (a sequence's group pairs: two workgroups per CU; h5 operand + wgrad.hip for W2),
-// 0 = tconvffn_bwd_v (four groups per workgroup, the W2 weight gradient contracted inside).  NBSS_TCF_BWD=v|q overrides (A/B; read once per process).
-// Same-box measurements (profiles/README.md, round 5): the sub-block (data-gradient kernel + tail kernel) 11.2 ms per step with v, 9.6 with q; the step
-// 656-660 utt/s with v, 661-662 with q (in order 656.7 / 656.2): q's W2 weight gradient is a launch of its own again (147 us in order) — contracting it in
-// the tail kernel instead (four images per chunk) made THAT kernel 160-250 us slower, in bwd_v it costs what it saves.
-static bool tcf_use_q() {
-    static const int v = [] {
-        const char* e = getenv("NBSS_TCF_BWD");
-        return e ? (e[0] == 'q' ? 1 : 0) : NBSS_TCF_BWD_DEFAULT_Q;
-    }();
-    return v != 0;
-}
 
-// bf16 stream, from the pre-activations a training-mode forward saved (tconvffn_s.hip): data gradient + the three T-conv weight gradients + the
-// W2 weight gradient in one kernel, the tail + W1 weight gradient in tailw.hip, one fold of the per-sequence partial rows
+// bf16 stream, from the pre-activations a training-mode forward saved (tconvffn_s.hip): data gradient + the three T-conv weight gradients in
+// tconvffn_bwd_q (a sequence's group pairs: two workgroups per CU), the tail + W1 weight gradient in tailw.hip, one fold of the per-sequence partial
+// rows, W2's weight gradient from the h5 operand through wgrad.hip
 static int tconvffn_bwd_saved(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, void* tsave,
                               void* dx, void* ws, hipStream_t st, const Side* sd) {
     const LayerPtrs lp = layer_ptrs(c, P, layer);
@@ -1147,28 +992,24 @@ static int tconvffn_bwd_saved(const nbss_cfg& c, const float* P, float* G, const
     void* op_da1 = base + (size_t)4 * ws_align(N * TF_FFN * 2);
     float* part = (float*)((char*)ws + ws_tcpart_offset(c));
     float* wgpart = (float*)((char*)ws + ws_wgpart_offset(c));
-    const bool q = tcf_use_q();
     int e;
     hipStream_t gs = st;  // parameter-gradient launches (side.h): everything behind the tail kernel
     FoldScope fs(st, wgpart, WGPART_BYTES, N);  // (fold.h: the sub-block's seven fold launches leave as two, one per stage, on the gradient stream)
     {
         ProfScope ps(PK_TCF_B, st);  // both kernels of the sub-block: ONE profiler interval per nbss_tconvffn_bwd call
-        if ((e = q ? tconvffn_bwd_q_launch(c, lp, part, packed, layer, dy, tsave, op_h5, op_da1, st) : tconvffn_bwd_v_launch(c, lp, part, packed, layer, dy, tsave, op_da1, st)))
-            return e;
+        if ((e = tconvffn_bwd_q_launch(c, lp, part, packed, layer, dy, tsave, op_h5, op_da1, st))) return e;
         if ((e = tailw_tconvffn(c, lp, packed, layer, x, dy, dx, tconvffn_save_ln_stats(c, tsave), op_da1, wgpart, G, P, st, sd, &gs))) return e;
     }
     const int convW[3] = {P_TF_C1W, P_TF_C2W, P_TF_C3W}, convBias[3] = {P_TF_C1B, P_TF_C2B, P_TF_C3B};
-    AffSegs sg;  // fp32 rows: GroupNorm affine sums + the three conv bias sums (+ W2's bias sums from the four-group kernel)
-    sg.n = q ? 5 : 6;
+    AffSegs sg;  // fp32 rows: GroupNorm affine sums + the three conv bias sums
+    sg.n = 5;
     sg.off[0] = param_off(c, layer, P_TF_GN_W); sg.cnt[0] = TF_FFN;
     sg.off[1] = param_off(c, layer, P_TF_GN_B); sg.cnt[1] = TF_FFN;
     for (int k = 0; k < 3; ++k) { sg.off[2 + k] = param_off(c, layer, convBias[k]); sg.cnt[2 + k] = TF_FFN; }
-    sg.off[5] = param_off(c, layer, P_TF_B2); sg.cnt[5] = TF_H;
     if ((e = affine_reduce_launch(part, c.B * c.F, sg, G, gs))) return e;
-    const long long woffs[4] = {param_off(c, layer, convW[0]), param_off(c, layer, convW[1]), param_off(c, layer, convW[2]), param_off(c, layer, P_TF_W2)};
-    // (the slice sums of the fold live in the wgrad partial-tile region, idle between this sub-block's wgrad launches: 64 x 59 904 floats = 15.3 MB)
-    if ((e = tconvffn_v_reduce16(c, part + (size_t)c.B * c.F * (5 * TF_FFN + (q ? 0 : TF_H)), wgpart, G, woffs, !q, gs))) return e;
-    if (!q) return fs.end();
+    const long long woffs[3] = {param_off(c, layer, convW[0]), param_off(c, layer, convW[1]), param_off(c, layer, convW[2])};
+    // (the slice sums of the fold live in the wgrad partial-tile region, idle between this sub-block's wgrad launches)
+    if ((e = tconvffn_v_reduce16(c, part + (size_t)c.B * c.F * 5 * TF_FFN, wgpart, G, woffs, gs))) return e;
     // W2: dW2[H][FFN] = dy^T h5 ; db2 = colsum(dy)
     WgradArgs a;
     a.part = wgpart;
@@ -1195,7 +1036,7 @@ int tconvffn_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* p
     for (int i = 0; i < 8; ++i) ops[i] = base + (size_t)i * ws_align(N * TF_FFN * esz);
     float* part = (float*)((char*)ws + ws_part_offset(c));
     float* wgpart = (float*)((char*)ws + ws_wgpart_offset(c));
-    const bool fused = c.dtype == NBSS_BF16 && TF_FUSED_TAIL;  // the tail kernel contracted dW1 / db1 and reduced the LayerNorm affine sums
+    const bool fused = c.dtype == NBSS_BF16;  // the tail kernel contracted dW1 / db1 and reduced the LayerNorm affine sums
     hipStream_t gs = st;  // parameter-gradient launches (side.h)
     int e = c.dtype == NBSS_BF16 ? tconvffn_bwd_bf16(c, P, G, part, packed, layer, x, dy, dx, stats, ops, wgpart, st, sd, &gs)
                                  : tconvffn_bwd_t<float>(c, P, part, packed, layer, x, dy, dx, stats, ops, st);

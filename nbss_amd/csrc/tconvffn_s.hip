@@ -78,13 +78,7 @@ NBSS_DEV void silu_pack(const f32x16& a, uint32_t vm, P6& out) {
 }
 
 NBSS_DEV void p6_gstore(bf16_t* __restrict__ g, const P6& p, bool ok, bool nt) {  // g = &op[group][token][4 h]
-#ifdef NBSS_K1_NOSTORE  // knock-out probe (flavour build): how much of the kernel is the operand stores?
-    return;
-#endif
     if (!ok) return;
-#ifdef NBSS_TS_NT0  // (A/B flavour: plain stores)
-    nt = false;
-#endif
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         u32x2 v = {p.d[2 * q], p.d[2 * q + 1]};
@@ -169,7 +163,7 @@ struct TsFwdW {  // packed fragment bases of one layer
 #define TS_SB 2  // strips per block of a group phase (independent MFMA chains in flight)
 #endif
 
-// What a training-mode forward keeps for the backward pass (tconvffn_bwd_v_kernel below): the pre-activations a1 (W1 output), a2, a3
+// What a training-mode forward keeps for the backward pass (tconvffn_bwd_q_kernel below): the pre-activations a1 (W1 output), a2, a3
 // (conv1 / conv2 outputs; a3 = GroupNorm input) as group-major [G][N][24] bf16 tensors — what the reference's autocast graph holds as
 // bf16 conv outputs —, the LayerNorm (mean, rstd) of every token and the GroupNorm (mean, rstd) of every (sequence, group).  With them
 // the backward pass evaluates each SiLU / SiLU' pair from ONE sigmoid and recomputes one convolution only: a5 = conv3(h4), whose input
@@ -284,15 +278,6 @@ __global__ __launch_bounds__(512) void tconvffn_fwd_s_kernel(nbss_cfg c, LayerPt
             for (int ks = 1; ks < 7; ++ks) a1 = mma32(w1[ks], u[ks], a1);
             P6 h1;
             silu_pack(a1, vm, h1);
-#ifdef NBSS_TS_LANE_SAVE  // (A/B flavour: rounds 3-5's lane-wise saves)
-            p6_store(orow + g * TS_CG, h1);
-            if (SAVE) {
-                P6 pa;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) pa.d[i] = pack2bf(a1[2 * i], a1[2 * i + 1]);
-                p6_gstore(sv.a1 + ((size_t)g * ntok + n0 + t) * TS_CG + 4 * L.h, pa, tv, true);
-            }
-#else
             if (SAVE) {
                 // The saved pre-activation leaves as WHOLE ROWS (round 6): staged in the image where h1 of the same group goes — the wave's own 32 rows,
                 // nobody else touches them before the barrier —, read back one group later as 16-byte pieces in address order and only then replaced
@@ -312,16 +297,13 @@ __global__ __launch_bounds__(512) void tconvffn_fwd_s_kernel(nbss_cfg c, LayerPt
             } else {
                 p6_store(orow + g * TS_CG, h1);
             }
-#endif
         }
-#ifndef NBSS_TS_LANE_SAVE
         if (SAVE) {
             wave_lds_sync();
             rows_gstore_t<96, TS_RS>(sv.a1 + ((size_t)(TS_G - 1) * ntok + n0 + 32 * w) * TS_CG, img + (size_t)(3 + 32 * w) * TS_RS + (TS_G - 1) * TS_CG, 32, T_ - 32 * w);
             wave_lds_sync();
             p6_store(orow + (TS_G - 1) * TS_CG, hprev);
         }
-#endif
     }
     PHASE(0);
     lds_barrier();
@@ -338,7 +320,7 @@ __global__ __launch_bounds__(512) void tconvffn_fwd_s_kernel(nbss_cfg c, LayerPt
     // ---- group phases: wave g owns channels 24g..24g+23 of every row ------------------------------------------------------------
     const int g = w, cbase = g * TS_CG;
     bf16_t* col = img + cbase;  // &img[0][24 g]
-    const size_t gsave0 = ((size_t)g * ntok + n0) * TS_CG, gsave = gsave0 + 4 * L.h;  // token 0 of this group in a saved [G][N][24] tensor (+ this lane's piece)
+    const size_t gsave0 = ((size_t)g * ntok + n0) * TS_CG;  // token 0 of this group in a saved [G][N][24] tensor
     bf16_t* scr = wl + (size_t)NV2 * 8 + (size_t)w * (32 * TS_CG);  // [32][24] per wave, behind the 39 W2 fragments
     // conv1: h1 (rows 3 + t) -> h2 = SiLU(.) (rows 2 + t)
 #pragma unroll 1
@@ -358,15 +340,11 @@ __global__ __launch_bounds__(512) void tconvffn_fwd_s_kernel(nbss_cfg c, LayerPt
                     P6 pa;
 #pragma unroll
                     for (int i = 0; i < 6; ++i) pa.d[i] = pack2bf(a2[2 * i], a2[2 * i + 1]);
-#ifdef NBSS_TS_LANE_SAVE
-                    p6_gstore(sv.a2 + gsave + (size_t)(32 * (s0 + k) + L.n) * TS_CG, pa, 32 * (s0 + k) + L.n < T_, true);
-#else
                     // whole rows through the wave's scratch strip (the window's 17 KB behind the W2 fragments: W1 is dead since the barrier)
                     p6_store(scr + L.n * TS_CG + 4 * L.h, pa);
                     wave_lds_sync();
                     rows_gstore_t<96, TS_CG>(sv.a2 + gsave0 + (size_t)32 * (s0 + k) * TS_CG, scr, 32, T_ - 32 * (s0 + k));
                     wave_lds_sync();
-#endif
                 }
             }
     }
@@ -400,19 +378,14 @@ __global__ __launch_bounds__(512) void tconvffn_fwd_s_kernel(nbss_cfg c, LayerPt
                     s2 += v0 * v0 + v1 * v1;
                 }
                 p6_store(col + (size_t)(1 + 32 * (s0 + k) + L.n) * TS_RS + 4 * L.h, a3p);
-#ifdef NBSS_TS_LANE_SAVE
-                if (SAVE) p6_gstore(sv.a3 + gsave + (size_t)(32 * (s0 + k) + L.n) * TS_CG, a3p, 32 * (s0 + k) + L.n < T_, true);
-#endif
             }
     }
     if (L.lane < 6) *reinterpret_cast<u32x2*>(col + (size_t)(1 + NT) * TS_RS + 4 * L.lane) = (u32x2){0u, 0u};
-#ifndef NBSS_TS_LANE_SAVE
     if (SAVE) {  // a3 sits in the image (rows 1 + t of the group's column) until GroupNorm rewrites it: the whole column slice leaves in address order
         wave_lds_sync();
         rows_gstore_t<3 * 256, TS_RS>(sv.a3 + gsave0, col + (size_t)TS_RS, NT, T_);
         wave_lds_sync();
     }
-#endif
     s1 = wave_sum64(s1);
     s2 = wave_sum64(s2);
     const float cnt = (float)(TS_CG * T_);
@@ -1211,13 +1184,8 @@ int tconvffn_bwd_s_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, c
 //     constant-one operand, and the workgroup's partial leaves in dW's own memory order inside the sequence's `part` row, which
 //     affine_reduce folds (the fconv_bwd pattern, profiles/README.md row 45).
 // Gone per layer: 12 S.B of operand stores, 12 S.B of operand reads, three wgrad_tr3 launches; new: 8 S.B of saved pre-activations written
-// by the forward and read here, 170 KB of partial row per sequence.  Still emitted: da1 (tail + W1 weight gradient, tailw.hip).
-//   * (round 5) the W2 weight gradient dW2[o][c] = sum_t dy[t][o] h5[t][c] is contracted here as well: the strip phase leaves its dy strip
-//     in a third LDS image D ([frame][96], 200-byte rows: the three images fill 158 of the 160 KB), h5 — rebuilt from a5 in stage 1b — is
-//     parked in registers until the conv3 contraction has released H, written there, and after the next barrier waves 0-5 contract one
-//     16-channel tile column of the workgroup's 96 x 96 block each (wave 6: db2 = colsum(dy)); the partial leaves inside the sequence's
-//     bf16 row as [channel][output] and is folded with the conv weight gradients.  Gone per layer: the h5 operand (2 S.B of lane-wise
-//     stores, 2 S.B of reads), the dy re-read and the wgrad_tr3<64,10> launch with its fold.
+// by the forward and read here, 170 KB of partial row per sequence.  Still emitted: da1 (tail + W1 weight gradient, tailw.hip) and h5 (the
+// W2 weight gradient, wgrad.hip).
 struct TvIn {
     const bf16_t *a1, *a2, *a3;
     const float* gn;
@@ -1226,12 +1194,9 @@ struct TvW {
     const bf16_t *W2T, *C1T, *C2T, *C3T, *C3;
 };
 #define TV_CONVW (TS_FFN * TS_CG * 3)                 // one conv weight [192][24][3]
-#define TV_PSTRIDE (2 * TS_FFN + 3 * TS_FFN + TS_H)    // floats per fp32 `part` row: GN w | GN b | conv1 b | conv2 b | conv3 b | W2 b
-#define TV_P16 (3 * TV_CONVW + TS_FFN * TS_H)          // bf16 per `part16` row: the three conv weight gradients, each as [group][tap][in][24 out], then dW2 as [FFN channel][H output]
-#define TQ_RS 56                                       // image row stride of the group-pair kernel (112 B: 48 channels + 8; conflict-free 16-byte row reads)
-#define TQ_PSTRIDE (5 * TS_FFN)                        // its fp32 `part` row: GN w | GN b | conv1 b | conv2 b | conv3 b
-#define TQ_P16 (3 * TV_CONVW)                          // its bf16 row: the three conv weight gradients
-#define TV_DRS 100                                     // dy image row stride in elements (200 B; with 208 B the three images miss the 160 KB by 176 bytes)
+#define TQ_RS 56                                       // image row stride (112 B: 48 channels + 8; conflict-free 16-byte row reads)
+#define TQ_PSTRIDE (5 * TS_FFN)                        // floats per fp32 `part` row: GN w | GN b | conv1 b | conv2 b | conv3 b
+#define TQ_P16 (3 * TV_CONVW)                          // bf16 per `part16` row: the three conv weight gradients, each as [group][tap][in][24 out]
 
 // dW tile accumulation of one conv group over the whole sequence.  Sg = &S[0][24 gl], Hg = &H[0][24 gl]; bases (bl, bu) as in the stage that
 // wrote S; H holds token t at row t + 1 (rows 0 and NT + 1 are zero).
@@ -1242,11 +1207,7 @@ NBSS_DEV void tv_contract_t(const bf16_t* Sg, const bf16_t* Hg, int bl, int bu, 
     // the frames).  The natural one — 4 g4 + (l15 >> 2): a 16-lane group reads four CONSECUTIVE rows — puts those rows 52 dwords apart (208-byte image
     // rows): bank offsets {0, 20, 8, 28}, and the 8-dword pieces of rows 0 and 3 overlap (SQ_LDS_BANK_CONFLICT 37 % of the kernel's LDS cycles,
     // round 4).  With every second row per group the offsets are {0, 8, 16, 24}: conflict-free.
-#ifdef NBSS_TV_ROWS_NATURAL
-    const int rowoff = 4 * g4 + (l15 >> 2);
-#else
     const int rowoff = 8 * (g4 >> 1) + (g4 & 1) + 2 * (l15 >> 2);
-#endif
     int boff[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -1273,9 +1234,6 @@ NBSS_DEV void tv_contract_t(const bf16_t* Sg, const bf16_t* Hg, int bl, int bu, 
         for (int j = 0; j < 5; ++j) acc[j] = mma(fa, fb[j], acc[j]);
     }
 }
-NBSS_DEV void tv_contract(const bf16_t* Sg, const bf16_t* Hg, int bl, int bu, int NS, int NSL, int mt, f32x4 (&acc)[5], f32x4& bsum) {
-    tv_contract_t<TB_RS>(Sg, Hg, bl, bu, NS, NSL, mt, acc, bsum);
-}
 // The per-sequence partial of a conv weight gradient leaves in bf16, as [group][tap][input channel][24 outputs of the group] (a lane's four output channels are one
 // 8-byte store; round 6: the rows of one store instruction are 48 bytes apart — one 768-byte region — instead of 384 bytes apart in [tap][in][192 out]); tconv_part_reduce_kernel sums the rows in fp32 and writes the parameter's own [out][in][tap] order.  (Under the reference's
 // autocast the weight gradient of a bf16 convolution IS a bf16 tensor before it is cast up for the fp32 parameter; here only the per-sequence
@@ -1284,9 +1242,6 @@ NBSS_DEV void tv_contract(const bf16_t* Sg, const bf16_t* Hg, int bl, int bu, in
 NBSS_DEV void tv_flush(bf16_t* __restrict__ w16, float* __restrict__ brow, int g, int mt, const f32x4 (&acc)[5], const f32x4& bsum) {
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4;
     const int oc0 = 16 * mt + 4 * g4;
-#ifdef TV_KO_FLUSH  // (timing knock-out, A/B flavour: the contraction stays — the compiler cannot see that the row pointer is never null — its stores go)
-    if (w16 != nullptr) return;
-#endif
     if (oc0 < TS_CG) {
         const int o0 = g * TS_CG + oc0;
 #pragma unroll
@@ -1319,475 +1274,10 @@ __global__ __launch_bounds__(256) void tconv_part_reduce2_kernel(const float* __
     fk_tconv_final(slices, nsl, G, off0, off1, off2, off3, P16, (int)blockIdx.x);
 }
 
-__global__ __launch_bounds__(512) void tconvffn_bwd_v_kernel(nbss_cfg c, LayerPtrs lp, TvW W, TvIn sv, const bf16_t* __restrict__ dy, float* __restrict__ part,
-                                                             bf16_t* __restrict__ part16, bf16_t* __restrict__ op_da1) {
-    NBSS_LDS(smem);
-    const int T_ = c.T, NS = (T_ + 31) >> 5, NT = NS * 32, NSL = NS >> 1, TS = 32 * NSL;
-    bf16_t* S = reinterpret_cast<bf16_t*>(smem);         // [NT + TB_PAD][TB_RS]  the gradient chain, in place
-    bf16_t* H = S + (size_t)(NT + TB_PAD) * TB_RS;      // [NT + 2][TB_RS]       the activation of the current stage (first: the W2^T window)
-    const size_t h_el = (size_t)(NT + 2) * TB_RS > (size_t)24 * 512 ? (size_t)(NT + 2) * TB_RS : (size_t)24 * 512;
-    float* red = reinterpret_cast<float*>(H + h_el);     // [4 groups][2 halves][2]
-    float* gnp = red + 16;                               // [2 halves][2 kinds][96] GroupNorm affine partial sums
-    bf16_t* mbox = reinterpret_cast<bf16_t*>(gnp + 4 * 96);  // [8 waves][24]
-    bf16_t* D = mbox + 8 * TS_CG;                            // [NT][TV_DRS]          dy of the sequence (the W2 weight gradient's other operand)
-    bf16_t* wl = H;
-    PHASE_BEGIN(D + (size_t)NT * TV_DRS);
-    const TsLane L;
-    const int w = wave_id_u(), tid = threadIdx.x;
-    const int row = blockIdx.x >> 1, gh = blockIdx.x & 1;
-    const size_t n0 = (size_t)row * T_, ntok = (size_t)c.B * c.F * T_;
-    const bf16_t* dyb = dy + n0 * TS_H;
-
-    // group-phase roles (wave = (group gl, half th)) — needed already here: the FIRST group stage's input (a3 of the wave's own strips)
-    // is requested together with the strip phase's inputs
-    const int gl = w >> 1, th = w & 1, g = 4 * gh + gl;
-    const int s_beg = th ? NSL : 0, s_end = th ? NS : NSL, nblk = (s_end - s_beg + TB_SB - 1) / TB_SB;
-    const size_t gsv = ((size_t)g * ntok + n0) * TS_CG + 4 * L.h;  // this lane's piece of token 0 in a saved [G][N][24] tensor
-    P6 pn0, pn1, pn2, pn3, pd0, pd1, pd2, pd3, ra0, ra1, ra2, ra3;
-#define TV_LOADA(k, src, dst)                                                        \
-    {                                                                                \
-        const int t_ = 32 * (s_beg + (k)) + L.n, tc_ = t_ < T_ ? t_ : T_ - 1;        \
-        if (s_beg + (k) < s_end) p6_gload((src) + gsv + (size_t)tc_ * TS_CG, dst);   \
-        else                                                                         \
-            for (int i_ = 0; i_ < 6; ++i_) dst.d[i_] = 0u;                           \
-    }
-#define TV_LOADA4(src) TV_LOADA(0, src, ra0) TV_LOADA(1, src, ra1) TV_LOADA(2, src, ra2) TV_LOADA(3, src, ra3)
-    // ---- strip phase: dh5 = W2^T dy -> S at bases (1,7) (it becomes da5 in place once a5 has been rebuilt from h4, stage 1b) --------------------
-    {
-        u32x4 wr[3];  // 24 W2^T fragments of this workgroup's four groups
-#pragma unroll
-        for (int i = 0; i < 3; ++i) wr[i] = reinterpret_cast<const u32x4*>(W.W2T + (size_t)gh * 24 * 512)[tid + i * 512];
-        u32x4 rawd[6];
-        const int t = 32 * w + L.n, tc = t < T_ ? t : T_ - 1;
-#pragma unroll
-        for (int ks = 0; ks < 6; ++ks) rawd[ks] = *reinterpret_cast<const u32x4*>(dyb + (size_t)tc * TS_H + 16 * ks + 8 * L.h);
-        TV_LOADA4(sv.a3)
-        for (int i = tid; i < 4 * TB_RS / 2; i += 512) reinterpret_cast<uint32_t*>(S)[i] = 0u;
-        for (int i = tid; i < 5 * TB_RS / 2; i += 512) reinterpret_cast<uint32_t*>(S + (size_t)(NT + 4) * TB_RS)[i] = 0u;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) reinterpret_cast<u32x4*>(wl)[tid + i * 512] = wr[i];
-        PHASE(0);
-        lds_barrier();
-        PHASE(1);
-        if (w < NS) {
-            const uint32_t vm = lane_mask(t < T_);
-            FragH dq[6];
-#pragma unroll
-            for (int ks = 0; ks < 6; ++ks) dq[ks].v = __builtin_bit_cast(s16x8, rawd[ks]);
-            {  // the strip's dy rows -> D (frames past T: zero rows)
-                bf16_t* drow = D + (size_t)t * TV_DRS + 8 * L.h;
-#pragma unroll
-                for (int ks = 0; ks < 6; ++ks) {
-                    *reinterpret_cast<u32x2*>(drow + 16 * ks) = (u32x2){rawd[ks][0] & vm, rawd[ks][1] & vm};
-                    *reinterpret_cast<u32x2*>(drow + 16 * ks + 4) = (u32x2){rawd[ks][2] & vm, rawd[ks][3] & vm};
-                }
-            }
-            bf16_t* srow = S + (size_t)((w < NSL ? 1 : 7) + t) * TB_RS + 4 * L.h;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                FragH w2t[6];
-                load_wfrags<6>(w2t, wl, q, L.lane);
-                f32x16 d5 = mma32(w2t[0], dq[0], f32x16_zero());
-#pragma unroll
-                for (int ks = 1; ks < 6; ++ks) d5 = mma32(w2t[ks], dq[ks], d5);
-                float dv[12];
-#pragma unroll
-                for (int r = 0; r < 12; ++r) dv[r] = d5[r];
-                P6 pd;
-                p6_pack(dv, vm, pd);
-                p6_store(srow + q * TS_CG, pd);
-            }
-        }
-    }
-    PHASE(2);
-
-    // ---- group phases: wave = (group gl, half th) ------------------------------------------------------------------------------------------------
-    bf16_t* Sc = S + gl * TS_CG;
-    bf16_t* Hc = H + gl * TS_CG;
-    const int run0 = 32 * s_beg, nrun = 32 * (s_end - s_beg);
-    auto rowp = [&](int tt, int bl, int bu) -> const bf16_t* { return Sc + (size_t)((tt < TS ? bl : bu) + tt) * TB_RS; };
-    auto orow = [&](int tt, int bl, int bu) -> bf16_t* { return Sc + (size_t)((th ? bu : bl) + tt) * TB_RS + 4 * L.h; };
-    bf16_t* mb = mbox + w * TS_CG;
-    auto fetch_cross = [&](int bl, int bu) {  // (see tconvffn_bwd_s_kernel: the one row a wave reads across the middle is copied before the stage writes)
-        const bf16_t* src = Sc + (size_t)(th ? bl + TS - 1 : bu + TS) * TB_RS;
-        if (L.lane < 6) *reinterpret_cast<u32x2*>(mb + 4 * L.lane) = *reinterpret_cast<const u32x2*>(src + 4 * L.lane);
-        lds_barrier();
-    };
-    auto rowx = [&](int tt, int bl, int bu) -> const bf16_t* {
-        const bool lower = tt < TS;
-        const bf16_t* r = Sc + (size_t)((lower ? bl : bu) + tt) * TB_RS;
-        return lower != (th == 0) ? mb : r;
-    };
-    float gw[12], gb[12];
-    chan_vec12(lp.p[P_TF_GN_W] + g * TS_CG, L.h, gw);
-    chan_vec12(lp.p[P_TF_GN_B] + g * TS_CG, L.h, gb);
-    const float cnt = (float)(TS_CG * T_);
-    const float gmean = sv.gn[((size_t)row * TS_G + g) * 2], grstd = sv.gn[((size_t)row * TS_G + g) * 2 + 1];
-    float* prow = part + (size_t)row * TV_PSTRIDE + 2 * TS_FFN;   // conv bias blocks of the fp32 row
-    bf16_t* prow16 = part16 + (size_t)row * TV_P16;
-
-    FragH wt[5];
-    load_wfrags<5>(wt, W.C3T, g, L.lane);
-    // per-strip parks pn* / pd* / ra*: named registers + per-dword selects (indexed structs become scratch arrays, see the kernel above)
-#define TV_PICK(dst, k_, hib_, q0, q1, q2, q3)                                                            \
-    for (int i_ = 0; i_ < 6; ++i_) {                                                                      \
-        const uint32_t lo_ = (k_) == 0 ? q0.d[i_] : q1.d[i_], hi_ = (k_) == 0 ? q2.d[i_] : q3.d[i_];      \
-        dst.d[i_] = (hib_) ? hi_ : lo_;                                                                   \
-    }
-#define TB_BLOCKS(fwd_dir)                                                   \
-    for (int bi_ = 0; bi_ < nblk; ++bi_)                                     \
-        for (int s0 = s_beg + TB_SB * (((fwd_dir) == (th == 0)) ? bi_ : nblk - 1 - bi_), once_ = 1; once_; once_ = 0)
-
-    // stage 1: a3 -> a3hat (parked), h4 = SiLU(a3hat gw + gb) -> H, SiLU' parked
-    lds_barrier();  // S = da5 is complete; the weight window (aliasing H) is dead
-    PHASE(3);
-    if (L.lane < 6) *reinterpret_cast<u32x2*>(Hc + (size_t)(th ? NT + 1 : 0) * TB_RS + 4 * L.lane) = (u32x2){0u, 0u};  // H's halo rows
-#define TV_STAGE1(k, RA, PN, PD)                                                          \
-    if (s_beg + (k) < s_end) {                                                            \
-        const int t = 32 * (s_beg + (k)) + L.n;                                           \
-        const uint32_t vm = lane_mask(t < T_);                                            \
-        float a3[12], hv[12], dv[12];                                                     \
-        p6_unpack(RA, a3);                                                                \
-        for (int q = 0; q < 12; ++q) a3[q] = (a3[q] - gmean) * grstd;                     \
-        p6_pack(a3, vm, PN);                                                              \
-        p6_unpack(PN, a3);                                                                \
-        for (int q = 0; q < 12; ++q) silu_dsilu(a3[q] * gw[q] + gb[q], hv[q], dv[q]);     \
-        P6 ph;                                                                            \
-        p6_pack(hv, vm, ph);                                                              \
-        p6_pack(dv, vm, PD);                                                              \
-        p6_store(Hc + (size_t)(1 + t) * TB_RS + 4 * L.h, ph);                             \
-    } else {                                                                              \
-        for (int i_ = 0; i_ < 6; ++i_) PN.d[i_] = PD.d[i_] = 0u;                          \
-    }
-    TV_STAGE1(0, ra0, pn0, pd0)
-    TV_STAGE1(1, ra1, pn1, pd1)
-    TV_STAGE1(2, ra2, pn2, pd2)
-    TV_STAGE1(3, ra3, pn3, pd3)
-#undef TV_STAGE1
-    PHASE(4);
-    lds_barrier();
-    // stage 1b: a5 = conv3(h4) rebuilt from H (own strips; neighbours' rows are complete), (h5, SiLU'(a5)) from one sigmoid: h5 -> parked in ra*
-    // (H still holds h4 for the conv3 contraction), da5 = dh5 * SiLU'(a5) in place in S (this lane's own piece)
-    {
-        FragH wf[5];
-        load_wfrags<5>(wf, W.C3, g, L.lane);
-#pragma unroll 1
-        for (int s0 = s_beg; s0 < s_end; s0 += TB_SB) {
-            FragH b[TB_SB][5];
-            const bool hib = s0 - s_beg >= 2;
-#pragma unroll
-            for (int k = 0; k < TB_SB; ++k)
-                if (s0 + k < s_end) {
-                    const bf16_t* r1 = Hc + (size_t)(1 + 32 * (s0 + k) + L.n) * TB_RS;
-                    conv_bfrags3(L, r1 - TB_RS, r1, r1 + TB_RS, b[k]);
-                }
-#pragma unroll
-            for (int k = 0; k < TB_SB; ++k)
-                if (s0 + k < s_end) {
-                    const int t = 32 * (s0 + k) + L.n;
-                    const bool tv = t < T_;
-                    const uint32_t vm = lane_mask(tv);
-                    const f32x16 a5 = conv_mma(wf, b[k]);
-                    bf16_t* r = orow(t, 1, 7);
-                    P6 p5, ph, pd;
-                    p6_load(r, p5);
-                    float hv[12], dv[12], d5[12];
-                    p6_unpack(p5, d5);
-#pragma unroll
-                    for (int q = 0; q < 12; ++q) {
-                        silu_dsilu(a5[q], hv[q], dv[q]);
-                        dv[q] *= d5[q];
-                    }
-                    p6_pack(hv, vm, ph);
-                    p6_pack(dv, vm, pd);
-                    p6_store(r, pd);
-#pragma unroll
-                    for (int i_ = 0; i_ < 6; ++i_) {  // park h5 of strip 2 hib + k (named registers + selects, as TV_PICK)
-                        if (k == 0) {
-                            ra0.d[i_] = hib ? ra0.d[i_] : ph.d[i_];
-                            ra2.d[i_] = hib ? ph.d[i_] : ra2.d[i_];
-                        } else {
-                            ra1.d[i_] = hib ? ra1.d[i_] : ph.d[i_];
-                            ra3.d[i_] = hib ? ph.d[i_] : ra3.d[i_];
-                        }
-                    }
-                }
-        }
-    }
-    lds_barrier();
-    PHASE(5);
-    // stage 2: conv3 weight gradient: da5 (1,7) x h4
-    {
-        f32x4 acc[5], bsum;
-        tv_contract(Sc, Hc, 1, 7, NS, NSL, th, acc, bsum);
-        tv_flush(prow16 + 2 * TV_CONVW, prow + 2 * TS_FFN, g, th, acc, bsum);
-    }
-    PHASE(6);
-    // B3: conv3^T: da5 (1,7) -> dh4; dn3 = dh4 * SiLU'(n3) -> S (2,6); GroupNorm backward sums and affine gradients
-    fetch_cross(1, 7);
-    // (every wave is past its conv3 contraction: H is free) h5 -> H for the W2 contraction behind B3's barrier; then the a2 request (needed in B3b)
-#define TV_H5STORE(k, RA)                                                                                                      \
-    if (s_beg + (k) < s_end) p6_store(Hc + (size_t)(1 + 32 * (s_beg + (k)) + L.n) * TB_RS + 4 * L.h, RA);
-    TV_H5STORE(0, ra0) TV_H5STORE(1, ra1) TV_H5STORE(2, ra2) TV_H5STORE(3, ra3)
-#undef TV_H5STORE
-    TV_LOADA4(sv.a2)
-    PHASE(7);
-    {
-        float sa = 0.f, sb = 0.f, dgw[12], dgb[12];
-#pragma unroll
-        for (int r = 0; r < 12; ++r) dgw[r] = dgb[r] = 0.f;
-#pragma unroll 1
-        TB_BLOCKS(false) {
-            FragH b[TB_SB][5];
-            const bool hib = s0 - s_beg >= 2;
-#pragma unroll
-            for (int k = 0; k < TB_SB; ++k)
-                if (s0 + k < s_end) {
-                    const int t = 32 * (s0 + k) + L.n;
-                    conv_bfrags3(L, rowx(t - 1, 1, 7), rowp(t, 1, 7), rowx(t + 1, 1, 7), b[k]);
-                }
-#pragma unroll
-            for (int k = 0; k < TB_SB; ++k)
-                if (s0 + k < s_end) {
-                    const int t = 32 * (s0 + k) + L.n;
-                    const uint32_t vm = lane_mask(t < T_);
-                    const f32x16 dh4 = conv_mma(wt, b[k]);
-                    P6 pn, pdv, pd;
-                    TV_PICK(pn, k, hib, pn0, pn1, pn2, pn3)
-                    TV_PICK(pdv, k, hib, pd0, pd1, pd2, pd3)
-                    float ah[12], d4[12], dn[12];
-                    p6_unpack(pn, ah);
-                    p6_unpack(pdv, d4);
-#pragma unroll
-                    for (int r = 0; r < 12; ++r) dn[r] = dh4[r] * d4[r];
-                    p6_pack(dn, vm, pd);
-                    p6_unpack(pd, dn);  // masked, bf16 (what the next stage reads back)
-#pragma unroll
-                    for (int r = 0; r < 12; ++r) {
-                        dgw[r] += dn[r] * ah[r];
-                        dgb[r] += dn[r];
-                        sa += gw[r] * dn[r];
-                        sb += gw[r] * dn[r] * ah[r];
-                    }
-                    p6_store(orow(t, 2, 6), pd);
-                }
-        }
-        sa = wave_sum64(sa);
-        sb = wave_sum64(sb);
-        if (L.lane == 0) {
-            red[(gl * 2 + th) * 2] = sa;
-            red[(gl * 2 + th) * 2 + 1] = sb;
-        }
-#pragma unroll
-        for (int r = 0; r < 12; ++r) {
-            const float a = half_sum32(dgw[r]), bq = half_sum32(dgb[r]);
-            if (L.n == 0) {
-                const int ch = gl * TS_CG + (r & 3) + 8 * (r >> 2) + 4 * L.h;
-                gnp[(th * 2 + 0) * 96 + ch] = a;
-                gnp[(th * 2 + 1) * 96 + ch] = bq;
-            }
-        }
-        if (L.lane < 6) *reinterpret_cast<u32x2*>(Sc + (size_t)(th ? NT + 6 : 1) * TB_RS + 4 * L.lane) = (u32x2){0u, 0u};
-    }
-    load_wfrags<5>(wt, W.C2T, g, L.lane);
-    PHASE(8);
-    lds_barrier();
-    // W2 weight gradient of the workgroup's 96 channels: dW2[o][c] = sum_t dy[t][o] h5[t][c]  (D x H, K = the frames).  Wave w < 6: channel tile w, all six
-    // output tiles (one h5 + six dy transposing fragment reads per six MFMAs and 32 frames); wave 6 of the sequence's first workgroup: db2 = colsum(dy)
-    {
-        const int l15 = L.lane & 15, g4 = L.lane >> 4;
-        const int rowoff = 4 * g4 + (l15 >> 2), c4 = 4 * (l15 & 3);
-        if (w < 6) {
-            f32x4 acc[6];
-#pragma unroll
-            for (int mt = 0; mt < 6; ++mt) acc[mt] = F32X4_ZERO;
-#pragma unroll 2
-            for (int ks = 0; ks < NS; ++ks) {
-                Frag<bf16_t> fb, fa[6];
-                frag_load_tr(fb, H + (size_t)(1 + 32 * ks + rowoff) * TB_RS + 16 * w + c4, TB_RS);
-#pragma unroll
-                for (int mt = 0; mt < 6; ++mt) frag_load_tr(fa[mt], D + (size_t)(32 * ks + rowoff) * TV_DRS + 16 * mt + c4, TV_DRS);
-#pragma unroll
-                for (int mt = 0; mt < 6; ++mt) acc[mt] = mma(fa[mt], fb, acc[mt]);
-            }
-            // lane: outputs 16 mt + 4 g4 + r of channel 96 gh + 16 w + l15 -> the sequence's bf16 row, [channel][output]: one 8-byte store per tile
-            bf16_t* dst = prow16 + 3 * TV_CONVW + (size_t)(96 * gh + 16 * w + l15) * TS_H + 4 * g4;
-#pragma unroll
-            for (int mt = 0; mt < 6; ++mt) *reinterpret_cast<u32x2*>(dst + 16 * mt) = (u32x2){pack2bf(acc[mt][0], acc[mt][1]), pack2bf(acc[mt][2], acc[mt][3])};
-        } else if (w == 6 && gh == 0) {
-            Frag<bf16_t> ones;
-#pragma unroll
-            for (int jq = 0; jq < 8; ++jq) frag_set(ones, jq, 1.0f);
-            f32x4 bs[6];
-#pragma unroll
-            for (int mt = 0; mt < 6; ++mt) bs[mt] = F32X4_ZERO;
-            for (int ks = 0; ks < NS; ++ks) {
-#pragma unroll
-                for (int mt = 0; mt < 6; ++mt) {
-                    Frag<bf16_t> fa;
-                    frag_load_tr(fa, D + (size_t)(32 * ks + rowoff) * TV_DRS + 16 * mt + c4, TV_DRS);
-                    bs[mt] = mma(fa, ones, bs[mt]);
-                }
-            }
-            if (l15 == 0) {  // every column holds the sums: rows 4 g4 + r
-                float* brow2 = part + (size_t)row * TV_PSTRIDE + 5 * TS_FFN + 4 * g4;
-#pragma unroll
-                for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) brow2[16 * mt + r] = bs[mt][r];
-            }
-        }
-    }
-    PHASE(19);
-    lds_barrier();  // H is rewritten (h2) by the next stage
-    PHASE(9);
-    // B3b (in place, own values): da3 = rstd (gw dn3 - mean(gw dn3) - a3hat mean(gw dn3 a3hat)) -> S (2,6);
-    // and the next activation: (h2, SiLU'(a2)) from the saved a2: h2 -> H (every wave is past its conv3 contraction), SiLU' parked
-    {
-        const float msa = (red[gl * 4] + red[gl * 4 + 2]) / cnt, msb = (red[gl * 4 + 1] + red[gl * 4 + 3]) / cnt;
-#define TV_STAGE3B(k, RA, PN, PD)                                                         \
-    if (s_beg + (k) < s_end) {                                                            \
-        const int t = 32 * (s_beg + (k)) + L.n;                                           \
-        const uint32_t vm = lane_mask(t < T_);                                            \
-        bf16_t* r = orow(t, 2, 6);                                                        \
-        P6 pdn, po, ph;                                                                   \
-        p6_load(r, pdn);                                                                  \
-        float dn[12], ah[12], a2[12], hv[12], dv[12];                                     \
-        p6_unpack(pdn, dn);                                                               \
-        p6_unpack(PN, ah);                                                                \
-        for (int q = 0; q < 12; ++q) dn[q] = grstd * (gw[q] * dn[q] - msa - ah[q] * msb); \
-        p6_pack(dn, vm, po);                                                              \
-        p6_store(r, po);                                                                  \
-        p6_unpack(RA, a2);                                                                \
-        for (int q = 0; q < 12; ++q) silu_dsilu(a2[q], hv[q], dv[q]);                     \
-        p6_pack(hv, vm, ph);                                                              \
-        p6_pack(dv, vm, PD);                                                              \
-        p6_store(Hc + (size_t)(1 + t) * TB_RS + 4 * L.h, ph);                             \
-    }
-        TV_STAGE3B(0, ra0, pn0, pd0)
-        TV_STAGE3B(1, ra1, pn1, pd1)
-        TV_STAGE3B(2, ra2, pn2, pd2)
-        TV_STAGE3B(3, ra3, pn3, pd3)
-#undef TV_STAGE3B
-        TV_LOADA4(sv.a1)  // needed at the end of B2: requested ahead of the conv2 contraction's stores
-    }
-    PHASE(10);
-    lds_barrier();
-    PHASE(11);
-    // conv2 weight gradient: da3 (2,6) x h2
-    {
-        f32x4 acc[5], bsum;
-        tv_contract(Sc, Hc, 2, 6, NS, NSL, th, acc, bsum);
-        tv_flush(prow16 + 1 * TV_CONVW, prow + 1 * TS_FFN, g, th, acc, bsum);
-    }
-    PHASE(12);
-    // B2: conv2^T: da3 (2,6) -> dh2; da2 = dh2 * SiLU'(a2) (parked) -> S (3,5)
-    fetch_cross(2, 6);
-    PHASE(13);
-#pragma unroll 1
-    TB_BLOCKS(false) {
-        FragH b[TB_SB][5];
-        const bool hib = s0 - s_beg >= 2;
-#pragma unroll
-        for (int k = 0; k < TB_SB; ++k)
-            if (s0 + k < s_end) {
-                const int t = 32 * (s0 + k) + L.n;
-                conv_bfrags3(L, rowx(t - 1, 2, 6), rowp(t, 2, 6), rowx(t + 1, 2, 6), b[k]);
-            }
-#pragma unroll
-        for (int k = 0; k < TB_SB; ++k)
-            if (s0 + k < s_end) {
-                const int t = 32 * (s0 + k) + L.n;
-                const uint32_t vm = lane_mask(t < T_);
-                const f32x16 dh2 = conv_mma(wt, b[k]);
-                P6 pdv, po;
-                TV_PICK(pdv, k, hib, pd0, pd1, pd2, pd3)
-                float d2[12], o[12];
-                p6_unpack(pdv, d2);
-#pragma unroll
-                for (int r = 0; r < 12; ++r) o[r] = dh2[r] * d2[r];
-                p6_pack(o, vm, po);
-                p6_store(orow(t, 3, 5), po);
-            }
-    }
-    if (L.lane < 6) *reinterpret_cast<u32x2*>(Sc + (size_t)(th ? NT + 5 : 2) * TB_RS + 4 * L.lane) = (u32x2){0u, 0u};
-    load_wfrags<5>(wt, W.C1T, g, L.lane);
-    // (h1, SiLU'(a1)) from the saved a1: h1 -> H (every wave passed fetch_cross' barrier, i.e. its conv2 contraction), SiLU' parked in pn*
-#define TV_STAGE5(k, RA, PN)                                                              \
-    if (s_beg + (k) < s_end) {                                                            \
-        const int t = 32 * (s_beg + (k)) + L.n;                                           \
-        const uint32_t vm = lane_mask(t < T_);                                            \
-        float a1[12], hv[12], dv[12];                                                     \
-        P6 ph;                                                                            \
-        p6_unpack(RA, a1);                                                                \
-        for (int q = 0; q < 12; ++q) silu_dsilu(a1[q], hv[q], dv[q]);                     \
-        p6_pack(hv, vm, ph);                                                              \
-        p6_pack(dv, vm, PN);                                                              \
-        p6_store(Hc + (size_t)(1 + t) * TB_RS + 4 * L.h, ph);                             \
-    }
-    TV_STAGE5(0, ra0, pn0)
-    TV_STAGE5(1, ra1, pn1)
-    TV_STAGE5(2, ra2, pn2)
-    TV_STAGE5(3, ra3, pn3)
-#undef TV_STAGE5
-    PHASE(14);
-    lds_barrier();
-    PHASE(15);
-    // conv1 weight gradient: da2 (3,5) x h1
-    {
-        f32x4 acc[5], bsum;
-        tv_contract(Sc, Hc, 3, 5, NS, NSL, th, acc, bsum);
-        tv_flush(prow16, prow, g, th, acc, bsum);
-    }
-    PHASE(16);
-    // B1: conv1^T: da2 (3,5) -> dh1; da1 = dh1 * SiLU'(a1) (parked) -> S (4,4) -> operand (whole rows, this wave's own run)
-    fetch_cross(3, 5);
-    PHASE(17);
-#pragma unroll 1
-    TB_BLOCKS(false) {
-        FragH b[TB_SB][5];
-        const bool hib = s0 - s_beg >= 2;
-#pragma unroll
-        for (int k = 0; k < TB_SB; ++k)
-            if (s0 + k < s_end) {
-                const int t = 32 * (s0 + k) + L.n;
-                conv_bfrags3(L, rowx(t - 1, 3, 5), rowp(t, 3, 5), rowx(t + 1, 3, 5), b[k]);
-            }
-#pragma unroll
-        for (int k = 0; k < TB_SB; ++k)
-            if (s0 + k < s_end) {
-                const int t = 32 * (s0 + k) + L.n;
-                const uint32_t vm = lane_mask(t < T_);
-                const f32x16 dh1 = conv_mma(wt, b[k]);
-                P6 pdv, po;
-                TV_PICK(pdv, k, hib, pn0, pn1, pn2, pn3)
-                float d1[12], o[12];
-                p6_unpack(pdv, d1);
-#pragma unroll
-                for (int r = 0; r < 12; ++r) o[r] = dh1[r] * d1[r];
-                p6_pack(o, vm, po);
-                p6_store(orow(t, 4, 4), po);
-            }
-    }
-    wave_lds_sync();
-    rows_gstore<128 * 3>(op_da1 + ((size_t)g * ntok + n0 + run0) * TS_CG, Sc + (size_t)(4 + run0) * TB_RS, nrun, T_ - run0);
-    PHASE(18);
-#undef TB_BLOCKS
-#undef TV_PICK
-#undef TV_LOADA4
-#undef TV_LOADA
-    // GroupNorm affine partial sums of this workgroup's 96 channels -> the sequence's `part` row (written in B3, two barriers ago)
-    for (int i = tid; i < 2 * 96; i += 512) {
-        const int kind = i / 96, ch = i % 96;
-        part[(size_t)row * TV_PSTRIDE + kind * TS_FFN + gh * 96 + ch] = gnp[(0 * 2 + kind) * 96 + ch] + gnp[(1 * 2 + kind) * 96 + ch];
-    }
-    PHASE_END();
-}
-
-// The same backward with HALF the workgroup (round 5): one workgroup = one sequence x TWO conv groups (4 waves = (group, half of the frames)), the images
-// 112-byte rows, 58 KB of LDS — two workgroups share a CU, so one's cold start (the prologue's memory round trip, 10 % of the big kernel's wave time) and
-// barrier waits overlap the other's math.  The strip phase takes two strips per wave; dy is read by four workgroups per sequence (L2).  No room for the
-// dy image beside two resident workgroups: this variant emits the h5 operand and the W2 weight gradient is wgrad.hip's, as in round 4.
+// One workgroup = one sequence x TWO conv groups (round 5; 4 waves = (group, half of the frames)), the images 112-byte rows, 58 KB of LDS — two
+// workgroups share a CU, so one's cold start (the prologue's memory round trip, 10 % of the four-group kernel's wave time) and barrier waits overlap
+// the other's math.  The strip phase takes two strips per wave; dy is read by four workgroups per sequence (L2).  No room for a dy image beside two
+// resident workgroups: the kernel emits the h5 operand and the W2 weight gradient is wgrad.hip's.
 __global__ __launch_bounds__(256, 2) void tconvffn_bwd_q_kernel(nbss_cfg c, LayerPtrs lp, TvW W, TvIn sv, const bf16_t* __restrict__ dy, float* __restrict__ part,
                                                                 bf16_t* __restrict__ part16, bf16_t* __restrict__ op_h5, bf16_t* __restrict__ op_da1, int flip) {
     NBSS_LDS(smem);
@@ -2198,11 +1688,7 @@ __global__ __launch_bounds__(256, 2) void tconvffn_bwd_q_kernel(nbss_cfg c, Laye
     }
     PHASE_END();
 }
-PHASE_READER(nbss_phase_read_tconvffn_bwd_v)
 
-size_t tconvffn_v_part_bytes(const nbss_cfg& c) { return (size_t)c.B * c.F * (TV_PSTRIDE * sizeof(float) + TV_P16 * sizeof(bf16_t)); }
-// fold of the bf16 weight-gradient partial rows into G (fp32); offs = flat-gradient offsets of the three conv weights and of W2; `slices`: TV_RSL x TV_P16 floats of scratch
-// with_w2: the rows carry the dW2 block behind the three conv blocks (tconvffn_bwd_v_kernel) or not (tconvffn_bwd_q_kernel)
 // first stage alone, for other kernels' bf16 partial rows (fconv.hip)
 int part16_slices_launch(const void* part16, int nrows, float* slices, int p16, int* nsl_out, hipStream_t st, bool batch) {
     const int nsl = nrows < TV_RSL ? nrows : TV_RSL;
@@ -2218,8 +1704,10 @@ int part16_slices_launch(const void* part16, int nrows, float* slices, int p16, 
     NBSS_FOLD_LAUNCH(tconv_part_reduce1_kernel, dim3((p16 / 8 + 255) / 256, nsl), dim3(256), 0, st, (const bf16_t*)part16, nrows, slices, p16);
     return NBSS_CHECK_LAUNCH();
 }
-int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, float* G, const long long* offs, bool with_w2, hipStream_t st) {
-    const int nrows = c.B * c.F, nsl = nrows < TV_RSL ? nrows : TV_RSL, p16 = with_w2 ? TV_P16 : TQ_P16;
+// fold of tconvffn_bwd_q_kernel's bf16 weight-gradient partial rows into G (fp32); offs = flat-gradient offsets of the three conv weights; `slices`:
+// TV_RSL x TQ_P16 floats of scratch.  (The rows hold no dW2 block: the final stage's fourth offset is never read.)
+int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, float* G, const long long* offs, hipStream_t st) {
+    const int nrows = c.B * c.F, nsl = nrows < TV_RSL ? nrows : TV_RSL, p16 = TQ_P16;
     if (g_fold) {  // inside a FoldScope (fold.h): the slice sums come from the scope's pool, the two passes join its first and second stage
         int err;
         void* sl = g_fold->alloc((size_t)nsl * p16 * sizeof(float), &err);
@@ -2230,7 +1718,8 @@ int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, fl
             it.kind = FK_P16_SLICES;
             it.gx = (p16 / 8 + 255) / 256; it.gy = nsl; it.nblk = it.gx * it.gy;
             it.u.p16.part16 = part16; it.u.p16.nrows = nrows; it.u.p16.p16 = p16; it.u.p16.nsl = nsl; it.u.p16.slices = (float*)sl; it.u.p16.G = G;
-            for (int k = 0; k < 4; ++k) it.u.p16.off[k] = offs[k];
+            for (int k = 0; k < 3; ++k) it.u.p16.off[k] = offs[k];
+            it.u.p16.off[3] = 0;
             if ((err = g_fold->add(1, it))) return err;
             it.kind = FK_TCONV_FINAL;
             it.gx = (p16 + 255) / 256; it.gy = 1; it.nblk = it.gx;
@@ -2241,27 +1730,7 @@ int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, fl
     NBSS_FOLD_LAUNCH(tconv_part_reduce1_kernel, dim3((p16 / 8 + 255) / 256, nsl), dim3(256), 0, st, (const bf16_t*)part16, nrows, slices, p16);
     int e = NBSS_CHECK_LAUNCH();
     if (e) return e;
-    NBSS_FOLD_LAUNCH(tconv_part_reduce2_kernel, dim3((p16 + 255) / 256), dim3(256), 0, st, (const float*)slices, nsl, G, offs[0], offs[1], offs[2], offs[3], p16);
-    return NBSS_CHECK_LAUNCH();
-}
-size_t tconvffn_v_slices_bytes() { return (size_t)TV_RSL * TV_P16 * sizeof(float); }
-// data-gradient + T-conv weight-gradient kernel from saved pre-activations; `part`: [B*F][TV_PSTRIDE] floats, then [B*F][TV_P16] bf16
-int tconvffn_bwd_v_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* dy, void* tsave, void* op_da1,
-                          hipStream_t st) {
-    bf16_t* part16 = reinterpret_cast<bf16_t*>(part + (size_t)c.B * c.F * TV_PSTRIDE);
-    if (c.dtype != NBSS_BF16 || c.T > 256 || !tsave) return NBSS_EUNSUPPORTED;
-    const size_t NT = (size_t)((c.T + 31) / 32) * 32;
-    const size_t h_el = (NT + 2) * TB_RS > (size_t)24 * 512 ? (NT + 2) * TB_RS : (size_t)24 * 512;
-    const size_t lds = ((NT + TB_PAD) * TB_RS + h_el + NT * TV_DRS) * sizeof(bf16_t) + (16 + 4 * 96) * sizeof(float) + 8 * TS_CG * sizeof(bf16_t) + PHASE_LDS_BYTES;
-    if (lds > 160 * 1024) return NBSS_EUNSUPPORTED;  // (T = 256: 161 968 of 163 840 bytes; the diagnostic build's timer slots fit up to T = 224)
-    const bf16_t* pk = (const bf16_t*)packed;
-    TvW W = {pk + pack_off(c, layer, K_TS_W2_T), pk + pack_off(c, layer, K_TS_C1_T), pk + pack_off(c, layer, K_TS_C2_T), pk + pack_off(c, layer, K_TS_C3_T),
-             pk + pack_off(c, layer, K_TS_C3)};
-    const TsSave s = ts_save_ptrs(c, tsave);
-    TvIn in = {s.a1, s.a2, s.a3, s.gn};
-    int e = NBSS_SET_MAX_LDS(tconvffn_bwd_v_kernel, lds);
-    if (e) return e;
-    NBSS_LAUNCH(tconvffn_bwd_v_kernel, dim3(2 * c.B * c.F), dim3(512), lds, st, c, lp, W, in, (const bf16_t*)dy, part, part16, (bf16_t*)op_da1);
+    NBSS_FOLD_LAUNCH(tconv_part_reduce2_kernel, dim3((p16 + 255) / 256), dim3(256), 0, st, (const float*)slices, nsl, G, offs[0], offs[1], offs[2], 0LL, p16);
     return NBSS_CHECK_LAUNCH();
 }
 int tconvffn_bwd_q_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* dy, void* tsave, void* op_h5, void* op_da1,

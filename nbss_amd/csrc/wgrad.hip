@@ -646,11 +646,7 @@ static int wgrad_launch_t(const WgradArgs& a_in, hipStream_t st) {
         const bool fmode3 = a.taps > 1 && a.shift_dim == 1 && a.shift_stride == a.T && a.Ntok % (a.F * a.T) == 0;
         const bool tmode3 = a.taps > 1 && a.shift_dim == 0 && a.shift_stride == 1 && a.Ntok % a.T == 0;
         // skinny dense problems (squeeze / unsqueeze: 6 tiles, 13 KB per 64 tokens): 128-token chunks halve the barrier rounds per byte
-#ifdef NBSS_WG_KC64
-        const bool skinny = false;
-#else
         const bool skinny = a.taps == 1 && cdiv((all ? a.groups : 1) * mtiles * ntiles, WG_WAVES) <= 2;
-#endif
         const int kc3 = fmode3 ? 96 : skinny ? 128 : 64, h3 = a.taps / 2, rowsB3 = kc3 + 2 * h3 * (fmode3 ? 2 : 1), nfirst3 = (all ? a.groups : 1) * mtiles;
         const size_t img3 = ((size_t)kc3 * tr_ld(ncA) + (size_t)rowsB3 * tr_ld(ncB)) * 2;
         const int nvec3 = (cdiv(kc3 * (ncA / 8), WG_THREADS) + cdiv(rowsB3 * (ncB / 8), WG_THREADS)) * WG_THREADS;  // whole A slots + whole B slots
@@ -692,11 +688,7 @@ static int wgrad_launch_t(const WgradArgs& a_in, hipStream_t st) {
         }
     }
     if (a.a_gw || a.b_gw) return NBSS_EUNSUPPORTED;
-#ifdef NBSS_WG_NOSMALL
-    const bool small = false;
-#else
     const bool small = (all ? a.groups : 1) * mtiles * ntz <= WG_WAVES * 4 && sizeof(T) == 2;
-#endif
     int xbl = (small ? 1024 : 384) / (ybl * nz);  // resident workgroups; every x-block ends with one atomicAdd per output element
     if (xbl < 16) xbl = 16;
     if (xbl > nchunks) xbl = nchunks;
@@ -705,9 +697,6 @@ static int wgrad_launch_t(const WgradArgs& a_in, hipStream_t st) {
     int e;
     WgradArgs ak = a_in;
     const int ntot_k = (all ? a.groups : 1) * tpg;
-#ifdef NBSS_WG_ATOMIC_FLUSH
-    ak.part = nullptr;
-#endif
     if (nz > 1 || (size_t)ybl * xbl * ntot_k * 272 * sizeof(float) > WGPART_BYTES) ak.part = nullptr;  // (column-tile ranges / huge grids: atomic flush)
     bool batched;
     if ((e = fold_part(ak, (size_t)ybl * xbl * ntot_k * 272 * sizeof(float), &batched))) return e;

@@ -1,7 +1,6 @@
 """Dense linear maps of SpatialNet-large at batch 4 (129 516 tokens) through nbss_nb_conv_t (bf16, one tap): microseconds and TFLOP/s per problem.
-NBSS_GEMM_V1=1 selects the previous kernel (gb_tap_gemm_lds_kernel) for comparison.  usage: python tools/gemm_g_bench.py [reps]"""
+usage: python tools/gemm_g_bench.py [reps]"""
 import json
-import os
 import sys
 from pathlib import Path
 
@@ -16,7 +15,7 @@ def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     lib, dev = hip(), torch.device("cuda:0")
     nseq, T = 516, 251
-    out = {"kernel": "v1" if os.environ.get("NBSS_GEMM_V1") == "1" else "tile", "rows": nseq * T}
+    out = {"rows": nseq * T}
     for K, M, act in ((192, 576, 0), (192, 192, 0), (576, 192, 0), (192, 384, 1), (384, 192, 0)):
         x = torch.randn(nseq, T, K, device=dev).to(torch.bfloat16)
         w = torch.randn(M, K, 1, device=dev) / K ** 0.5
