@@ -64,7 +64,8 @@ class TrainModule(nn.Module):
         self.precision = "32"
 
     def _fusable(self) -> bool:
-        return self.norm.mode == "frequency" and self.norm.online and self.loss.mask is None
+        # cc_mse compares STFT coefficients: it needs `out` and `stft` in loss_paras, which only the module sequence supplies
+        return self.norm.mode == "frequency" and self.norm.online and self.loss.mask is None and self.loss.name != "cc_mse"
 
     def _fused_path(self, x: Tensor) -> bool:
         from models.arch.SpatialNet import SpatialNet
@@ -152,8 +153,8 @@ class TrainModule(nn.Module):
     def training_step(self, batch, batch_idx=0):
         x, ys, paras = batch
         yr = ys[:, :, self.ref_channel, :]
-        yr_hat, _ = self.forward(x)
-        loss, perms, _ = self.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True)
+        yr_hat, loss_paras = self.forward(x)
+        loss, perms, _ = self.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True, **loss_paras)  # reference :139-141
         return loss
 
     def configure_optimizers(self):
@@ -307,15 +308,21 @@ def load_checkpoint(path: str, module: "TrainModule", ts=None, plateau: "Optiona
 
 def _fused_step_for(module: "TrainModule", cfg: dict, dev):
     """engine.TrainStep for a TrainModule whose configuration the fused HIP step implements; everything else raises HERE (the fused
-    step hard-wires Norm('frequency', online) + uPIT neg-SI-SDR, so a different YAML must not train a different model silently)"""
+    step hard-wires Norm('frequency', online) + a uPIT time-domain loss — neg_si_sdr, neg_snr or neg_sa_sdr —, so a different YAML must not
+    train a different model silently).  cc_mse is refused by name: it lives in the STFT domain and the fused step hard-wires iSTFT -> time-domain
+    loss; TrainModule.training_step serves it through the module sequence."""
     from nbss_amd._lib import NBSS_BF16, NBSS_F32
     from nbss_amd.engine import TrainStep
     from models.arch.SpatialNet import SpatialNet
     tr = cfg.get("trainer", {})
     if not isinstance(module.arch, SpatialNet):
         raise NotImplementedError(f"the fused MI355X step serves models.arch.SpatialNet.SpatialNet, not {type(module.arch).__name__}")
+    if module.loss.name == "cc_mse":
+        raise NotImplementedError("the fused MI355X step computes its loss on the iSTFT output (neg_si_sdr, neg_snr, neg_sa_sdr); cc_mse compares STFT "
+                                  "coefficients and is served by TrainModule.training_step (module sequence) only")
     if not module._fusable() or not module.loss.pit:
-        raise NotImplementedError("the fused MI355X step implements norm = Norm('frequency', online=True) and loss = Loss(neg_si_sdr, pit=True) "
+        raise NotImplementedError("the fused MI355X step implements norm = Norm('frequency', online=True) and loss = Loss(neg_si_sdr | neg_snr | "
+                                  "neg_sa_sdr, pit=True) "
                                   f"(configs/SpatialNet.yaml); got norm=({module.norm.mode}, online={module.norm.online}), pit={module.loss.pit}")
     eng = module.arch._engine_for(dev)
     eng.dtype = NBSS_BF16 if module.precision in ("bf16-mixed", "bf16") else NBSS_F32
@@ -335,7 +342,7 @@ def _fused_step_for(module: "TrainModule", cfg: dict, dev):
     ts = TrainStep(eng, n_fft=module.stft.n_fft, ref_channel=module.channels.index(module.ref_channel), lr=okw.get("lr", 1e-3),
                    betas=tuple(okw.get("betas", (0.9, 0.999))), eps=okw.get("eps", 1e-8), weight_decay=wd,
                    decoupled_weight_decay=oname == "AdamW", clip=float(tr.get("gradient_clip_val") or 0.0),
-                   window=0 if module.stft.win == "hann_window" else 1)
+                   window=0 if module.stft.win == "hann_window" else 1, loss=module.loss.name, loss_kwargs=module.loss.loss_func_kwargs)
     return eng, ts, gamma
 
 
@@ -463,8 +470,8 @@ def fit(cfg: dict) -> Dict[str, Any]:
             loss = ts.step(x[:, module.channels].to(dev).contiguous(), ys[:, :, module.ref_channel].to(dev).contiguous())
             tot += float(loss)
             n += 1
-        # validation pass of the epoch (forward-only path, every rank the same unsharded split): `val/neg_si_sdr` is what `val_metric: loss`
-        # monitors in the reference (SharedTrainer.py:151-205) and what a ReduceLROnPlateau scheduler steps on
+        # validation pass of the epoch (forward-only path, every rank the same unsharded split; the configured loss: ts carries it):
+        # `val/<loss name>` is what `val_metric: loss` monitors in the reference (SharedTrainer.py:151-205) and what a ReduceLROnPlateau scheduler steps on
         vtot, vn = 0.0, 0
         for x, ys, _ in data.batches(1, 0, 1, 0):
             vl, _, _, _, _ = ts.forward_loss(x[:, module.channels].to(dev).contiguous(), ys[:, :, module.ref_channel].to(dev).contiguous(), need_grad=False)
@@ -476,7 +483,8 @@ def fit(cfg: dict) -> Dict[str, Any]:
         else:
             ts.lr *= gamma
         ts.check_replicas()  # every N steps (here: once per epoch): all ranks must still hold bitwise the same parameters and moments
-        rec = {"epoch": epoch, "train/neg_si_sdr": tot / max(n, 1), "val/neg_si_sdr": val, "lr": ts.lr, "steps": n, "sec": time.time() - t0}
+        rec = {"epoch": epoch, f"train/{module.loss.name}": tot / max(n, 1), f"val/{module.loss.name}": val, "lr": ts.lr, "steps": n,
+               "sec": time.time() - t0}
         log.append(rec)
         if rank == 0:
             print(json.dumps(rec), flush=True)
@@ -534,13 +542,17 @@ def _evaluate_generic(cfg: dict, stage: int) -> Dict[str, Any]:
     with torch.no_grad():
         for x, ys, _ in data.batches(stage, rank, world, 0):
             x, yr = x.to(dev), ys[:, :, module.ref_channel].to(dev).contiguous()
-            yr_hat, _ = module.forward(x)
-            loss, _, _ = module.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True)
-            mix = x[:, module.ref_channel][:, None].expand_as(yr).contiguous()
-            loss_in, _, _ = module.loss(yr_hat=mix, yr=yr, reorder=False, reduce_batch=True)
-            tot, tot_in, n = tot + float(loss), tot_in + float(loss_in), n + 1
+            yr_hat, loss_paras = module.forward(x)
+            loss, _, _ = module.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True, **loss_paras)
+            tot, n = tot + float(loss), n + 1
+            if module.loss.name != "cc_mse":  # the loss of the unprocessed mixture: a time-domain notion
+                mix = x[:, module.ref_channel][:, None].expand_as(yr).contiguous()
+                loss_in, _, _ = module.loss(yr_hat=mix, yr=yr, reorder=False, reduce_batch=True)
+                tot_in += float(loss_in)
     name = "val" if stage == 1 else "test"
-    rec = {f"{name}/neg_si_sdr": tot / max(n, 1), f"{name}/si_sdr_improvement_dB": (tot_in - tot) / max(n, 1), "batches": n, "device": str(dev)}
+    rec = {f"{name}/{module.loss.name}": tot / max(n, 1), "batches": n, "device": str(dev)}
+    if module.loss.name != "cc_mse":
+        rec[f"{name}/{module.loss.name.removeprefix('neg_')}_improvement_dB"] = (tot_in - tot) / max(n, 1)
     if rank == 0:
         print(json.dumps(rec), flush=True)
     return rec
@@ -572,7 +584,7 @@ def _predict_generic(cfg: dict) -> Dict[str, Any]:
 
 
 def evaluate(cfg: dict, stage: int) -> Dict[str, Any]:
-    """`validate` (stage 1) / `test` (stage 2): uPIT neg-SI-SDR of the separated signals and the SI-SDR improvement over the
+    """`validate` (stage 1) / `test` (stage 2): the configured uPIT loss (neg-SI-SDR as shipped) of the separated signals and its improvement over the
     unprocessed reference-channel mixture, through the forward-only path (SharedTrainer.py:151-205 without the PESQ/STOI pools)."""
     if not _is_fused_arch(cfg):
         return _evaluate_generic(cfg, stage)
@@ -585,12 +597,17 @@ def evaluate(cfg: dict, stage: int) -> Dict[str, Any]:
         yr = ys[:, :, module.ref_channel].to(dev).contiguous()
         loss, yr_hat, _, _, _ = ts.forward_loss(xs, yr, need_grad=False)
         mix = xs[:, module.channels.index(module.ref_channel)][:, None].expand_as(yr).contiguous()
-        loss_in, _, _ = ops.pit_neg_sisdr(ts.lib, mix, yr, need_grad=False)
+        if ts.loss == "neg_si_sdr":
+            loss_in, _, _ = ops.pit_neg_sisdr(ts.lib, mix, yr, need_grad=False)
+        else:
+            loss_in, _, _ = ops.pit_loss(ts.lib, ts.loss, mix, yr, pit=True, scale_invariant=bool(ts.loss_kwargs.get("scale_invariant", False)),
+                                         need_grad=False)
         tot += float(loss)
         tot_in += float(loss_in)
         n += 1
     name = "val" if stage == 1 else "test"
-    rec = {f"{name}/neg_si_sdr": tot / max(n, 1), f"{name}/si_sdr_improvement_dB": (tot_in - tot) / max(n, 1), "batches": n}
+    lname = module.loss.name
+    rec = {f"{name}/{lname}": tot / max(n, 1), f"{name}/{lname.removeprefix('neg_')}_improvement_dB": (tot_in - tot) / max(n, 1), "batches": n}
     if rank == 0:
         print(json.dumps(rec), flush=True)
     return rec

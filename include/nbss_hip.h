@@ -175,6 +175,30 @@ int64_t nbss_pit_ws_bytes(int B, int S);
 int nbss_pit_neg_sisdr(int B, int S, int N, const float* preds, const float* target, float* loss, int32_t* perm, float* dpreds, float* ws,
                        void* stream);
 
+/* Loss(loss_func, pit).forward for the reference's other objectives (models/io/loss.py:15-71,95-118; torchmetrics snr,
+ * source_aggregated_signal_distortion_ratio, pit 'permutation-wise'/'min'; zero_mean=False, eps = float32 epsilon):
+ *   NBSS_LOSS_SI_SDR  -mean_s si_sdr(p_s, t_s)                         (neg_si_sdr, as nbss_pit_neg_sisdr)
+ *   NBSS_LOSS_SNR     -mean_s 10 log10((|t_s|^2 + eps) / (|t_s - p_s|^2 + eps))           (neg_snr)
+ *   NBSS_LOSS_SA_SDR  -10 log10((sum_s |t_s|^2 + eps) / (sum_s |t_s - p_s|^2 + eps))     (neg_sa_sdr; with
+ *                     NBSS_LOSS_SCALE_INVARIANT the targets are first scaled by (sum_s <p_s,t_s> + eps) / (sum_s |t_s|^2 + eps))
+ *   NBSS_LOSS_MSE     mean over S*N elements of (p - t)^2                                 (cc_mse / _mse)
+ * flags: NBSS_LOSS_PIT = minimum over the speaker permutations in itertools order (first wins a tie); clear = estimate s
+ * paired with target s.  NBSS_LOSS_SCALE_INVARIANT: SA-SDR only (NBSS_EINVAL with another kind).
+ * preds/target [B,S,N] fp32, N = any flattened trailing size; S <= 4, B <= 1024 (NBSS_EUNSUPPORTED beyond).
+ * loss: 1 float (mean over the batch), perm [B,S] (prediction index paired with target s), dpreds (optional) = d loss / d preds.
+ * The distortion energies |t - p|^2 of SNR, unscaled SA-SDR and MSE are accumulated element-wise, not formed from dot products.
+ * ws: nbss_pit_loss_ws_bytes() bytes of floats = partial sums | per-item loss [B] | pairing coefficients [3 B S]; the caller may
+ * read the per-item losses from that tail after the call (nbss_pit_ws_bytes() has the same tail). */
+#define NBSS_LOSS_SI_SDR 0
+#define NBSS_LOSS_SNR 1
+#define NBSS_LOSS_SA_SDR 2
+#define NBSS_LOSS_MSE 3
+#define NBSS_LOSS_PIT 1
+#define NBSS_LOSS_SCALE_INVARIANT 2
+int64_t nbss_pit_loss_ws_bytes(int kind, int B, int S);
+int nbss_pit_loss(int kind, int flags, int B, int S, int N, const float* preds, const float* target, float* loss, int32_t* perm, float* dpreds,
+                  float* ws, void* stream);
+
 /* clip_grad_norm_(max_norm, L2) + torch.optim.Adam(W) step on the flat fp32 buffers
  * (configs/SpatialNet.yaml:3-4,44; general_steps.py:243-271).  grads are first multiplied by
  * grad_scale (1/world_size after a SUM all-reduce).  scratch: >= 258 floats; scratch[0] returns the

@@ -11,6 +11,9 @@ import os
 from pathlib import Path
 
 NBSS_F32, NBSS_BF16 = 0, 1
+# nbss_pit_loss: kind, flags (include/nbss_hip.h)
+NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR, NBSS_LOSS_SA_SDR, NBSS_LOSS_MSE = 0, 1, 2, 3
+NBSS_LOSS_PIT, NBSS_LOSS_SCALE_INVARIANT = 1, 2
 
 _ERR = {0: "OK", -1: "NBSS_EINVAL (bad argument)", -2: "NBSS_EUNSUPPORTED (no kernel for this shape/config)",
         -3: "NBSS_ELAUNCH (HIP launch failed)", -4: "NBSS_ELDS (cannot raise dynamic LDS limit)"}
@@ -73,6 +76,8 @@ SIGNATURES = {
     "nbss_inorm_istft_bwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nbss_pit_ws_bytes": (C.c_int64, [_I, _I]),
     "nbss_pit_neg_sisdr": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "nbss_pit_loss_ws_bytes": (C.c_int64, [_I, _I, _I]),
+    "nbss_pit_loss": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "nbss_online_encoder_step": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "nbss_online_ret_step": (_I, [_I, _I] + [_P] * 12),
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),

@@ -36,6 +36,9 @@ int inorm_istft_impl(int nfft, int B, int S, int N, const float* tab, const floa
 int inorm_istft_bwd_impl(int nfft, int B, int S, int N, const float* tab, const float* dy, const float* xrmm, float* dout, hipStream_t st);
 size_t pit_ws_floats(int B, int S);
 int pit_sisdr_impl(int B, int S, int N, const float* p, const float* t, float* loss, int* perm, float* dp, float* ws, hipStream_t st);
+size_t pit_loss_ws_floats(int kind, int B, int S);
+int pit_loss_impl(int kind, int flags, int B, int S, int N, const float* p, const float* t, float* loss, int* perm, float* dp, float* ws,
+                  hipStream_t st);
 int clip_adam_dev_impl(size_t n, float* p, float* g, float* m, float* v, float* scal, const float* hyper, float max_norm, float grad_scale, float beta1,
                        float beta2, float eps, float wd, int flags, hipStream_t st);
 int adam_hyper_impl(int step, float lr, float beta1, float beta2, float* out);
@@ -474,6 +477,17 @@ int nbss_pit_neg_sisdr(int B, int S, int N, const float* preds, const float* tar
                        void* stream) {
     if (!preds || !target || !loss || !perm || !ws || N <= 0) return NBSS_EINVAL;
     return pit_sisdr_impl(B, S, N, preds, target, loss, perm, dpreds, ws, (hipStream_t)stream);
+}
+
+int64_t nbss_pit_loss_ws_bytes(int kind, int B, int S) {
+    if (kind < NBSS_LOSS_SI_SDR || kind > NBSS_LOSS_MSE || B <= 0 || S <= 0) return -1;
+    return (int64_t)pit_loss_ws_floats(kind, B, S) * (int64_t)sizeof(float);
+}
+
+int nbss_pit_loss(int kind, int flags, int B, int S, int N, const float* preds, const float* target, float* loss, int32_t* perm, float* dpreds,
+                  float* ws, void* stream) {
+    if (!preds || !target || !loss || !perm || !ws || N <= 0) return NBSS_EINVAL;
+    return pit_loss_impl(kind, flags, B, S, N, preds, target, loss, perm, dpreds, ws, (hipStream_t)stream);
 }
 
 int nbss_clip_adam_step(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* scratch, float max_norm,

@@ -173,8 +173,17 @@ class TrainStep:
 
     def __init__(self, engine: SpatialNetEngine, *, n_fft: int = 256, ref_channel: int = 0, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, clip: float = 5.0, process_group=None, bucketed: bool = True, force_collectives: bool = False,
-                 decoupled_weight_decay: bool = False, window: int = 0, graph: Optional[bool] = None):
+                 decoupled_weight_decay: bool = False, window: int = 0, graph: Optional[bool] = None, loss: str = "neg_si_sdr",
+                 loss_kwargs: Optional[dict] = None):
         self.e = engine
+        # the time-domain objective: the reference's function name (models/io/loss.py), always with PIT.  neg_si_sdr keeps its own entry point
+        # (nbss_pit_neg_sisdr); neg_snr and neg_sa_sdr (loss_kwargs: scale_invariant) go through nbss_pit_loss.  cc_mse lives in the STFT domain
+        # and this step hard-wires iSTFT -> time-domain loss: it is refused.
+        self.loss, self.loss_kwargs = loss, dict(loss_kwargs or {})
+        if loss not in ("neg_si_sdr", "neg_snr", "neg_sa_sdr"):
+            raise NotImplementedError(f"TrainStep: loss {loss!r} is not a time-domain loss of the fused step (neg_si_sdr, neg_snr, neg_sa_sdr)")
+        if set(self.loss_kwargs) - ({"scale_invariant"} if loss == "neg_sa_sdr" else set()):
+            raise TypeError(f"TrainStep: {loss} takes no loss_kwargs {sorted(self.loss_kwargs)}")
         self.lib = engine.lib
         self.n_fft, self.ref = n_fft, ref_channel
         self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip
@@ -240,7 +249,11 @@ class TrainStep:
         xin, xrmm = ops.stft_norm_fwd(lib, self.n_fft, e.dtype, self.tables, x, self.ref)
         out = e.forward(xin, train=need_grad)
         yr_hat = ops.inorm_istft_fwd(lib, self.n_fft, self.tables, out, xrmm, N)
-        loss, perm, dyh = ops.pit_neg_sisdr(lib, yr_hat, yr, need_grad=need_grad)
+        if self.loss == "neg_si_sdr":
+            loss, perm, dyh = ops.pit_neg_sisdr(lib, yr_hat, yr, need_grad=need_grad)
+        else:
+            loss, perm, dyh = ops.pit_loss(lib, self.loss, yr_hat, yr, pit=True, scale_invariant=bool(self.loss_kwargs.get("scale_invariant", False)),
+                                           need_grad=need_grad)
         dout = ops.inorm_istft_bwd(lib, self.n_fft, self.tables, dyh, xrmm) if need_grad else None
         return loss, yr_hat, dout, xin, perm
 
@@ -268,7 +281,8 @@ class TrainStep:
 
     def graph_step(self, x: Tensor, yr: Tensor) -> Tensor:
         e = self.e
-        key = (tuple(x.shape), tuple(yr.shape), e.dtype, self.betas, self.eps, self.wd, self.clip, self.decoupled_wd, self.world, e.params.data_ptr())
+        key = (tuple(x.shape), tuple(yr.shape), e.dtype, self.betas, self.eps, self.wd, self.clip, self.decoupled_wd, self.world, e.params.data_ptr(),
+               self.loss, tuple(sorted(self.loss_kwargs.items())))
         g = self._graphs.get(key)
         if g is None or g["state"] == 0:
             # first call with this key: one eager step (lazy one-time work — workspace allocation, kernel attributes, the library's streams —

@@ -87,7 +87,7 @@ def fit_generic(cfg: dict, build_module, instantiate) -> Dict[str, Any]:
         val = vtot / max(vn, 1)
         if sched is not None:
             sched.step(val) if plateau else sched.step()
-        rec = {"epoch": epoch, "train/neg_si_sdr": tot / max(n, 1), "val/neg_si_sdr": val, "steps": n, "lr": opt.param_groups[0]["lr"],
+        rec = {"epoch": epoch, f"train/{module.loss.name}": tot / max(n, 1), f"val/{module.loss.name}": val, "steps": n, "lr": opt.param_groups[0]["lr"],
                "sec": time.time() - t0, "device": str(dev)}
         log.append(rec)
         if rank == 0:

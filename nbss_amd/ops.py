@@ -12,7 +12,8 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
-from ._lib import NBSS_BF16, NBSS_F32, Cfg, Lib, NbssError
+from ._lib import (NBSS_BF16, NBSS_F32, NBSS_LOSS_MSE, NBSS_LOSS_PIT, NBSS_LOSS_SA_SDR, NBSS_LOSS_SCALE_INVARIANT, NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR, Cfg,
+                   Lib, NbssError)
 from .params import param_table
 
 
@@ -245,6 +246,34 @@ def pit_neg_sisdr(lib, preds, target, need_grad=True, return_items=False):
     dp = torch.empty_like(preds) if need_grad else None
     ws = torch.empty(lib.nbss_pit_ws_bytes(B, S) // 4, dtype=torch.float32, device=dev)
     lib.call("nbss_pit_neg_sisdr", B, S, N, _ptr(lib, preds, torch.float32), _ptr(lib, target, torch.float32), _ptr(lib, loss), _ptr(lib, perm),
+             _ptr(lib, dp), _ptr(lib, ws), _stream(lib, preds))
+    if return_items:  # workspace tail (include/nbss_hip.h): ... | per-item loss [B] | pairing coefficients [3 B S]
+        return loss, perm, dp, ws[ws.numel() - B - 3 * B * S: ws.numel() - 3 * B * S].clone()
+    return loss, perm, dp
+
+
+LOSS_KINDS = {"neg_si_sdr": NBSS_LOSS_SI_SDR, "neg_snr": NBSS_LOSS_SNR, "neg_sa_sdr": NBSS_LOSS_SA_SDR, "cc_mse": NBSS_LOSS_MSE}
+
+
+def pit_loss(lib, kind, preds, target, pit=True, scale_invariant=False, need_grad=True, return_items=False):
+    """the loss family of nbss_pit_loss: kind = NBSS_LOSS_* or the reference's function name (LOSS_KINDS); preds / target [B,S,...] (trailing
+    dimensions are flattened: cc_mse hands in [B,S,F,T,2]); pit=False pairs estimate s with target s in the same single call
+    -> (loss [1], perm [B,S] int32, dpreds (shaped as preds) or None[, per-item losses [B]])"""
+    kind = LOSS_KINDS[kind] if isinstance(kind, str) else int(kind)
+    B, S = preds.shape[:2]
+    if target.shape != preds.shape or preds.dim() < 3:
+        raise NbssError(f"pit_loss: preds {tuple(preds.shape)} and target {tuple(target.shape)} must be the same [B,S,...]")
+    N = preds[0, 0].numel()
+    dev = preds.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    perm = torch.empty(B, S, dtype=torch.int32, device=dev)
+    dp = torch.empty_like(preds) if need_grad else None
+    nws = lib.nbss_pit_loss_ws_bytes(kind, B, S)
+    if nws <= 0:
+        raise NbssError(f"nbss_pit_loss_ws_bytes(kind={kind}, B={B}, S={S}): no such loss kind or empty batch")
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+    flags = (NBSS_LOSS_PIT if pit else 0) | (NBSS_LOSS_SCALE_INVARIANT if scale_invariant else 0)
+    lib.call("nbss_pit_loss", kind, flags, B, S, N, _ptr(lib, preds, torch.float32), _ptr(lib, target, torch.float32), _ptr(lib, loss), _ptr(lib, perm),
              _ptr(lib, dp), _ptr(lib, ws), _stream(lib, preds))
     if return_items:  # workspace tail (include/nbss_hip.h): ... | per-item loss [B] | pairing coefficients [3 B S]
         return loss, perm, dp, ws[ws.numel() - B - 3 * B * S: ws.numel() - 3 * B * S].clone()
