@@ -259,7 +259,8 @@ int nbss_nb_layernorm(int dtype, int64_t rows, int C, const void* x, const float
  * itself; x, y [B][F][T][C]; gamma / beta [C] or NULL */
 int nbss_nb_group_batch_norm(int dtype, int B, int F, int T, int C, const void* x, const float* gamma, const float* beta, float eps, int act_out, void* y,
                              void* stream);
-/* softmax(q k^T / sqrt(dh)) v per (sequence, head): qkv [nseq][T][3H] (q | k | v; head h at columns h dh), o [nseq][T][H]; T <= 256, dh in {24, 48} */
+/* softmax(q k^T / sqrt(dh)) v per (sequence, head): qkv [nseq][T][3H] (q | k | v; head h at columns h dh), o [nseq][T][H]; T <= 256, dh in {24, 48, 96}
+ * (24 / 48: a head's K and V stay in LDS; 96: walked in blocks of 64 keys with a running max / sum per query, csrc/attn_kb.hip); anything else: NBSS_EUNSUPPORTED */
 int nbss_nb_attention_fwd(int dtype, int64_t nseq, int T, int H, int heads, const void* qkv, void* o, void* stream);
 /* the narrow-band conformer NBC (reference models/arch/NBC.py): Transformer-XL relative-position attention (NBC.py:106-143) —
  *   softmax(((q + u) k^T + (q + v) P[i - j]) * scale) v per (sequence, head); pos [2T - 1][H] = pos_proj of the sinusoid table for the offsets
@@ -278,7 +279,8 @@ int nbss_nb_group_norm(int dtype, int64_t nseq, int T, int C, int groups, const 
  *   NULL).  ws: nbss_nb_bwd_ws_bytes(Cout, Cin, groups, taps) bytes (the re-laid transposed weights + partial tiles of the weight gradient).
  * layernorm_bwd: dx = dres + LayerNorm'(dy) with the forward's stats; dgamma / dbeta accumulated.
  * group_batch_norm_bwd: gradient through y = act(GroupBatchNorm(x)) (statistics recomputed from x); dgamma / dbeta accumulated (NULL when not affine).
- * attention_bwd: dqkv [nseq][T][3H] from qkv and d_o = gradient w.r.t. the attention output; ws: nbss_nb_attention_bwd_ws_bytes() bytes. */
+ * attention_bwd: dqkv [nseq][T][3H] from qkv and d_o = gradient w.r.t. the attention output; ws: nbss_nb_attention_bwd_ws_bytes() bytes.  Same limits as
+ *   attention_fwd (T <= 256, dh in {24, 48, 96}); scores are recomputed, no atomics: bitwise repeatable. */
 int64_t nbss_nb_bwd_ws_bytes(int Cout, int Cin, int groups, int taps);
 int nbss_nb_conv_t_train(int dtype, int64_t nseq, int T, int Cin, int ldx, int Cout, int groups, int taps, const void* x, const float* w, const float* bias, void* y,
                          void* y_silu, const void* residual, void* ws, void* stream);

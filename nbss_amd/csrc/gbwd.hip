@@ -2281,9 +2281,13 @@ static int nb_attn_fwd(long nseq, int Tn, int H, int heads, const void* qkv, voi
                 (float*)nullptr, Tn, H, heads);
     return NBSS_CHECK_LAUNCH();
 }
+// head width 96: the key-blocked kernels of attn_kb.hip
+int nb_attention_kb_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st);
+int nb_attention_kb_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* dO, void* O, void* dqkv, float* lse, float* Dv, hipStream_t st);
 int nb_attention_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st) {
     if (heads <= 0 || H % heads) return NBSS_EINVAL;
     const int dh = H / heads;
+    if (dh == 96) return nb_attention_kb_fwd_impl(dtype, nseq, Tn, H, heads, qkv, o, st);
     if (dh == 48) return dtype == NBSS_BF16 ? nb_attn_fwd<bf16_t, 48>(nseq, Tn, H, heads, qkv, o, st) : nb_attn_fwd<float, 48>(nseq, Tn, H, heads, qkv, o, st);
     if (dh == 24) return dtype == NBSS_BF16 ? nb_attn_fwd<bf16_t, 24>(nseq, Tn, H, heads, qkv, o, st) : nb_attn_fwd<float, 24>(nseq, Tn, H, heads, qkv, o, st);
     return NBSS_EUNSUPPORTED;
@@ -2499,6 +2503,7 @@ int nb_attention_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const 
     float* lse = (float*)((char*)ws + ws_align((size_t)N * H * (dtype == NBSS_BF16 ? 2 : 4)));
     float* Dv = (float*)((char*)lse + ws_align((size_t)N * heads * sizeof(float)));
     const int dh = H / heads;
+    if (dh == 96) return nb_attention_kb_bwd_impl(dtype, nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st);
     if (dh == 48) return dtype == NBSS_BF16 ? gb_attn_launch<bf16_t, 48>(c, qkv, dO, O, dqkv, lse, Dv, st) : gb_attn_launch<float, 48>(c, qkv, dO, O, dqkv, lse, Dv, st);
     if (dh == 24) return dtype == NBSS_BF16 ? gb_attn_launch<bf16_t, 24>(c, qkv, dO, O, dqkv, lse, Dv, st) : gb_attn_launch<float, 24>(c, qkv, dO, O, dqkv, lse, Dv, st);
     return NBSS_EUNSUPPORTED;

@@ -9,7 +9,7 @@ the SiLU' factor in their epilogue, the token-contraction weight gradients of cs
 every parameter gradient comes from these kernels, torch contributes buffers and two residual adds per block.
 
 `supported(net)` names what the kernels are built for: norms (LN, GBN, GBN) with per-frame GroupBatchNorm statistics, no dropout, head
-width 24 or 48, channel counts that are multiples of 8 per conv group, sequences of at most 256 frames."""
+width 24, 48 or 96 (96 = NBC2-large, dim_hidden 192 with 2 heads: the key-blocked attention of csrc/attn_kb.hip), channel counts that are multiples of 8 per conv group, sequences of at most 256 frames."""
 from __future__ import annotations
 
 import ctypes as C
@@ -40,8 +40,8 @@ def supported(net) -> Optional[str]:
             return "GroupBatchNorm statistics must be per frame (share_along_sequence_dim = False)"
         if b.dropout1.p or b.dropout2.p or b.conv[8].p:
             return "dropout must be 0"
-        if H // b.self_attn.num_heads not in (24, 48) or not b.self_attn._qkv_same_embed_dim or b.self_attn.in_proj_bias is None:
-            return "attention head width must be 24 or 48 (packed in_proj with bias)"
+        if H // b.self_attn.num_heads not in (24, 48, 96) or not b.self_attn._qkv_same_embed_dim or b.self_attn.in_proj_bias is None:
+            return "attention head width must be 24, 48 or 96 (packed in_proj with bias)"
         g = b.conv[1].groups
         if (FFN // g) % 8 or FFN % g or b.conv[1].kernel_size[0] % 2 == 0:
             return "conv groups must be multiples of 8 channels wide, odd kernel"
