@@ -20,8 +20,26 @@
 #define BL_THREADS 512
 #define BL_WAVES 8
 
+// The gate arithmetic below is written as the exact sequence of roundings it means: every fused multiply-add is an explicit fmaf, and the compiler may neither
+// fuse nor reassociate the rest.  Left to the library's fast-math flags, the choice of which a * b + c to fuse differed between the NTN instantiations of the
+// same kernel (seen in the ISA of bwd<float, 128, 1> against <float, 128, 2>, and as differing bits on the device), against "results do not depend on the grid".
+#pragma clang fp contract(off) reassociate(off)
+
 NBSS_DEV float bl_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
-NBSS_DEV float bl_tanh(float x) { return 2.0f / (1.0f + __expf(-2.0f * x)) - 1.0f; }
+// tanh to a few ulp RELATIVE over the whole range (g and c of a quiet input are small: 2 / (1 + e^-2x) - 1 is one ulp of 1 off, i.e. 1e-4 relative at 1e-3):
+// below 0.75 the odd polynomial x (1 + z Q(z)), z = x^2 (Q: degree-4 minimax fit of (tanh(x) / x - 1) / z, 3e-8 relative), above it (1 - e) / (1 + e) with
+// e = e^-2|x| <= 0.23 (no cancellation; e -> 0 saturates to exactly +-1 without an overflow)
+NBSS_DEV float bl_tanh(float x) {
+    const float z = x * x;
+    float q = -0.0047694854f;
+    q = fmaf(q, z, 0.019664908f);
+    q = fmaf(q, z, -0.053390257f);
+    q = fmaf(q, z, 0.13326521f);
+    q = fmaf(q, z, -0.33333069f);
+    const float e = __expf(-2.0f * fabsf(x));
+    const float r = copysignf((1.0f - e) / (1.0f + e), x);  // (both sides evaluated, then ONE select: written as a branch, fwd<bf16, 256, 4> spills 76 bytes / lane)
+    return z < 0.5625f ? fmaf(x, z * q, x) : r;
+}
 
 // A-operand fragments of a row-major matrix W [M][K] (tiles of 16 rows, k-steps of 32): out[(tile * KS + ks) * 64 + lane][8] = W[16 tile + l15][32 ks + 8 g4 + j];
 // TRANSPOSE: the fragments of W^T (W is [K][M]: out = W[32 ks + 8 g4 + j][16 tile + l15])
@@ -114,7 +132,7 @@ __global__ __launch_bounds__(BL_THREADS) void blstm_fwd_kernel(BlArgs a) {
                     fv[r] = bl_sigmoid(acc[u][1][nt][r]);
                     gv[r] = bl_tanh(acc[u][2][nt][r]);
                     ov[r] = bl_sigmoid(acc[u][3][nt][r]);
-                    c[u][nt][r] = fv[r] * c[u][nt][r] + iv[r] * gv[r];
+                    c[u][nt][r] = fmaf(fv[r], c[u][nt][r], iv[r] * gv[r]);
                     hv[r] = ov[r] * bl_tanh(c[u][nt][r]);
                 }
                 store4(hnext + (size_t)(16 * nt + l15) * HLD + unit, hv[0], hv[1], hv[2], hv[3]);
@@ -184,10 +202,10 @@ __global__ __launch_bounds__(BL_THREADS) void blstm_bwd_kernel(BlBwdArgs a) {
                     for (int r = 0; r < 4; ++r) {
                         const float dh = dyv[r] + dhr[u][nt][r];
                         const float th = bl_tanh(cv[r]);
-                        const float dct = dh * ov[r] * (1.0f - th * th) + dc[u][nt][r];
+                        const float dct = fmaf(dh * ov[r], fmaf(-th, th, 1.0f), dc[u][nt][r]);
                         dov[r] = dh * th * ov[r] * (1.0f - ov[r]);
                         di[r] = dct * gv[r] * iv[r] * (1.0f - iv[r]);
-                        dgg[r] = dct * iv[r] * (1.0f - gv[r] * gv[r]);
+                        dgg[r] = dct * iv[r] * fmaf(-gv[r], gv[r], 1.0f);
                         df[r] = dct * cp[r] * fv[r] * (1.0f - fv[r]);
                         dc[u][nt][r] = dct * fv[r];
                     }
@@ -249,7 +267,12 @@ static int bl_bwd_go(const BlBwdArgs& a, hipStream_t st) {
     return NBSS_CHECK_LAUNCH();
 }
 // sequences per workgroup: as few as keep the grid within one round of the chip (the recurrence is latency-bound: T dependent steps), at most 64
+// NBSS_BLSTM_NTN=1|2|4 forces a width (test knob, clamped to cap; read at every call: two launches per layer and step)
 static int bl_ntn(long n, int cap) {
+    if (const char* e = getenv("NBSS_BLSTM_NTN")) {
+        const int forced = atoi(e);
+        if (forced == 1 || forced == 2 || forced == 4) return forced < cap ? forced : cap;
+    }
     int ntn = 1;
     while (ntn < cap && 2 * cdiv(n, 16 * ntn) > 256) ntn *= 2;
     return ntn;

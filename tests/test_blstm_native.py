@@ -48,6 +48,43 @@ def test_native_blstm_forward_and_gradients(backend, dtype):
     assert not bad, bad
 
 
+@pytest.mark.parametrize("shape", [(1, 3, 6), (1, 17, 1), (2, 9, 2)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("hidden", [(256, 128), (128, 256), (256, 256)], ids=lambda h: f"h{h[0]}_{h[1]}")
+@pytest.mark.parametrize("dtype", [pytest.param(NBSS_F32, id="f32"), pytest.param(NBSS_BF16, id="bf16")])
+def test_native_blstm_sizes_and_short_sequences(backend, dtype, hidden, shape):
+    """every pairing of the two recurrence widths, at the same small shapes on both backends: a single frame (T = 1: no recurrent step at all, and the empty
+    y[:, :-1] shift that feeds dW_hh in nbss_amd/blstm.py — that gradient is exactly zero), two frames, and more than one 16-sequence tile; bars as above"""
+    from nbss_amd.blstm import NativeBLSTM, supported
+    B, F, T = shape
+    net = _net(hidden)
+    assert supported(net) is None
+    g = torch.Generator().manual_seed(3)
+    td = torch.bfloat16 if dtype == NBSS_BF16 else torch.float32
+    x = torch.randn(B, F, T, 4, generator=g).to(td)
+    r = torch.randn(B, F, T, 4, generator=g)
+    ref = copy.deepcopy(net).double()
+    want = ref(x.double())
+    (want * r.double()).sum().backward()
+    net = net.to(backend.device)
+    run = NativeBLSTM(net, backend.lib)
+    y0 = run.forward(x.to(backend.device))
+    tol = 2e-5 if dtype == NBSS_F32 else 3e-2
+    assert y0.shape == want.shape and rel_l2(y0, want.detach()) < tol
+    y = run.forward_train(x.to(backend.device))
+    assert torch.equal(y.detach(), y0)
+    (y.float() * r.to(backend.device)).sum().backward()
+    gtol = 1e-4 if dtype == NBSS_F32 else 6e-2
+    bad = {}
+    for (n, p), (_, q) in zip(net.named_parameters(), ref.named_parameters()):
+        assert p.grad is not None and torch.isfinite(p.grad).all(), n
+        if T == 1 and "weight_hh" in n:
+            assert not q.grad.any() and not p.grad.any(), n
+        e = rel_l2(p.grad, q.grad)
+        if e > gtol:
+            bad[n] = e
+    assert not bad, bad
+
+
 def test_supported_names_the_reason():
     from nbss_amd.blstm import supported
     assert "hidden size" in supported(_net(hidden=(8, 6)))
