@@ -150,6 +150,15 @@ class TrainModule(nn.Module):
                  "native": type(s).__name__ == "NativeOnlineStreamer"}
         return self.stft.istft(Yr_hat, length), stats
 
+    def open_stream(self, batch: int, chunk: int, device=None, use_graph: Optional[bool] = None, native: Optional[bool] = None):
+        """a waveform-to-waveform stream of this module's OnlineSpatialNet (nbss_amd/online_io.py): push(x_chunk [B,C,chunk*hop]) ->
+        y [B,Spk,chunk*hop] one hop late, finish(), reset(), separate(x), latency_samples.  On a HIP device the native streamer (STFT step,
+        network step and iSTFT step in one HIP graph per chunk) when it serves the configuration, else the torch one (WaveStreamer);
+        native=True raises the native streamer's reason instead of falling back, native=False takes the torch one."""
+        from nbss_amd.online_io import open_wave_stream
+        dev = torch.device(device) if device is not None else next(self.arch.parameters()).device
+        return open_wave_stream(self.arch, batch, chunk, self.stft, self.norm, self.channels, self.ref_channel, device=dev, use_graph=use_graph, native=native)
+
     def training_step(self, batch, batch_idx=0):
         x, ys, paras = batch
         yr = ys[:, :, self.ref_channel, :]
@@ -561,16 +570,29 @@ def _evaluate_generic(cfg: dict, stage: int) -> Dict[str, Any]:
 def _predict_generic(cfg: dict) -> Dict[str, Any]:
     """`predict` for the torch.nn archs.  OnlineSpatialNet with a fixed-size state ('mhsa(N)', 'ret(..)' without rotary positions) is
     evaluated the way it is deployed: causal, `stream_chunk` frames at a time (CLI: --stream_chunk N, default 8) through
-    OnlineStreamer, whose step is captured once into a HIP graph on a HIP device and replayed (BASELINE config 5)."""
+    OnlineStreamer, whose step is captured once into a HIP graph on a HIP device and replayed (BASELINE config 5).  `--stream_wave true`
+    streams the SAMPLES instead (TrainModule.open_stream(...).separate: STFT and iSTFT per chunk too, one graph replay per chunk on a HIP
+    device) and reports {"chunks", "graph_replays", "native", "latency_samples"}."""
     from models.arch.OnlineSpatialNet import OnlineSpatialNet
     dev, module, data = _setup_generic(cfg)
     out_dir = cfg.get("trainer", {}).get("default_root_dir")
     chunk = int(cfg.get("stream_chunk", 8))
+    wave, stream, stream_key = bool(cfg.get("stream_wave", False)), None, None  # --stream_wave true: waveform-to-waveform streaming (opt-in)
     outs, info = [], {"device": str(dev), "streamed": False, "graph_replays": 0}
     with torch.no_grad():
         for bi, (x, ys, paras) in enumerate(data.batches(2, 0, 1, 0)):
             x = x.to(dev)
-            if isinstance(module.arch, OnlineSpatialNet) and chunk > 0:
+            if isinstance(module.arch, OnlineSpatialNet) and chunk > 0 and wave:
+                # samples in, samples out (TrainModule.open_stream): the signal is filled up with zeros to whole hops, as a live feed would end
+                key = (x.shape[0], str(x.device))
+                if stream is None or stream_key != key:
+                    stream, stream_key = module.open_stream(x.shape[0], chunk, device=x.device), key
+                n = -(-x.shape[-1] // module.stft.n_hop) * module.stft.n_hop
+                yr_hat = stream.separate(torch.nn.functional.pad(x, (0, n - x.shape[-1])))[..., :x.shape[-1]]
+                info["streamed"], info["chunks"] = True, info.get("chunks", 0) + stream.chunks
+                info["graph_replays"] += stream.chunks if stream.graph is not None else 0
+                info["native"], info["latency_samples"] = type(stream).__name__ == "NativeWaveStreamer", stream.latency_samples
+            elif isinstance(module.arch, OnlineSpatialNet) and chunk > 0:
                 yr_hat, st = module.forward_streaming(x, chunk)
                 info["streamed"], info["graph_replays"] = True, info["graph_replays"] + st["graph_replays"]
                 info["frames_per_s"], info["native"] = st["frames_per_s"], st["native"]

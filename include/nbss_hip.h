@@ -242,6 +242,26 @@ int nbss_online_tconvffn_step(int B, int F, int C, const float* ln_w, const floa
                               const float* c1b, const float* c2w, const float* c2b, const float* gn_w, const float* gn_b, const float* c3w, const float* c3b,
                               const float* w2_t, const float* b2, float* s1, float* s2, float* s3, float* a3, float* gn_sums, float* x, void* stream);
 
+/* ---- OnlineSpatialNet: the waveform ends of a streaming step (csrc/online_io.hip; nbss_amd/online_io.py: NativeWaveStreamer) ----------------
+ * n_fft in {256, 512}, hop = n_fft/2, win_len = n_fft, `tables` of nbss_stft_tables; 2 <= C <= 32 frames per call (NBSS_EUNSUPPORTED outside).
+ * Frame t of the stream is frame t of torch.stft(center=True): samples [(t-1) hop, (t+1) hop).  Neither call knows a first or a last chunk:
+ * the caller puts the left reflect padding into `tail` before the first chunk and pushes the right one after the last sample.
+ * norm: the online normalisation by the reference microphone (models/io/norm.py): NONE; FREQUENCY: xrmm [B,F,C] = |X_ref| + 1e-6;
+ * UTTERANCE: xrmm [B,1,C] = mean over F of |X_ref| + 1e-6 (folded in a fixed order: bitwise repeatable, the same for every chunk size).
+ * stft step: x_chunk [B,M,C hop], tail [B,M,hop] (the hop samples before the chunk; updated in place to the chunk's last hop)
+ * -> feats [B,F,C,2M] (normalised; the layout the network step reads) and xrmm (may be NULL with NONE).  ws: B F C floats of scratch,
+ * UTTERANCE only (else may be NULL). */
+#define NBSS_ONLINE_NORM_NONE 0
+#define NBSS_ONLINE_NORM_FREQUENCY 1
+#define NBSS_ONLINE_NORM_UTTERANCE 2
+int nbss_online_stft_step(int n_fft, int norm, int B, int M, int C, int ref_channel, const float* tables, const float* x_chunk, float* tail,
+                          float* feats, float* xrmm, float* ws, void* stream);
+/* istft step: out [B,F,C,2S] * xrmm -> irfft, window, overlap-add, / window envelope -> y_chunk [B,S,C hop]: the sample stream DELAYED BY ONE
+ * HOP (call k returns the samples [k C hop - hop, (k+1) C hop - hop)).  ola [B,S,hop]: the windowed second half of the frame before the chunk
+ * (zero at the start of a stream), updated in place.  One lane writes each sample: no atomics, y_chunk needs no clearing. */
+int nbss_online_istft_step(int n_fft, int norm, int B, int S, int C, const float* tables, const float* out, const float* xrmm, float* ola,
+                           float* y_chunk, void* stream);
+
 /* ---- narrow-band building blocks (models/arch/NBC2.py:152-238 in the reference: pre-norm self-attention over time + convolutional feed-forward with
  * GroupBatchNorm, per (batch, frequency) sequence) -------------------------------------------------------------------------------------------------
  * Geometry-generic kernels (csrc/gbwd.hip), one operation per call on caller-owned tensors of `dtype` (NBSS_F32 | NBSS_BF16) in the [nseq][T][C] layout

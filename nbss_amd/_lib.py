@@ -14,6 +14,8 @@ NBSS_F32, NBSS_BF16 = 0, 1
 # nbss_pit_loss: kind, flags (include/nbss_hip.h)
 NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR, NBSS_LOSS_SA_SDR, NBSS_LOSS_MSE = 0, 1, 2, 3
 NBSS_LOSS_PIT, NBSS_LOSS_SCALE_INVARIANT = 1, 2
+# nbss_online_stft_step / nbss_online_istft_step: norm
+NBSS_ONLINE_NORM_NONE, NBSS_ONLINE_NORM_FREQUENCY, NBSS_ONLINE_NORM_UTTERANCE = 0, 1, 2
 
 _ERR = {0: "OK", -1: "NBSS_EINVAL (bad argument)", -2: "NBSS_EUNSUPPORTED (no kernel for this shape/config)",
         -3: "NBSS_ELAUNCH (HIP launch failed)", -4: "NBSS_ELDS (cannot raise dynamic LDS limit)"}
@@ -83,6 +85,8 @@ SIGNATURES = {
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),
     "nbss_online_advance": (_I, [_P, _I, _P]),
     "nbss_online_tconvffn_step": (_I, [_I, _I, _I] + [_P] * 21),
+    "nbss_online_stft_step": (_I, [_I] * 6 + [_P] * 7),
+    "nbss_online_istft_step": (_I, [_I] * 5 + [_P] * 6),
     "nbss_nb_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),
     "nbss_nb_conv_t": (_I, [_I, C.c_int64, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "nbss_nb_layernorm": (_I, [_I, C.c_int64, _I, _P, _P, _P, _P, _P, _P]),
