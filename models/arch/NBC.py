@@ -6,7 +6,6 @@ the relative offset (the reference materialises a [T, T, heads, d] tensor).  Pla
 device inference AND training take the native path of nbss_amd/nbc.py (see NBC.forward)."""
 import math
 import os
-import warnings
 import weakref
 from typing import Callable, Optional, Tuple
 
@@ -15,10 +14,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch import Tensor
 
+from models.arch.base.native import NATIVE as _NATIVE  # NBC module -> (nbss_amd.nbc.NativeNBC or None, reason it is None)
+from models.arch.base.native import native_runner, torch_path_note
 
 _TRAIN_OK = weakref.WeakKeyDictionary()  # NBC module -> ((n parameters, n modules), nbss_amd.nbc.train_supported's answer)
-_NATIVE = weakref.WeakKeyDictionary()  # NBC module -> (nbss_amd.nbc.NativeNBC or None, reason it is None)
-_NOTED = weakref.WeakKeyDictionary()   # NBC module -> reasons already reported
 
 
 class _GroupNorm(nn.GroupNorm):
@@ -149,18 +148,7 @@ class NBC(nn.Module):
 
     def _native(self):
         """nbss_amd.nbc.NativeNBC of this module when the HIP library is there and the configuration is one its kernels take, else None (the reason is kept)"""
-        if self not in _NATIVE:
-            runner, why = None, None
-            try:
-                from nbss_amd._lib import hip
-                from nbss_amd.nbc import NativeNBC, supported
-                why = supported(self)
-                if why is None:
-                    runner = NativeNBC(self, hip())
-            except Exception as e:  # (no library / no HIP runtime: torch.nn below)
-                runner, why = None, f"{type(e).__name__}: {e}"
-            _NATIVE[self] = (runner, why)
-        return _NATIVE[self][0]
+        return native_runner(self, "nbss_amd.nbc", "NativeNBC")[0]
 
     def _train_supported(self) -> Optional[str]:
         """nbss_amd.nbc.train_supported(self), evaluated once per module structure (it walks every block and builds an id-set of all parameters: host
@@ -172,13 +160,6 @@ class NBC(nn.Module):
             hit = (key, train_supported(self))
             _TRAIN_OK[self] = hit
         return hit[1]
-
-    def _torch_path_note(self, why: str) -> None:
-        """one warning per module and reason: a user on a HIP device can tell which path ran"""
-        seen = _NOTED.setdefault(self, set())
-        if why not in seen:
-            seen.add(why)
-            warnings.warn(f"NBC: torch.nn path instead of the native HIP kernels ({why})", RuntimeWarning, stacklevel=3)
 
     def forward(self, x: Tensor) -> Tensor:
         B, Fq, T, _ = x.shape
@@ -213,7 +194,7 @@ class NBC(nn.Module):
                             return self._native().forward_train(x.contiguous())
                 except NbssError as e:  # (a shape the kernels refuse, e.g. fp32 with head width 48 beyond ~200 frames: LDS)
                     why = str(e)
-            self._torch_path_note(why)
+            torch_path_note(self, "NBC", why)
         h = self.encoder(x.reshape(B * Fq, T, -1).transpose(1, 2)).transpose(1, 2)
         for block in self.sa_layers:
             h, _ = block(h)

@@ -5,6 +5,7 @@ convolutional feed-forward (1x1 -> 3 grouped k=3 convs along T with a norm in th
 normalises with statistics shared by the `group_size` (= num_freqs) sequences of one utterance, in training AND evaluation.
 torch.nn modules for training and on the CPU; inference on a HIP device runs the native forward of
 nbss_amd/nbc2.py (MFMA tap-GEMMs, attention, GroupBatchNorm and LayerNorm kernels behind the `nbss_nb_*` entry points of the C ABI)."""
+import os
 from typing import Any, Dict, Optional, Tuple
 
 import torch
@@ -12,13 +13,8 @@ import torch.nn as nn
 from torch import Tensor
 from torch.nn import MultiheadAttention
 
-
-import os
-import warnings
-import weakref
-
-_NATIVE = weakref.WeakKeyDictionary()  # NBC2 module -> (nbss_amd.nbc2.NativeNBC2 or None, reason it is None)
-_NOTED = weakref.WeakKeyDictionary()   # NBC2 module -> reasons already reported
+from models.arch.base.native import NATIVE as _NATIVE  # NBC2 module -> (nbss_amd.nbc2.NativeNBC2 or None, reason it is None)
+from models.arch.base.native import native_runner, torch_path_note
 
 
 class LayerNorm(nn.LayerNorm):
@@ -145,28 +141,8 @@ class NBC2(nn.Module):
         self.decoder = nn.Linear(dim_hidden, dim_output)
 
     def _native(self):
-        """the HIP path (nbss_amd/nbc2.py) when this configuration is one its kernels are built for, else None.  The handle lives in a module-level
-        WeakKeyDictionary (a ctypes library handle as a module attribute would break deepcopy / pickle of the module); a library that cannot be
-        loaded means the torch.nn path, not an exception — the reason is kept and reported once by forward()."""
-        if self not in _NATIVE:
-            runner, why = None, None
-            try:
-                from nbss_amd._lib import hip
-                from nbss_amd.nbc2 import NativeNBC2, supported
-                why = supported(self)
-                if why is None:
-                    runner = NativeNBC2(self, hip())
-            except Exception as e:  # (no library / no HIP runtime: torch.nn below)
-                runner, why = None, f"{type(e).__name__}: {e}"
-            _NATIVE[self] = (runner, why)
-        return _NATIVE[self][0]
-
-    def _torch_path_note(self, why: str) -> None:
-        """one warning per module and reason: a user on a HIP device can tell which path ran"""
-        seen = _NOTED.setdefault(self, set())
-        if why not in seen:
-            seen.add(why)
-            warnings.warn(f"NBC2: torch.nn path instead of the native HIP kernels ({why})", RuntimeWarning, stacklevel=3)
+        """the HIP path (nbss_amd/nbc2.py) when this configuration is one its kernels are built for, else None (the reason is kept: models/arch/base/native.py)"""
+        return native_runner(self, "nbss_amd.nbc2", "NativeNBC2")[0]
 
     def _native_or_reason(self, x: Tensor):
         """(runner, None) when the native path takes this call, else (None, reason); reason None on the CPU (nothing to report)"""
@@ -203,7 +179,7 @@ class NBC2(nn.Module):
             if why is None:
                 return nat.forward_train(x.contiguous())
         if why is not None:
-            self._torch_path_note(why)
+            torch_path_note(self, "NBC2", why)
         h = self.encoder(x.reshape(B * F, T, -1).transpose(1, 2)).transpose(1, 2)
         for block in self.sa_layers:
             h, _ = block(h)

@@ -4,16 +4,14 @@
 config 1 is a CPU plumbing run); on a HIP device the native path of nbss_amd/blstm.py — one persistent launch per layer for the recurrences of both
 directions, dense maps and contractions around it — for inference and training (hidden sizes 128 / 256: the shipped configuration)."""
 import os
-import warnings
-import weakref
 from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-_NATIVE = weakref.WeakKeyDictionary()  # module -> (nbss_amd.blstm.NativeBLSTM or None, reason it is None)
-_NOTED = weakref.WeakKeyDictionary()   # module -> reasons already reported
+from models.arch.base.native import NATIVE as _NATIVE  # module -> (nbss_amd.blstm.NativeBLSTM or None, reason it is None)
+from models.arch.base.native import native_runner, torch_path_note
 
 
 class BLSTM2_FC1(nn.Module):
@@ -31,18 +29,7 @@ class BLSTM2_FC1(nn.Module):
         self.activation_func = getattr(nn, activation)() if activation else None
 
     def _native(self):
-        if self not in _NATIVE:
-            runner, why = None, None
-            try:
-                from nbss_amd._lib import hip
-                from nbss_amd.blstm import NativeBLSTM, supported
-                why = supported(self)
-                if why is None:
-                    runner = NativeBLSTM(self, hip())
-            except Exception as e:  # (no library / no HIP runtime: torch.nn below)
-                runner, why = None, f"{type(e).__name__}: {e}"
-            _NATIVE[self] = (runner, why)
-        return _NATIVE[self][0]
+        return native_runner(self, "nbss_amd.blstm", "NativeBLSTM")[0]
 
     def forward(self, x: Tensor) -> Tensor:
         B, F, T, _ = x.shape
@@ -60,10 +47,7 @@ class BLSTM2_FC1(nn.Module):
                 why = "the input requires a gradient (the native backward produces parameter gradients only)"
             if why is None:
                 return self._native().forward_train(x.contiguous()) if torch.is_grad_enabled() else self._native().forward(x.contiguous())
-            seen = _NOTED.setdefault(self, set())
-            if why not in seen:
-                seen.add(why)
-                warnings.warn(f"NB-BLSTM: torch.nn path instead of the native HIP kernels ({why})", RuntimeWarning, stacklevel=2)
+            torch_path_note(self, "NB-BLSTM", why)
         h = x.reshape(B * F, T, -1)  # every frequency is an independent sequence
         for rnn, drop in ((self.blstm1, "dropout1"), (self.blstm2, "dropout2")):
             h, _ = rnn(h)
