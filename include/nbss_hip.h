@@ -264,7 +264,7 @@ int nbss_online_istft_step(int n_fft, int norm, int B, int S, int C, const float
 
 /* ---- narrow-band building blocks (models/arch/NBC2.py:152-238 in the reference: pre-norm self-attention over time + convolutional feed-forward with
  * GroupBatchNorm, per (batch, frequency) sequence) -------------------------------------------------------------------------------------------------
- * Geometry-generic kernels (csrc/gbwd.hip), one operation per call on caller-owned tensors of `dtype` (NBSS_F32 | NBSS_BF16) in the [nseq][T][C] layout
+ * Geometry-generic kernels (csrc/nb_blocks.hip over gb_gemm.hip, gb_rows.hip, gb_attn.hip, attn_relpos.hip, attn_kb.hip), one operation per call on caller-owned tensors of `dtype` (NBSS_F32 | NBSS_BF16) in the [nseq][T][C] layout
  * of the reference's [B*F, T, C] activations; weights / biases / affines are the fp32 parameters in their state_dict layout.  nbss_amd/nbc2.py sequences an
  * NBC2 forward from them.  act_in / act_out: 1 = SiLU applied to the input as it is read / to the result.
  * conv_t: y[n][t][o] = sum_tap sum_i x[n][t + tap - taps/2][i] w[o][i][tap] + bias[o] (+ residual[n][t][o]), grouped, zero padded ("same"); taps = 1 is a

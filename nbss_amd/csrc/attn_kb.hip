@@ -1,6 +1,6 @@
 // Key-blocked scaled-dot-product attention for wide heads (head width 96: NBC2-large, dim_hidden 192 / 2 heads), forward and backward.
 //
-// gbwd.hip's gb_attn_q_kernel / gb_attn_k_kernel keep a whole head's K and V (or Q and dO) in LDS and a whole score row in registers: at head width
+// gb_attn.hip's gb_attn_q_kernel / gb_attn_k_kernel keep a whole head's K and V (or Q and dO) in LDS and a whole score row in registers: at head width
 // 96 and T = 251 that is 2 x 256 x 96 x 4 B = 196 KB in fp32, more than a CU has.  Here the OTHER axis is walked in blocks of KB_BLK = 64 rows:
 //
 //   kb_attn_q_kernel   one workgroup per (sequence, head, 64 queries); each of the 4 waves owns one 16-query tile (queries = the MFMA N dimension) and
@@ -24,6 +24,7 @@
 #include "launch.h"
 #include "layout.h"
 #include "blocks.h"
+#include "nb.h"
 
 #define KB_THREADS 256
 #define KB_BLK 64  // rows per LDS block = rows per workgroup (4 waves x one 16-row tile)
@@ -328,7 +329,7 @@ static int kb_attn_bwd(long nseq, int Tn, int H, int heads, const void* qkv, con
     return NBSS_CHECK_LAUNCH();
 }
 
-// head width 96 (gbwd.hip dispatches here: nb_attention_fwd_impl / nb_attention_bwd_impl); same tensors and workspace pieces as the narrow kernels
+// head width 96 (nb_blocks.hip dispatches here: nb_attention_fwd_impl / nb_attention_bwd_impl); same tensors and workspace pieces as the narrow kernels
 int nb_attention_kb_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st) {
     if (heads <= 0 || H != heads * 96 || Tn > KB_TMAX || heads > 65535) return NBSS_EUNSUPPORTED;
     return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 96>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 96>(nseq, Tn, H, heads, qkv, o, st);

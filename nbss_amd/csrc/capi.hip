@@ -3,6 +3,7 @@
 #include "launch.h"
 #include "layout.h"
 #include "side.h"
+#include "nb.h"
 #include <stdlib.h>
 
 int pack_params_impl(const nbss_cfg& c, const float* params, void* packed, hipStream_t stream);
@@ -15,7 +16,6 @@ int mhsa_fwd_impl(const nbss_cfg& c, const float* P, const void* packed, int lay
 int mhsa_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, const void* osave,
                   void* dx, void* ws, hipStream_t st, const Side* sd);
 int tconvffn_fwd_impl(const nbss_cfg& c, const float* P, const void* packed, int layer, const void* x, void* y, void* tsave, hipStream_t st, const SeqTail* tl);
-int gb_tconvffn_fwd(const nbss_cfg& c, const float* P, int layer, const void* x, void* y, void* ws, hipStream_t st);
 size_t tconvffn_save_bytes(const nbss_cfg& c);
 
 int tconvffn_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, const void* tsave,
@@ -45,36 +45,9 @@ int adam_hyper_impl(int step, float lr, float beta1, float beta2, float* out);
 int clip_adam_impl(size_t n, float* p, float* g, float* m, float* v, float* scal, float max_norm, float grad_scale, float lr, float beta1,
                    float beta2, float eps, float wd, int step, int flags, hipStream_t st);
 
-size_t nb_ws_bytes_impl(int M, int K, int groups, int taps);
-int nb_conv_t_impl(int dtype, long nseq, int Tn, int Cin, int ldx, int Cout, int groups, int taps, const void* x, const float* w, const float* bias, void* y,
-                   const void* residual, int act_in, int act_out, void* ws, hipStream_t st);
-int nb_layernorm_impl(int dtype, long rows, int C, const void* x, const float* gamma, const float* beta, void* y, float* stats, hipStream_t st);
-int nb_gbn_impl(int dtype, int B, int F, int Tn, int C, const void* x, const float* gamma, const float* beta, float eps, int act, void* y, hipStream_t st);
-int nb_attention_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st);
-int nb_attention_relpos_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* pos, const float* ub, const float* vb, float scale, void* o,
-                                 hipStream_t st, const uint32_t* mask, float keep);
-size_t nb_relpos_bwd_ws_bytes_impl(long nseq, int Tn, int H, int heads);
-int nb_attention_relpos_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* pos, const float* ub, const float* vb, float scale,
-                                 const uint32_t* mask, float keep, const void* dO, void* dqkv, float* dpos, float* du, float* dvb, void* ws, hipStream_t st);
-int nb_group_norm_train_impl(int dtype, long nseq, int Tn, int C, int groups, const void* x, const float* gamma, const float* beta, int act, void* y, float* stats,
-                             hipStream_t st);
-int nb_group_norm_bwd_impl(int dtype, long nseq, int Tn, int C, int groups, const void* x, const float* stats, const float* gamma, const float* beta, void* dy_dx,
-                           float* dgamma, float* dbeta, hipStream_t st);
-int nb_group_norm_impl(int dtype, long nseq, int Tn, int C, int groups, const void* x, const float* gamma, const float* beta, int act, void* y, hipStream_t st);
 size_t blstm_ws_bytes_impl(int HD, int dtype);
 int blstm_fwd_impl(int dtype, long n, int Tn, int HD, int ldg, const void* gx, const float* whh0, const float* whh1, void* y, void* save, void* ws, hipStream_t st);
 int blstm_bwd_impl(int dtype, long n, int Tn, int HD, const void* dy, const void* save, const float* whh0, const float* whh1, void* dg, void* ws, hipStream_t st);
-size_t nb_bwd_ws_bytes_impl(int M, int K, int groups, int taps);
-int nb_conv_t_train_impl(int dtype, long nseq, int Tn, int Cin, int ldx, int Cout, int groups, int taps, const void* x, const float* w, const float* bias, void* y,
-                         void* y2, const void* residual, void* ws, hipStream_t st);
-int nb_conv_t_bwd_impl(int dtype, long nseq, int Tn, int Cin, int ldx, int Cout, int groups, int taps, const void* x, const float* w, const void* dy, const void* dact,
-                       void* dx, float* dw, float* dbias, void* ws, hipStream_t st);
-int nb_layernorm_bwd_impl(int dtype, long rows, int C, const void* x, const float* stats, const float* gamma, const void* du, const void* dres, void* dx, float* dgamma,
-                          float* dbeta, hipStream_t st);
-int nb_gbn_bwd_impl(int dtype, int B, int F, int Tn, int C, const void* x, const float* gamma, const float* beta, float eps, int act, const void* dy, void* dx,
-                    float* dgamma, float* dbeta, hipStream_t st);
-size_t nb_attn_bwd_ws_bytes_impl(long N, int H, int heads, int dtype);
-int nb_attention_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* dO, void* dqkv, void* ws, hipStream_t st);
 
 #define CHECK_CFG(cfg)                         \
     if (!(cfg)) return NBSS_EINVAL;            \

@@ -10,7 +10,7 @@
 //                     contraction axis of 120), PReLU', dv in place of dy, slope gradient
 //   groups (phase 2): transposed conv of dv -> du in place of LN(x); dv rows out (operand of the conv weight gradient, wgrad.hip)
 //   rows   (phase 3): LayerNorm backward + residual -> dx; affine gradients
-// The unfused path (gbwd.hip) took LN forward + 2 tap-GEMMs + PReLU backward + LN backward = ~460 us per block at batch 4.
+// The unfused path (gbwd.hip over gb_rows.hip / gb_gemm.hip) took LN forward + 2 tap-GEMMs + PReLU backward + LN backward = ~460 us per block at batch 4.
 #include "launch.h"
 #include "layout.h"
 #include "prof.h"

@@ -575,7 +575,6 @@ static int full_bwd_t(const nbss_cfg& c, const float* P, float* part, const void
     }
 }
 
-int memset_async_impl(void* p, size_t bytes, hipStream_t st);
 
 int full_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, void* dx, void* ws,
                   hipStream_t st, const Side* sd) {

@@ -8,7 +8,7 @@
 // DMA instruction writes one FRAGMENT BLOCK: the 16 rows x 32 k of one MFMA operand in reader-lane order (lane l's 16-byte piece at 16 l),
 // so the fragment read is one conflict-free ds_read_b128 at base + 16 lane and the global side fetches 64 contiguous bytes per row.
 // Two workgroups share a CU (76 KB of LDS each): one computes while the other waits for its slab or stores a tile.
-// gb_tap_gemm_lds_kernel (gbwd.hip) fed the MFMA from global memory one 16-row tile at a time: 102 TF/s over the large train step.
+// gb_tap_gemm_lds_kernel (gb_gemm.hip) fed the MFMA from global memory one 16-row tile at a time: 102 TF/s over the large train step.
 #include "tapgemm.h"
 #include "layout.h"
 

@@ -43,3 +43,6 @@ NBSS_DEV int flip_bid(int flip) { return flip ? (int)(gridDim.x - 1 - blockIdx.x
 #define NBSS_EINVAL (-1)
 #define NBSS_EUNSUPPORTED (-2)
 #define NBSS_ELAUNCH (-3)
+
+// util.hip: hipMemsetAsync behind the launch shim (the emulator build has no stream)
+int memset_async_impl(void* p, size_t bytes, hipStream_t st);

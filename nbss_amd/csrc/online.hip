@@ -370,7 +370,6 @@ __global__ void online_pos_advance_kernel(int* pos, int C) {
     if (threadIdx.x == 0 && blockIdx.x == 0) pos[0] += C;
 }
 
-int memset_async_impl(void* p, size_t bytes, hipStream_t st);
 
 static bool on_ok(int BF, int C) { return BF > 0 && C > 0 && C <= ON_CMAX; }
 

@@ -36,9 +36,11 @@ struct SeqTail {
     hipStream_t ts;  // its stream
 };
 
-// gbwd.hip: geometry-generic backward (every geometry but SpatialNet-small)
+// gbwd.hip: geometry-generic backward (every geometry but SpatialNet-small), sequenced from the pieces of gb.h
 int gb_fconv_bwd(const nbss_cfg& c, const float* P, float* G, int layer, int which, const void* x, const void* dy, void* dx, void* ws, hipStream_t st, const Side* sd);
 int gb_full_bwd(const nbss_cfg& c, const float* P, float* G, int layer, const void* x, const void* dy, void* dx, void* ws, hipStream_t st, const Side* sd);
 int gb_mhsa_bwd(const nbss_cfg& c, const float* P, float* G, int layer, const void* x, const void* dy, void* dx, void* ws, hipStream_t st, const Side* sd);
 int gb_tconvffn_bwd(const nbss_cfg& c, const float* P, float* G, int layer, const void* x, const void* dy, void* dx, void* ws, hipStream_t st, const Side* sd);
 int gb_decoder_bwd(const nbss_cfg& c, const float* P, float* G, const void* x, const float* dout, void* dx, void* ws, hipStream_t st);
+// the T-ConvFFN forward on the same pieces (bf16, T <= 256): the workspace carries the block's intermediates
+int gb_tconvffn_fwd(const nbss_cfg& c, const float* P, int layer, const void* x, void* y, void* ws, hipStream_t st);

@@ -277,7 +277,6 @@ __global__ __launch_bounds__(256) void inorm_istft_bwd_kernel(int B, int S, int 
     }
 }
 
-int memset_async_impl(void* p, size_t bytes, hipStream_t st);
 
 int stft_tables_impl(int nfft, int win_kind, float* tab, hipStream_t st) {
     if (nfft != 256 && nfft != 512) return NBSS_EUNSUPPORTED;

@@ -1,4 +1,4 @@
-// Descriptor of one tap-GEMM (gbwd.hip: every per-token linear map, grouped convolution and data gradient of the geometry-generic path):
+// Descriptor of one tap-GEMM (gb_gemm.hip: every per-token linear map, grouped convolution and data gradient of the geometry-generic path):
 //   Y[n][o] = sum_tap sum_i X[n + (tap - center) shift][i] W[g][tap][o][i]  (+ bias, activations, residual)
 #pragma once
 #include "launch.h"

@@ -10,7 +10,7 @@
 // (12 accumulator tiles; weights = MFMA A operand, fragment-ordered in LDS; tokens = N), the pre-activations the backward
 // needs again stay in registers (a3) or in LDS (a2) as packed bf16.  69 KB of LDS: two workgroups per CU.
 // A tap is a row offset into the image: (tap, channel) is ONE contraction axis of 3 x 48 = 144 (4.5 k-steps instead of 3 x 2).
-// The unfused path (gbwd.hip) ran six tap-GEMM launches + GroupNorm forward / backward per layer through ~40 [N][FFN] tensor passes.
+// The unfused path (gbwd.hip over gb_gemm.hip / gb_rows.hip) ran six tap-GEMM launches + GroupNorm forward / backward per layer through ~40 [N][FFN] tensor passes.
 #include "tchain.h"
 #include "layout.h"
 #include <cstdlib>

@@ -26,3 +26,5 @@ struct WgradArgs {
 };
 
 int wgrad_launch(const WgradArgs& a, int dtype, hipStream_t st);
+// wgrad_g.hip: dense bf16 problems on 192 x 96 output tiles with fragment reuse; NBSS_EUNSUPPORTED where the shape does not fit
+int wgrad_dense_g(const void* A, int lda, int M, const void* B, int ldb, int K, float* dW, float* dbias, long Ntok, float* part, hipStream_t st);

@@ -1,5 +1,5 @@
 """Native forward of the narrow-band conformer NBC2 (reference: models/arch/NBC2.py:152-289) on the HIP device, sequenced from the
-geometry-generic building blocks of the C ABI (`nbss_nb_*`, csrc/gbwd.hip): the encoder Conv1d along time, per block LayerNorm ->
+geometry-generic building blocks of the C ABI (`nbss_nb_*`, csrc/nb_blocks.hip): the encoder Conv1d along time, per block LayerNorm ->
 in_proj -> softmax(q k^T / sqrt(dh)) v per (sequence, head) -> out_proj + residual, GroupBatchNorm -> Linear -> SiLU -> grouped conv ->
 SiLU -> grouped conv -> GroupBatchNorm -> SiLU -> grouped conv -> SiLU -> Linear + residual, and the decoder.  Every GEMM-shaped step is
 one MFMA tap-GEMM launch (weights re-laid on the fly from the module's own fp32 parameters); activations stay in the

@@ -63,7 +63,7 @@ def main():
         out[f"{nm}_large_full"] = ops.full_fwd(cs.lib, cs.cfg, cs.flat, cs.packed, 0, x)
         out[f"{nm}_large_mhsa"] = ops.mhsa_fwd(cs.lib, cs.cfg, cs.flat, cs.packed, 0, x, o_save=ops.mhsa_save(cs.lib, cs.cfg, x.device))
         out[f"{nm}_large_tconvffn"] = ops.tconvffn_fwd(cs.lib, cs.cfg, cs.flat, cs.packed, 0, x)
-        # ... and the geometry-generic backward (gbwd.hip: LDS-staged tap-GEMM weights, LDS partial sums of the row / GroupNorm kernels, the two attention kernels)
+        # ... and the geometry-generic backward (gbwd.hip over gb_gemm.hip: LDS-staged tap-GEMM weights; gb_rows.hip: LDS partial sums of the row / GroupNorm kernels; gb_attn.hip: the two attention kernels)
         dy, _ = cs.stream(seed=34)
         save = ops.mhsa_save(cs.lib, cs.cfg, x.device)
         for name, fn in (("fconv_bwd", lambda G, ws: ops.fconv_bwd(cs.lib, cs.cfg, cs.flat, G, cs.packed, 0, 1, x, dy, ws)),
