@@ -264,7 +264,7 @@ int nbss_online_istft_step(int n_fft, int norm, int B, int S, int C, const float
 
 /* ---- narrow-band building blocks (models/arch/NBC2.py:152-238 in the reference: pre-norm self-attention over time + convolutional feed-forward with
  * GroupBatchNorm, per (batch, frequency) sequence) -------------------------------------------------------------------------------------------------
- * Geometry-generic kernels (csrc/nb_blocks.hip over gb_gemm.hip, gb_rows.hip, gb_attn.hip, attn_relpos.hip, attn_kb.hip), one operation per call on caller-owned tensors of `dtype` (NBSS_F32 | NBSS_BF16) in the [nseq][T][C] layout
+ * Geometry-generic kernels (csrc/nb_blocks.hip over gb_gemm.hip, gb_rows.hip, gb_attn.hip, attn_relpos.hip, attn_kb.hip, attn_relpos_kb.hip), one operation per call on caller-owned tensors of `dtype` (NBSS_F32 | NBSS_BF16) in the [nseq][T][C] layout
  * of the reference's [B*F, T, C] activations; weights / biases / affines are the fp32 parameters in their state_dict layout.  nbss_amd/nbc2.py sequences an
  * NBC2 forward from them.  act_in / act_out: 1 = SiLU applied to the input as it is read / to the result.
  * conv_t: y[n][t][o] = sum_tap sum_i x[n][t + tap - taps/2][i] w[o][i][tap] + bias[o] (+ residual[n][t][o]), grouped, zero padded ("same"); taps = 1 is a
@@ -290,6 +290,13 @@ int nbss_nb_attention_fwd(int dtype, int64_t nseq, int T, int H, int heads, cons
 int nbss_nb_attention_relpos_fwd(int dtype, int64_t nseq, int T, int H, int heads, const void* qkv, const void* pos, const float* u_bias, const float* v_bias,
                                  float scale, void* o, void* stream);
 int nbss_nb_group_norm(int dtype, int64_t nseq, int T, int C, int groups, const void* x, const float* gamma, const float* beta, int act_out, void* y, void* stream);
+/* the two attentions on LONG sequences, forward only (inference on whole utterances: the reference evaluates every dataset on 4 - 32 s, 400 - 2 000 frames,
+ * through NBC2.py:152-238 resp. NBC.py:106-143, which materialise [nseq heads][T][T] scores): 1 <= T <= 4096, the keys walked in blocks of 64 with a running
+ * max / sum per query (csrc/attn_kb.hip, csrc/attn_relpos_kb.hip: per key block also the 127 rows of pos its offsets i - j need).  Same tensors as
+ * attention_fwd / attention_relpos_fwd; dh in {24, 48, 96} resp. {24, 48}; anything else: NBSS_EUNSUPPORTED.  One writer per output element, no atomics. */
+int nbss_nb_attention_long_fwd(int dtype, int64_t nseq, int T, int H, int heads, const void* qkv, void* o, void* stream);
+int nbss_nb_attention_relpos_long_fwd(int dtype, int64_t nseq, int T, int H, int heads, const void* qkv, const void* pos, const float* u_bias, const float* v_bias,
+                                      float scale, void* o, void* stream);
 
 /* ---- the same building blocks for TRAINING (autograd of the reference's torch.nn NBC2: NBC2.py:152-238; sequenced by nbss_amd/nbc2.py) ---------------
  * conv_t_train: conv_t without fused input / output activations, plus an optional second output y_silu = SiLU(y) (pre-activation and activation of a

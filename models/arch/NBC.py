@@ -150,6 +150,14 @@ class NBC(nn.Module):
         """nbss_amd.nbc.NativeNBC of this module when the HIP library is there and the configuration is one its kernels take, else None (the reason is kept)"""
         return native_runner(self, "nbss_amd.nbc", "NativeNBC")[0]
 
+    def _long_ok(self, T: int) -> bool:
+        """beyond 256 frames: inference (no_grad, eval mode) with NBSS_NB_LONG=1 runs the key-blocked attention, up to 4096 frames and the sinusoid table
+        (nbss_amd/nb.py: long_enabled)"""
+        from nbss_amd.nb import T_LONG, long_enabled
+        max_len = self.sa_layers[0].self_attn.rel_pos.max_len
+        return (T > 256 and not torch.is_grad_enabled() and not self.training and long_enabled() and T <= T_LONG
+                and T - self.encoder.kernel_size[0] + 1 <= max_len + 1)
+
     def _train_supported(self) -> Optional[str]:
         """nbss_amd.nbc.train_supported(self), evaluated once per module structure (it walks every block and builds an id-set of all parameters: host
         work that does not belong in every training step); re-evaluated when the number of parameters or sub-modules changes"""
@@ -173,7 +181,7 @@ class NBC(nn.Module):
                 why = "NBSS_NBC_NATIVE=0"
             elif x.dtype not in (torch.float32, torch.bfloat16):
                 why = f"input dtype {x.dtype}"
-            elif not 4 <= T <= 256:
+            elif not 4 <= T <= 256 and not self._long_ok(T):
                 why = f"{T} frames: the attention kernel keeps a sequence and its offsets table in LDS (4 .. 256)"
             elif any(p.dtype != torch.float32 for p in self.parameters()):
                 why = "parameters are not fp32"

@@ -144,6 +144,12 @@ class NBC2(nn.Module):
         """the HIP path (nbss_amd/nbc2.py) when this configuration is one its kernels are built for, else None (the reason is kept: models/arch/base/native.py)"""
         return native_runner(self, "nbss_amd.nbc2", "NativeNBC2")[0]
 
+    @staticmethod
+    def _long_ok(T: int) -> bool:
+        """beyond 256 frames: inference (no_grad) with NBSS_NB_LONG=1 runs the key-blocked attention, up to 4096 frames (nbss_amd/nb.py: long_enabled)"""
+        from nbss_amd.nb import T_LONG, long_enabled
+        return not torch.is_grad_enabled() and long_enabled() and T <= T_LONG
+
     def _native_or_reason(self, x: Tensor):
         """(runner, None) when the native path takes this call, else (None, reason); reason None on the CPU (nothing to report)"""
         if not x.is_cuda:
@@ -156,7 +162,7 @@ class NBC2(nn.Module):
         nat = self._native()  # first: supported() also guards the attribute reads below (other norm types have no group_size)
         if nat is None:
             return None, _NATIVE[self][1] or "native path unavailable"
-        if T > 256:
+        if T > 256 and not self._long_ok(T):
             return None, f"{T} frames: the attention kernels keep a sequence in LDS (<= 256)"
         gs = getattr(self.sa_layers[0].norm2, "group_size", None)
         if F != gs:

@@ -3,7 +3,8 @@
 narrow-band network ("NB_BLSTM", "NBC" or "NBC2").  STFT (hann, hop = n_overlap) -> per-frequency normalisation by the mean
 magnitude of the reference channel -> network on [B,F,T,2C] -> de-normalisation -> iSTFT.  `neg_si_sdr` is the full-band PIT
 criterion's metric (the reference takes SI-SDR from torchmetrics; its closed form is restated here).  On a HIP device the STFT / iSTFT are the
-kernels of nbss_amd/csrc/signal.hip (through models.io.stft.STFT) and NBC / NBC2 take their native paths; the CPU runs plain PyTorch."""
+kernels of nbss_amd/csrc/signal.hip (through models.io.stft.STFT) and NBC / NBC2 take their native paths (whole utterances beyond 256 frames under
+no_grad: with NBSS_NB_LONG=1, else their torch.nn modules with a warning); the CPU runs plain PyTorch."""
 from typing import Any, Dict
 
 import torch

@@ -20,48 +20,23 @@
 // consecutive rows 100 (fp32) / 52 (bf16) banks apart instead of 96 / 48: the 16 rows a ds_read_b128 group touches land on distinct banks but for one pair.
 // Transposed operands (token axis as the K dimension) are read as in the siblings: ds_read_b64_tr_b16 for bf16, element gathers for fp32 (conflict-free:
 // 16 consecutive words x 4 rows that are 400 words apart).
-// Tail rows of a block (>= T) are staged as zeros and their scores masked, so any T >= 1 works; the launchers keep the narrow-band cap of 256 frames.
-#include "launch.h"
+// Tail rows of a block (>= T) are staged as zeros and their scores masked, so any T >= 1 works; the training launchers keep the narrow-band cap of 256 frames.
+//
+// Long sequences (nbss_nb_attention_long_fwd: inference on whole utterances, T <= 4096): the same forward kernel, also instantiated for the narrow heads
+// (DH = 24, 48) the whole-head kernels of gb_attn.hip serve up to 256 frames.  K steps (DH + 31) / 32 with zero fragment lanes from DH on, (DH + 15) / 16
+// output tiles whose rows >= DH are never stored; the backward kernels stay at whole 32-wide K steps (DH = 96).
+#include "kb.h"
 #include "layout.h"
 #include "blocks.h"
 #include "nb.h"
-
-#define KB_THREADS 256
-#define KB_BLK 64  // rows per LDS block = rows per workgroup (4 waves x one 16-row tile)
-#define KB_TMAX 256
-
-NBSS_DEV int kb_perm_k(int g4, int j) { return j < 4 ? 4 * g4 + j : 16 + 4 * g4 + (j - 4); }
-
-// rows t0 .. t0 + 63 of the head's [Tn][DH] slice of a [N][ld] tensor into a row-major image (row stride DH + 16 bytes), zero rows from Tn on
-template <class T, int DH>
-NBSS_DEV void kb_stage(T* img, const T* src, int ld, int t0, int Tn) {
-    constexpr int VE = 16 / sizeof(T), PR = DH / VE, LD = DH + VE;
-    for (int e = threadIdx.x; e < KB_BLK * PR; e += KB_THREADS) {
-        const int r = e / PR, pc = e % PR;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (t0 + r < Tn) v = *reinterpret_cast<const u32x4*>(src + (size_t)(t0 + r) * ld + pc * VE);
-        *reinterpret_cast<u32x4*>(img + (size_t)r * LD + pc * VE) = v;
-    }
-}
-// A fragment whose K dimension is the token axis (permuted order: two stacked C tiles), rows = channels 16 mt + l15, from such an image
-template <class T, int DH>
-NBSS_DEV void kb_frag_t(Frag<T>& f, const T* img, int tok0, int mt) {
-    constexpr int LD = DH + 16 / sizeof(T);
-    const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4;
-    if constexpr (sizeof(T) == 2) {
-        frag_load_tr(f, img + (size_t)(tok0 + 4 * g4 + (l15 >> 2)) * LD + 16 * mt + 4 * (l15 & 3), LD);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) frag_set(f, j, load1(img + (size_t)(tok0 + kb_perm_k(g4, j)) * LD + 16 * mt + l15));
-    }
-}
 
 // BWD = false: the forward alone (O; dO / dqkv / lse / Dv are not touched)
 template <class T, int DH, bool BWD>
 __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restrict__ qkv, const T* __restrict__ dO, T* __restrict__ O, T* __restrict__ dqkv,
                                                                float* __restrict__ lse, float* __restrict__ Dv, int Tn, int H, int heads) {
-    static_assert(DH % 32 == 0, "whole 32-wide K steps");
-    constexpr int KS = DH / 32, MTD = DH / 16, LD = DH + 16 / sizeof(T), JT = KB_BLK / 16;
+    static_assert(DH % 8 == 0 && (DH % 32 == 0 || !BWD), "the backward takes whole 32-wide K steps");
+    constexpr int KS = (DH + 31) / 32, MTD = (DH + 15) / 16, LD = DH + 16 / sizeof(T), JT = KB_BLK / 16;
+    constexpr bool WHOLE = DH % 32 == 0;  // else: fragment lanes with d0 = 32 ks + 8 g4 >= DH are zeros
     NBSS_LDS(smem);
     T* Ks = reinterpret_cast<T*>(smem);  // [KB_BLK][LD]
     T* Vs = Ks + (size_t)KB_BLK * LD;    // [KB_BLK][LD]
@@ -81,7 +56,7 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
     for (int ks = 0; ks < KS; ++ks) {
         frag_zero(qf[ks]);
         frag_zero(dof[ks]);
-        if (qv) {
+        if (qv && (WHOLE || 32 * ks + 8 * g4 < DH)) {
             frag_load(qf[ks], qkv + nq * ld + head * DH + 32 * ks + 8 * g4);
             if (BWD) frag_load(dof[ks], dO + nq * H + head * DH + 32 * ks + 8 * g4);
         }
@@ -108,7 +83,8 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 Frag<T> kf, vf;
-                frag_load(kf, Ks + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
+                if constexpr (!WHOLE) frag_zero(kf);
+                if (WHOLE || 32 * ks + 8 * g4 < DH) frag_load(kf, Ks + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
                 st[jt] = mma(kf, qf[ks], st[jt]);
                 if (BWD) {
                     frag_load(vf, Vs + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
@@ -160,7 +136,7 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
             const int d = 16 * mt + 4 * g4;
 #pragma unroll
             for (int r = 0; r < 4; ++r) oacc[mt][r] *= inv;
-            if (qv) store4(O + nq * H + head * DH + d, oacc[mt][0], oacc[mt][1], oacc[mt][2], oacc[mt][3]);
+            if (qv && (DH % 16 == 0 || d < DH)) store4(O + nq * H + head * DH + d, oacc[mt][0], oacc[mt][1], oacc[mt][2], oacc[mt][3]);
         }
     }
     if (!BWD) return;
@@ -338,4 +314,14 @@ int nb_attention_kb_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, con
     if (heads <= 0 || H != heads * 96 || Tn > KB_TMAX || heads > 65535) return NBSS_EUNSUPPORTED;
     return dtype == NBSS_BF16 ? kb_attn_bwd<bf16_t, 96>(nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st)
                               : kb_attn_bwd<float, 96>(nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st);
+}
+// forward on long sequences (nbss_nb_attention_long_fwd): the key-blocked kernel at every head width the narrow-band networks use, T <= KB_TLONG
+int nb_attention_long_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st) {
+    if (heads <= 0 || H % heads) return NBSS_EINVAL;
+    if (Tn > KB_TLONG || heads > 65535) return NBSS_EUNSUPPORTED;
+    const int dh = H / heads;
+    if (dh == 96) return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 96>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 96>(nseq, Tn, H, heads, qkv, o, st);
+    if (dh == 48) return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 48>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 48>(nseq, Tn, H, heads, qkv, o, st);
+    if (dh == 24) return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 24>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 24>(nseq, Tn, H, heads, qkv, o, st);
+    return NBSS_EUNSUPPORTED;
 }

@@ -509,6 +509,15 @@ int nbss_nb_attention_relpos_fwd(int dtype, int64_t nseq, int T, int H, int head
     if (!nb_dtype_ok(dtype) || nseq <= 0 || nseq >= 65536 * 32768LL || T <= 0 || H <= 0 || !qkv || !pos || !u_bias || !v_bias || !o) return NBSS_EINVAL;
     return nb_attention_relpos_fwd_impl(dtype, (long)nseq, T, H, heads, qkv, pos, u_bias, v_bias, scale, o, (hipStream_t)stream, nullptr, 1.0f);
 }
+int nbss_nb_attention_long_fwd(int dtype, int64_t nseq, int T, int H, int heads, const void* qkv, void* o, void* stream) {
+    if (!nb_dtype_ok(dtype) || nseq <= 0 || nseq >= 65536 * 32768LL || T <= 0 || H <= 0 || !qkv || !o) return NBSS_EINVAL;
+    return nb_attention_long_fwd_impl(dtype, (long)nseq, T, H, heads, qkv, o, (hipStream_t)stream);
+}
+int nbss_nb_attention_relpos_long_fwd(int dtype, int64_t nseq, int T, int H, int heads, const void* qkv, const void* pos, const float* u_bias, const float* v_bias,
+                                      float scale, void* o, void* stream) {
+    if (!nb_dtype_ok(dtype) || nseq <= 0 || nseq >= 65536 * 32768LL || T <= 0 || H <= 0 || !qkv || !pos || !u_bias || !v_bias || !o) return NBSS_EINVAL;
+    return nb_attention_relpos_long_fwd_impl(dtype, (long)nseq, T, H, heads, qkv, pos, u_bias, v_bias, scale, o, (hipStream_t)stream);
+}
 int nbss_nb_group_norm(int dtype, int64_t nseq, int T, int C, int groups, const void* x, const float* gamma, const float* beta, int act_out, void* y, void* stream) {
     if (!nb_dtype_ok(dtype) || nseq <= 0 || nseq * (int64_t)(groups > 0 ? groups : 1) >= (1LL << 31) || T <= 0 || C <= 0 || !x || !y || !gamma || !beta) return NBSS_EINVAL;
     return nb_group_norm_impl(dtype, (long)nseq, T, C, groups, x, gamma, beta, act_out, y, (hipStream_t)stream);

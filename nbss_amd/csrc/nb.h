@@ -1,5 +1,6 @@
 // nb.h — the implementations behind the narrow-band building blocks of the C ABI (capi.hip: nbss_nb_*; include/nbss_hip.h documents the arguments).
-// Defined in nb_blocks.hip, but for nb_attention_relpos_* / nb_relpos_bwd_ws_bytes_impl (attn_relpos.hip) and nb_attention_kb_* (attn_kb.hip).
+// Defined in nb_blocks.hip, but for nb_attention_relpos_* / nb_relpos_bwd_ws_bytes_impl (attn_relpos.hip), nb_attention_kb_* / nb_attention_long_fwd_impl
+// (attn_kb.hip) and nb_attention_relpos_long_fwd_impl (attn_relpos_kb.hip).
 #pragma once
 #include "launch.h"
 
@@ -33,3 +34,7 @@ int nb_attention_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const 
 // head width 96: the key-blocked kernels of attn_kb.hip (nb_attention_fwd_impl / nb_attention_bwd_impl dispatch here)
 int nb_attention_kb_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st);
 int nb_attention_kb_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* dO, void* O, void* dqkv, float* lse, float* Dv, hipStream_t st);
+// forward on long sequences (T <= 4096: inference on whole utterances), key-blocked: attn_kb.hip (head widths 24 / 48 / 96), attn_relpos_kb.hip (24 / 48)
+int nb_attention_long_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st);
+int nb_attention_relpos_long_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* pos, const float* ub, const float* vb, float scale,
+                                      void* o, hipStream_t st);

@@ -7,6 +7,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 import weakref
 from typing import Optional
 
@@ -15,6 +16,16 @@ from torch import Tensor
 
 from . import ops
 from ._lib import NBSS_BF16, NBSS_F32, Lib, NbssError
+
+
+T_WHOLE = 256  # frames per sequence of the whole-head attention kernels: the training paths' limit
+T_LONG = 4096  # ... of the key-blocked forward kernels behind nbss_nb_attention_long_fwd / nbss_nb_attention_relpos_long_fwd
+
+
+def long_enabled() -> bool:
+    """NBSS_NB_LONG=1: inference (`NativeNBC2.forward`, `NativeNBC.forward`) beyond 256 frames runs natively, through the key-blocked attention kernels.
+    Read at call time, like NBSS_NBC2_NATIVE; off by default (then such calls are refused, and the modules take their torch.nn path with a warning)."""
+    return os.environ.get("NBSS_NB_LONG", "0") == "1"
 
 
 def pad8(c: int) -> int:

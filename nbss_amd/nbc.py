@@ -7,7 +7,8 @@ of nb.py; the relative-position attention launches, the encoder / decoder tap ar
             -> out_proj + residual;  LayerNorm -> linear1 -> SiLU -> 3 x (grouped conv -> GroupNorm(8) -> SiLU) -> linear2 + residual
   decoder   ConvTranspose1d(k)                                          = a zero-padded tap-GEMM over the frames shifted by one, taps flipped
 
-Inference and training: `models.arch.NBC.NBC.forward` takes this path by default for every call on a HIP tensor the kernels support (NBSS_NBC_NATIVE=0
+Inference beyond 256 frames (whole utterances) with NBSS_NB_LONG=1 (nb.long_enabled): `nbss_nb_attention_relpos_long_fwd`, up to 4096 frames and the sinusoid
+table's 1001 frames behind the encoder.  Inference and training: `models.arch.NBC.NBC.forward` takes this path by default for every call on a HIP tensor the kernels support (NBSS_NBC_NATIVE=0
 switches it off).  The reference trains NBC with dropout 0.1 inside the attention and the feed-forward (NBC.py:73-104,161-193): the attention dropout
 goes through keep-bits both passes read (`_keep_bits`), the element-wise dropouts are device tensors.  `tests/test_nbc_native.py` runs both paths on the
 emulator and on the device against the torch.nn module, `tests/test_nb_native_vs_reference.py` against numbers of the reference's own module."""
@@ -19,7 +20,7 @@ import torch
 from torch import Tensor
 
 from ._lib import NbssError
-from .nb import Launcher, NativeRunner, TrainFn, pad8
+from .nb import T_LONG, T_WHOLE, Launcher, NativeRunner, TrainFn, long_enabled, pad8
 
 
 def supported(net) -> Optional[str]:
@@ -122,7 +123,13 @@ class NativeNBC(NativeRunner):
         B, F, T, Cin = x.shape
         K = net.encoder.kernel_size[0]
         Ti = T - K + 1  # frames inside the network
-        if Ti < 1 or T > 256:
+        if what == "forward" and long_enabled() and Ti >= 1:  # (inference alone: the backward blocks are whole-head kernels)
+            max_len = net.sa_layers[0].self_attn.rel_pos.max_len
+            if T > T_LONG:
+                raise NbssError(f"NBC native {what}: {T} frames; the key-blocked attention takes <= {T_LONG} frames")
+            if Ti > max_len + 1:
+                raise NbssError(f"NBC native {what}: {T} frames; the sinusoid table holds the offsets of {max_len + 1} frames behind the encoder (kernel {K})")
+        elif Ti < 1 or T > T_WHOLE:
             lds = "kernels keep a sequence and its" if what == "training" else "kernel keeps a sequence's K / V /"
             raise NbssError(f"NBC native {what}: {T} frames (kernel {K}; the attention {lds} offsets table in LDS: <= 256)")
         b0 = net.sa_layers[0]
@@ -158,6 +165,8 @@ class NativeNBC(NativeRunner):
         L = Launcher(self.lib, x)
         nseq = B * F
         L.alloc_ws(shapes)
+        # (beyond a head's K / V / offsets table in LDS: keys and table rows walked in blocks; T, not Ti, decides — the launch sequence up to 256 frames is one)
+        attention = "nbss_nb_attention_relpos_long_fwd" if T > T_WHOLE else "nbss_nb_attention_relpos_fwd"
         # encoder: y[t'] = sum_k x[t' + k] w[k] (t' < T - K + 1) = rows K/2 .. of the zero-padded ("same", centre K/2) conv over the T frames
         xin = L.pad_cols(x, nseq, T, Cin)
         wenc = L.padded(L.f32(net.encoder.weight), H, Cin8, K1)
@@ -168,8 +177,7 @@ class NativeNBC(NativeRunner):
             qkv = L.conv(u, nseq, Ti, H, H, 3 * H, 1, 1, self._qkv(L, a, "weight"), self._qkv(L, a, "bias"))
             pos = L.conv(self._pos_table(L, a, Ti), 1, 2 * Ti - 1, H, H, H, 1, 1, a.pos_proj.weight, None)
             o = torch.empty_like(h)
-            L.lib.call("nbss_nb_attention_relpos_fwd", L.dt, nseq, Ti, H, heads, L.p(qkv), L.p(pos), L.p(L.f32(a.u_bias)), L.p(L.f32(a.v_bias)), 1.0 / a.sqrt_dim,
-                       L.p(o), L.st)
+            L.lib.call(attention, L.dt, nseq, Ti, H, heads, L.p(qkv), L.p(pos), L.p(L.f32(a.u_bias)), L.p(L.f32(a.v_bias)), 1.0 / a.sqrt_dim, L.p(o), L.st)
             h = L.conv(o, nseq, Ti, H, H, H, 1, 1, a.out_proj.weight, a.out_proj.bias, res=h)
             v, _ = L.layernorm(h, b.norm2)
             c = L.conv(v, nseq, Ti, H, H, FFN, 1, 1, b.linear1.weight, b.linear1.bias, act_out=1)

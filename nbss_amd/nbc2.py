@@ -9,7 +9,8 @@ the SiLU' factor in their epilogue, the token-contraction weight gradients of cs
 every parameter gradient comes from these kernels, torch contributes buffers and two residual adds per block.
 
 `supported(net)` names what the kernels are built for: norms (LN, GBN, GBN) with per-frame GroupBatchNorm statistics, no dropout, head
-width 24, 48 or 96 (96 = NBC2-large, dim_hidden 192 with 2 heads: the key-blocked attention of csrc/attn_kb.hip), channel counts that are multiples of 8 per conv group, sequences of at most 256 frames."""
+width 24, 48 or 96 (96 = NBC2-large, dim_hidden 192 with 2 heads: the key-blocked attention of csrc/attn_kb.hip), channel counts that are multiples of 8 per conv group, sequences of at most 256 frames
+— inference with NBSS_NB_LONG=1 (nb.long_enabled): at most 4096 frames, the attention of longer sequences through `nbss_nb_attention_long_fwd`."""
 from __future__ import annotations
 
 from typing import Optional
@@ -18,7 +19,7 @@ import torch
 from torch import Tensor
 
 from ._lib import NbssError
-from .nb import Launcher, NativeRunner, TrainFn, pad8
+from .nb import T_LONG, T_WHOLE, Launcher, NativeRunner, TrainFn, long_enabled, pad8
 
 
 def supported(net) -> Optional[str]:
@@ -79,7 +80,10 @@ class NativeNBC2(NativeRunner):
         """checks the input against the kernels' limits -> (B, F, T, Cin, Cin8, Cout, Co8, H, FFN, heads, g, ks, ks_e) and the tap-GEMM shapes of the network"""
         net = self.net
         B, F, T, Cin = x.shape
-        if T > 256:
+        if what == "forward" and long_enabled():  # (inference alone: the backward blocks are whole-head kernels)
+            if T > T_LONG:
+                raise NbssError(f"NBC2 native {what}: {T} frames; the key-blocked attention takes <= {T_LONG} frames")
+        elif T > T_WHOLE:
             kern = "kernels keep" if what == "training" else "kernel keeps"
             raise NbssError(f"NBC2 native {what}: {T} frames; the attention {kern} a sequence's K / V in LDS (<= 256 frames)")
         gs = net.sa_layers[0].norm2.group_size
@@ -100,13 +104,14 @@ class NativeNBC2(NativeRunner):
         nseq = B * F
         L.alloc_ws(shapes)  # scratch for the re-laid weights of one launch (the largest of the network)
         stats = torch.empty(nseq * T, 2, dtype=torch.float32, device=L.dev)  # LayerNorm statistics (unused here: one buffer for all blocks)
+        attention = "nbss_nb_attention_long_fwd" if T > T_WHOLE else "nbss_nb_attention_fwd"  # (beyond a head's K / V in LDS: walked in blocks of 64 keys)
         # SiLU is fused into the consumer (act_in) or behind the norm
         h = L.conv(L.pad_cols(x, nseq, T, Cin), nseq, T, Cin, Cin8, H, 1, ks_e, net.encoder.weight, net.encoder.bias)
         for b in net.sa_layers:
             u, _ = L.layernorm(h, b.norm1, stats)
             qkv = L.conv(u, nseq, T, H, H, 3 * H, 1, 1, b.self_attn.in_proj_weight, b.self_attn.in_proj_bias)
             o = torch.empty_like(h)
-            L.lib.call("nbss_nb_attention_fwd", L.dt, nseq, T, H, heads, L.p(qkv), L.p(o), L.st)
+            L.lib.call(attention, L.dt, nseq, T, H, heads, L.p(qkv), L.p(o), L.st)
             h = L.conv(o, nseq, T, H, H, H, 1, 1, b.self_attn.out_proj.weight, b.self_attn.out_proj.bias, res=h)
             v = L.gbn(h, b.norm2, B, F, T, 0)
             a = L.conv(v, nseq, T, H, H, FFN, 1, 1, b.linear1.weight, b.linear1.bias)
