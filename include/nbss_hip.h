@@ -156,7 +156,9 @@ int64_t nbss_stft_tables_bytes(int n_fft);
 int nbss_stft_tables(int n_fft, int window, float* tables, void* stream);
 /* STFT.stft (stft.py:49-66) + Norm('frequency', online=True).norm (norm.py:77-81,94) + the
  * [B,C,F,T] complex -> [B,F,T,2C] real re-layout of TrainModule.forward (SharedTrainer.py:113-117).
- * x [B,C,N] fp32 -> X [B,F,T,2C] of `dtype` (T = N/hop + 1), xrmm [B,F,T] fp32 = |X_ref| + 1e-6. */
+ * x [B,C,N] fp32 -> X [B,F,T,2C] of `dtype` (T = N/hop + 1), xrmm [B,F,T] fp32 = |X_ref| + 1e-6.
+ * N is unrestricted apart from N >= n_fft (NBSS_EINVAL below that): rows of x that do not start on a
+ * 16-byte boundary (N % 4 != 0) are read sample by sample, aligned rows with 16-byte loads. */
 int nbss_stft_norm_fwd(int n_fft, int dtype, int B, int C, int N, int ref_channel, const float* tables, const float* x, void* X, float* xrmm,
                        void* stream);
 /* Norm.inorm (norm.py:97-108) + STFT.istft (stft.py:68-97): out [B,F,T,2S] fp32 -> y [B,S,N].

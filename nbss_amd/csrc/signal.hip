@@ -81,7 +81,9 @@ NBSS_DEV int reflect_idx(int n, int N) {
 }
 
 // one wave = 16 frames of one batch item, all channels; output [B,F,T,2C] normalised + XrMM [B,F,T]
-template <class T, int NFFT>
+// VEC: every row of x starts on a 16-byte boundary (x itself does and N % 4 == 0; decided by stft_norm_impl), so a lane's 8 in-range samples
+// are two 16-byte loads.  With N % 4 != 0 most rows do not, and the instantiation without it reads sample by sample.
+template <class T, int NFFT, bool VEC>
 __global__ __launch_bounds__(256) void stft_norm_kernel(int B, int C, int N, int Tn, int ref, const float* __restrict__ tab,
                                                         const float* __restrict__ x, T* __restrict__ X, float* __restrict__ xrmm) {
     constexpr int HOP = NFFT / 2, F = NFFT / 2 + 1, KSm = NFFT / 32, MTq = (2 * F + 15) / 16;
@@ -103,9 +105,9 @@ __global__ __launch_bounds__(256) void stft_norm_kernel(int B, int C, int N, int
 #pragma unroll
             for (int ks = 0; ks < KSm; ++ks) {
                 Frag<float> bq;
-                const int p0 = t * HOP + ks * 32 + 8 * g4 - NFFT / 2;  // first sample of this lane's 8 (centre padding removed)
+                const int p0 = t * HOP + ks * 32 + 8 * g4 - NFFT / 2;  // first sample of this lane's 8 (centre padding removed): a multiple of 8
                 if (t < Tn) {
-                    if (p0 >= 0 && p0 + 8 <= N) {
+                    if (VEC && p0 >= 0 && p0 + 8 <= N) {
                         load8(xc + p0, bq.v);
                     } else {
 #pragma unroll
@@ -286,17 +288,24 @@ int stft_tables_impl(int nfft, int win_kind, float* tab, hipStream_t st) {
 
 static int grid_for(int ntask) { return cdiv(ntask, 4) < 4096 ? cdiv(ntask, 4) : 4096; }
 
+template <class T, int NFFT>
+static void stft_norm_launch(bool vec, dim3 grid, hipStream_t st, int B, int C, int N, int Tn, int ref, const float* tab, const float* x, void* X, float* xrmm) {
+    if (vec) NBSS_LAUNCH((stft_norm_kernel<T, NFFT, true>), grid, dim3(256), 0, st, B, C, N, Tn, ref, tab, x, (T*)X, xrmm);
+    else NBSS_LAUNCH((stft_norm_kernel<T, NFFT, false>), grid, dim3(256), 0, st, B, C, N, Tn, ref, tab, x, (T*)X, xrmm);
+}
+
 int stft_norm_impl(int nfft, int dtype, int B, int C, int N, int ref, const float* tab, const float* x, void* X, float* xrmm, hipStream_t st) {
     if (ref < 0 || ref >= C || N < nfft) return NBSS_EINVAL;
     const int Tn = N / (nfft / 2) + 1, MTq = cdiv(nfft + 2, 16);
+    const bool vec = N % 4 == 0 && (uintptr_t)x % 16 == 0;  // row (b, c) starts at x + (b C + c) N
     ProfScope ps(PK_STFT, st);
-    dim3 grid(grid_for(B * cdiv(Tn, 16) * MTq)), block(256);
+    dim3 grid(grid_for(B * cdiv(Tn, 16) * MTq));
     if (nfft == 256) {
-        if (dtype == NBSS_BF16) NBSS_LAUNCH((stft_norm_kernel<bf16_t, 256>), grid, block, 0, st, B, C, N, Tn, ref, tab, x, (bf16_t*)X, xrmm);
-        else NBSS_LAUNCH((stft_norm_kernel<float, 256>), grid, block, 0, st, B, C, N, Tn, ref, tab, x, (float*)X, xrmm);
+        if (dtype == NBSS_BF16) stft_norm_launch<bf16_t, 256>(vec, grid, st, B, C, N, Tn, ref, tab, x, X, xrmm);
+        else stft_norm_launch<float, 256>(vec, grid, st, B, C, N, Tn, ref, tab, x, X, xrmm);
     } else if (nfft == 512) {
-        if (dtype == NBSS_BF16) NBSS_LAUNCH((stft_norm_kernel<bf16_t, 512>), grid, block, 0, st, B, C, N, Tn, ref, tab, x, (bf16_t*)X, xrmm);
-        else NBSS_LAUNCH((stft_norm_kernel<float, 512>), grid, block, 0, st, B, C, N, Tn, ref, tab, x, (float*)X, xrmm);
+        if (dtype == NBSS_BF16) stft_norm_launch<bf16_t, 512>(vec, grid, st, B, C, N, Tn, ref, tab, x, X, xrmm);
+        else stft_norm_launch<float, 512>(vec, grid, st, B, C, N, Tn, ref, tab, x, X, xrmm);
     } else {
         return NBSS_EUNSUPPORTED;
     }
