@@ -24,6 +24,10 @@ from torch import Tensor
 from models.io.loss import Loss, neg_si_sdr
 from models.io.norm import Norm
 from models.io.stft import STFT
+from models.utils.metrics import pit_reorder as _reordered, val_metrics
+
+
+VAL_METRICS = ("loss", "si_sdr", "sdr")  # what `val_metric` may name: val/metric = -loss | SI-SDR | SDR (reference :175)
 
 
 class _FusedIO(torch.autograd.Function):
@@ -59,7 +63,9 @@ class TrainModule(nn.Module):
         self.norm = norm if norm is not None else Norm(mode="utterance")
         self.loss = loss if loss is not None else Loss(loss_func=neg_si_sdr, pit=True)
         self.optimizer, self.lr_scheduler = optimizer, lr_scheduler
-        self.metrics, self.val_metric, self.exp_name, self.reset = list(metrics), val_metric, exp_name, reset
+        if val_metric not in VAL_METRICS:
+            raise ValueError(f"val_metric must be one of {', '.join(VAL_METRICS)} (reference SharedTrainer.py:175), got {val_metric!r}")
+        self.metrics, self.mchunk, self.val_metric, self.exp_name, self.reset = list(metrics), mchunk, val_metric, exp_name, reset
         self.name = type(arch).__name__
         self.precision = "32"
 
@@ -481,18 +487,22 @@ def fit(cfg: dict) -> Dict[str, Any]:
             n += 1
         # validation pass of the epoch (forward-only path, every rank the same unsharded split; the configured loss: ts carries it):
         # `val/<loss name>` is what `val_metric: loss` monitors in the reference (SharedTrainer.py:151-205) and what a ReduceLROnPlateau scheduler steps on
-        vtot, vn = 0.0, 0
+        vtot, vn, vsdr, vsi = 0.0, 0, 0.0, 0.0
         for x, ys, _ in data.batches(1, 0, 1, 0):
-            vl, _, _, _, _ = ts.forward_loss(x[:, module.channels].to(dev).contiguous(), ys[:, :, module.ref_channel].to(dev).contiguous(), need_grad=False)
-            vtot, vn = vtot + float(vl), vn + 1
+            yr = ys[:, :, module.ref_channel].to(dev).contiguous()
+            vl, yr_hat, _, _, perm = ts.forward_loss(x[:, module.channels].to(dev).contiguous(), yr, need_grad=False)
+            sdr, si = val_metrics(_reordered(yr_hat, perm), yr)  # the reference's validation step: always SDR and SI-SDR (:166-182)
+            vtot, vn, vsdr, vsi = vtot + float(vl), vn + 1, vsdr + sdr, vsi + si
         val = vtot / vn if vn else float("nan")
+        vrec = {"val/sdr": vsdr / vn, "val/si_sdr": vsi / vn} if vn else {"val/sdr": float("nan"), "val/si_sdr": float("nan")}
+        vrec["val/metric"] = {"loss": -val, "si_sdr": vrec["val/si_sdr"], "sdr": vrec["val/sdr"]}[module.val_metric]
         if isinstance(gamma, _Plateau):
-            if vn:
-                ts.lr = gamma.step(val, ts.lr)
+            if vn:  # `val_metric: loss` steps on the loss itself, as before; sdr | si_sdr on val/metric (the reference's monitor, general_steps.py:259-271)
+                ts.lr = gamma.step(val if module.val_metric == "loss" else vrec["val/metric"], ts.lr)
         else:
             ts.lr *= gamma
         ts.check_replicas()  # every N steps (here: once per epoch): all ranks must still hold bitwise the same parameters and moments
-        rec = {"epoch": epoch, f"train/{module.loss.name}": tot / max(n, 1), f"val/{module.loss.name}": val, "lr": ts.lr, "steps": n,
+        rec = {"epoch": epoch, f"train/{module.loss.name}": tot / max(n, 1), f"val/{module.loss.name}": val, **vrec, "lr": ts.lr, "steps": n,
                "sec": time.time() - t0}
         log.append(rec)
         if rank == 0:
@@ -544,16 +554,81 @@ def _setup_generic(cfg: dict):
     return dev, module, data
 
 
+def _val_record(module: "TrainModule", name: str, loss: float, sdr: float, si_sdr: float) -> Dict[str, float]:
+    """what the reference's validation step logs besides the loss (:174-182)"""
+    rec = {f"{name}/sdr": sdr}
+    if module.loss.name != "neg_si_sdr":
+        rec[f"{name}/neg_si_sdr"] = -si_sdr
+    rec[f"{name}/metric"] = {"loss": -loss, "si_sdr": si_sdr, "sdr": sdr}[module.val_metric]
+    return rec
+
+
+class _TestMetrics:
+    """the reference's test step after the loss (:239-248, 268-273): the scale of a scale-invariant model's estimates is recovered from the mixture,
+    then every metric of `module.metrics` that the device pass serves, its input value and its improvement; means over the split and one row per
+    utterance"""
+
+    def __init__(self, module: "TrainModule"):
+        self.module, self.sums, self.rows, self.n = module, {}, [], 0
+
+    def add(self, yr_hat: Tensor, yr: Tensor, x_ref: Tensor, loss_items, paras) -> None:
+        """yr_hat / yr [B,S,N] (estimates in target order), x_ref [B,N]; loss_items: one loss per utterance"""
+        from models.utils.metrics import cal_metrics_functional, recover_scale
+        m = self.module
+        if m.loss.is_scale_invariant_loss:
+            yr_hat = recover_scale(preds=yr_hat, mixture=x_ref, scale_src_together=m.loss.name == "neg_sa_sdr", norm_if_exceed_1=False)
+        B = yr.shape[0]
+        fs = int(paras[0].get("sample_rate", 16000)) if paras and isinstance(paras[0], dict) else 16000
+        mix = x_ref[:, None].expand_as(yr).contiguous()
+        metrics, input_metrics, imp_metrics = cal_metrics_functional(m.metrics, yr_hat, yr, mix, fs, device_only="gpu", chunk=m.mchunk)
+        rows = [{"id": self.n + b, m.loss.name: float(loss_items[b])} for b in range(B)]
+        for d in (input_metrics, imp_metrics, metrics):
+            for k, v in d.items():
+                if "_all" in k:  # per utterance: one value per source
+                    for b in range(B):
+                        rows[b][k] = v[b]
+                else:
+                    self.sums[k] = self.sums.get(k, 0.0) + float(v) * B
+        for b in range(B):
+            if paras and isinstance(paras[b], dict):
+                rows[b]["paras"] = {k: v for k, v in paras[b].items() if isinstance(v, (int, float, str))}
+        self.rows += rows
+        self.n += B
+
+    def record(self) -> Dict[str, float]:
+        return {f"test/{k}": v / max(self.n, 1) for k, v in self.sums.items()}
+
+    def write(self, root: Optional[str]) -> None:
+        if root:
+            os.makedirs(root, exist_ok=True)
+            with open(os.path.join(root, "test_results.json"), "w") as f:
+                json.dump(self.rows, f, indent=1)
+
+
+def _loss_items(module: "TrainModule", yr_hat: Tensor, yr: Tensor, loss: float):
+    """one loss per utterance of estimates already in target order; cc_mse lives in the STFT domain: its rows carry the batch loss"""
+    if module.loss.name == "cc_mse":
+        return [loss] * yr.shape[0]
+    return module.loss.loss_func(yr_hat, yr, **module.loss.loss_func_kwargs).tolist()
+
+
 def _evaluate_generic(cfg: dict, stage: int) -> Dict[str, Any]:
     dev, module, data = _setup_generic(cfg)
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     tot, tot_in, n = 0.0, 0.0, 0
+    sdr_tot, si_tot, tm = 0.0, 0.0, _TestMetrics(module)
     with torch.no_grad():
-        for x, ys, _ in data.batches(stage, rank, world, 0):
+        for x, ys, paras in data.batches(stage, rank, world, 0):
             x, yr = x.to(dev), ys[:, :, module.ref_channel].to(dev).contiguous()
             yr_hat, loss_paras = module.forward(x)
-            loss, _, _ = module.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True, **loss_paras)
+            loss, perms, _ = module.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True, **loss_paras)
             tot, n = tot + float(loss), n + 1
+            yr_hat = _reordered(yr_hat.float(), perms)
+            if stage == 1:
+                sdr, si = val_metrics(yr_hat, yr)
+                sdr_tot, si_tot = sdr_tot + sdr, si_tot + si
+            else:
+                tm.add(yr_hat, yr, x[:, module.ref_channel].float().contiguous(), _loss_items(module, yr_hat, yr, float(loss)), paras)
             if module.loss.name != "cc_mse":  # the loss of the unprocessed mixture: a time-domain notion
                 mix = x[:, module.ref_channel][:, None].expand_as(yr).contiguous()
                 loss_in, _, _ = module.loss(yr_hat=mix, yr=yr, reorder=False, reduce_batch=True)
@@ -562,6 +637,12 @@ def _evaluate_generic(cfg: dict, stage: int) -> Dict[str, Any]:
     rec = {f"{name}/{module.loss.name}": tot / max(n, 1), "batches": n, "device": str(dev)}
     if module.loss.name != "cc_mse":
         rec[f"{name}/{module.loss.name.removeprefix('neg_')}_improvement_dB"] = (tot_in - tot) / max(n, 1)
+    if stage == 1:
+        rec.update(_val_record(module, name, tot / max(n, 1), sdr_tot / max(n, 1), si_tot / max(n, 1)))
+    else:
+        rec.update(tm.record())
+        if rank == 0:
+            tm.write(cfg.get("trainer", {}).get("default_root_dir"))
     if rank == 0:
         print(json.dumps(rec), flush=True)
     return rec
@@ -607,18 +688,29 @@ def _predict_generic(cfg: dict) -> Dict[str, Any]:
 
 def evaluate(cfg: dict, stage: int) -> Dict[str, Any]:
     """`validate` (stage 1) / `test` (stage 2): the configured uPIT loss (neg-SI-SDR as shipped) of the separated signals and its improvement over the
-    unprocessed reference-channel mixture, through the forward-only path (SharedTrainer.py:151-205 without the PESQ/STOI pools)."""
+    unprocessed reference-channel mixture, through the forward-only path (SharedTrainer.py:151-205 without the PESQ/STOI pools).  `validate` adds
+    val/sdr, val/neg_si_sdr (when the loss is another one) and val/metric (`val_metric`); `test` recovers the scale of a scale-invariant model's
+    estimates and adds test/<m>, test/input_<m>, test/<m>_i for the metrics of `model.metrics` that the device pass serves (SDR, SI_SDR, SI_SNR, SNR),
+    and writes one row per utterance to <trainer.default_root_dir>/test_results.json (reference :221-273)."""
     if not _is_fused_arch(cfg):
         return _evaluate_generic(cfg, stage)
     from nbss_amd import ops
     dev, module, data, ts = _setup(cfg)
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     tot, tot_in, n = 0.0, 0.0, 0
-    for x, ys, _ in data.batches(stage, rank, world, 0):
+    sdr_tot, si_tot, tm = 0.0, 0.0, _TestMetrics(module)
+    for x, ys, paras in data.batches(stage, rank, world, 0):
         xs = x[:, module.channels].to(dev).contiguous()
         yr = ys[:, :, module.ref_channel].to(dev).contiguous()
-        loss, yr_hat, _, _, _ = ts.forward_loss(xs, yr, need_grad=False)
-        mix = xs[:, module.channels.index(module.ref_channel)][:, None].expand_as(yr).contiguous()
+        loss, yr_hat, _, _, perm = ts.forward_loss(xs, yr, need_grad=False)
+        x_ref = xs[:, module.channels.index(module.ref_channel)].contiguous()
+        mix = x_ref[:, None].expand_as(yr).contiguous()
+        yr_hat = _reordered(yr_hat, perm)
+        if stage == 1:
+            sdr, si = val_metrics(yr_hat, yr)
+            sdr_tot, si_tot = sdr_tot + sdr, si_tot + si
+        else:
+            tm.add(yr_hat, yr, x_ref, _loss_items(module, yr_hat, yr, float(loss)), paras)
         if ts.loss == "neg_si_sdr":
             loss_in, _, _ = ops.pit_neg_sisdr(ts.lib, mix, yr, need_grad=False)
         else:
@@ -630,6 +722,12 @@ def evaluate(cfg: dict, stage: int) -> Dict[str, Any]:
     name = "val" if stage == 1 else "test"
     lname = module.loss.name
     rec = {f"{name}/{lname}": tot / max(n, 1), f"{name}/{lname.removeprefix('neg_')}_improvement_dB": (tot_in - tot) / max(n, 1), "batches": n}
+    if stage == 1:
+        rec.update(_val_record(module, name, tot / max(n, 1), sdr_tot / max(n, 1), si_tot / max(n, 1)))
+    else:
+        rec.update(tm.record())
+        if rank == 0:
+            tm.write(cfg.get("trainer", {}).get("default_root_dir"))
     if rank == 0:
         print(json.dumps(rec), flush=True)
     return rec

@@ -201,6 +201,39 @@ int64_t nbss_pit_loss_ws_bytes(int kind, int B, int S);
 int nbss_pit_loss(int kind, int flags, int B, int S, int N, const float* preds, const float* target, float* loss, int32_t* perm, float* dpreds,
                   float* ws, void* stream);
 
+/* ---- evaluation metrics (csrc/metrics.hip) -------------------------------------------------------------------------------------------------
+ * What the reference's validation and test steps compute on the device (SharedTrainer.py:163-182,239-248 through
+ * models/utils/metrics.py:14-151: torchmetrics signal_noise_ratio, scale_invariant_signal_distortion_ratio, scale_invariant_signal_noise_ratio,
+ * signal_distortion_ratio) and its recover_scale (models/utils/metrics.py:192-218).  preds / target [B,S,N] fp32, estimate s paired with target s;
+ * S <= 4, B <= 1024 (NBSS_EUNSUPPORTED beyond).  Every sum is accumulated in fp64 in a fixed order, no atomics: two calls give the same bits.
+ *
+ * nbss_signal_ratios: out [B][S][3] fp32 = SNR, SI-SDR, SI-SNR in dB, one pass over the signals; eps = float32 epsilon:
+ *   SNR    10 log10((|t|^2 + eps) / (|t - p|^2 + eps)), the distortion accumulated element by element          (metrics.py:79-81)
+ *   SI-SDR alpha = (<p,t> + eps) / (|t|^2 + eps); 10 log10((|alpha t|^2 + eps) / (|alpha t - p|^2 + eps))       (metrics.py:73-75)
+ *   SI-SNR SI-SDR of the two signals minus their means                                                         (metrics.py:76-78)
+ * ws: nbss_signal_ratios_ws_bytes() bytes. */
+int64_t nbss_signal_ratios_ws_bytes(int B, int S);
+int nbss_signal_ratios(int B, int S, int N, const float* preds, const float* target, float* out, void* ws, void* stream);
+/* nbss_sdr: torchmetrics signal_distortion_ratio(preds, target, filter_length, zero_mean) (metrics.py:66-69; SharedTrainer.py:167: `sdr`), BSS-eval
+ * with a distortion filter of filter_length taps, fp64 from the first step on: t / max(|t|, 1e-6), p / max(|p|, 1e-6); r[k] = sum_n t[n] t[n+k],
+ * b[k] = sum_n t[n] p[n+k] (linear correlations, k < filter_length); Toeplitz(r) x = b by Levinson-Durbin; coh = <b, x>;
+ * sdr [B][S] fp32 = 10 log10(coh / (1 - coh)).  flags: NBSS_SDR_ZERO_MEAN subtracts each signal's mean first (torchmetrics' default is off).
+ * 1 <= filter_length <= 512 (torchmetrics' default) and N >= filter_length, else NBSS_EUNSUPPORTED.  A silent target or estimate gives NaN, as it does there.
+ * ws: nbss_sdr_ws_bytes() bytes. */
+#define NBSS_SDR_ZERO_MEAN 1
+int64_t nbss_sdr_ws_bytes(int B, int S, int N, int filter_length);
+int nbss_sdr(int B, int S, int N, int filter_length, int flags, const float* preds, const float* target, float* sdr, void* ws, void* stream);
+/* nbss_recover_scale: recover_scale(preds, mixture, scale_src_together, norm_if_exceed_1) (metrics.py:192-218; SharedTrainer.py:239-242): preds
+ * [B,S,N], mixture [B,N] -> out [B,S,N] = a_s preds_s with the least-squares scales a [S] of min |sum_s a_s p_s - x| per utterance, from the normal
+ * equations (S x S Gram matrix and right-hand side accumulated and solved in fp64); NBSS_SCALE_TOGETHER: one scale for sum_s p_s.
+ * NBSS_SCALE_NORM_IF_EXCEED_1: a source whose scaled maximum magnitude exceeds 1 is divided by it.  The result is defined only when the Gram matrix
+ * is non-singular (linearly independent estimates; with NBSS_SCALE_TOGETHER: a non-zero sum) — otherwise it is inf / NaN, no error is raised.
+ * out may not alias preds.  ws: nbss_recover_scale_ws_bytes() bytes; its last B S doubles hold the applied scales after the call. */
+#define NBSS_SCALE_TOGETHER 1
+#define NBSS_SCALE_NORM_IF_EXCEED_1 2
+int64_t nbss_recover_scale_ws_bytes(int B, int S);
+int nbss_recover_scale(int B, int S, int N, int flags, const float* preds, const float* mixture, float* out, void* ws, void* stream);
+
 /* clip_grad_norm_(max_norm, L2) + torch.optim.Adam(W) step on the flat fp32 buffers
  * (configs/SpatialNet.yaml:3-4,44; general_steps.py:243-271).  grads are first multiplied by
  * grad_scale (1/world_size after a SUM all-reduce).  scratch: >= 258 floats; scratch[0] returns the

@@ -14,6 +14,9 @@ NBSS_F32, NBSS_BF16 = 0, 1
 # nbss_pit_loss: kind, flags (include/nbss_hip.h)
 NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR, NBSS_LOSS_SA_SDR, NBSS_LOSS_MSE = 0, 1, 2, 3
 NBSS_LOSS_PIT, NBSS_LOSS_SCALE_INVARIANT = 1, 2
+# nbss_sdr / nbss_recover_scale: flags
+NBSS_SDR_ZERO_MEAN = 1
+NBSS_SCALE_TOGETHER, NBSS_SCALE_NORM_IF_EXCEED_1 = 1, 2
 # nbss_online_stft_step / nbss_online_istft_step: norm
 NBSS_ONLINE_NORM_NONE, NBSS_ONLINE_NORM_FREQUENCY, NBSS_ONLINE_NORM_UTTERANCE = 0, 1, 2
 
@@ -80,6 +83,12 @@ SIGNATURES = {
     "nbss_pit_neg_sisdr": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "nbss_pit_loss_ws_bytes": (C.c_int64, [_I, _I, _I]),
     "nbss_pit_loss": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "nbss_signal_ratios_ws_bytes": (C.c_int64, [_I, _I]),
+    "nbss_signal_ratios": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "nbss_sdr_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),
+    "nbss_sdr": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "nbss_recover_scale_ws_bytes": (C.c_int64, [_I, _I]),
+    "nbss_recover_scale": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nbss_online_encoder_step": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "nbss_online_ret_step": (_I, [_I, _I] + [_P] * 12),
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),

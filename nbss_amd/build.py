@@ -40,6 +40,8 @@ _SCHED = lambda s: ["-mllvm", f"-amdgpu-sched-strategy={s}"]
 PER_FILE_FLAGS["full"] = _SCHED("iterative-minreg")
 PER_FILE_FLAGS["mhsa_bwd"] = PER_FILE_FLAGS["mhsa_bwd"] + _SCHED("iterative-minreg")
 PER_FILE_FLAGS["tailw"] = _SCHED("max-ilp")
+# metrics.hip is fp64 arithmetic pinned to 1e-4 dB against an fp64 restatement: no reassociation, exact division and square root
+PER_FILE_FLAGS["metrics"] = ["-fno-fast-math"]
 
 
 def _sources():

@@ -39,6 +39,12 @@ int pit_sisdr_impl(int B, int S, int N, const float* p, const float* t, float* l
 size_t pit_loss_ws_floats(int kind, int B, int S);
 int pit_loss_impl(int kind, int flags, int B, int S, int N, const float* p, const float* t, float* loss, int* perm, float* dp, float* ws,
                   hipStream_t st);
+size_t signal_ratios_ws_bytes_impl(int B, int S);
+int signal_ratios_impl(int B, int S, int N, const float* p, const float* t, float* out, void* ws, hipStream_t st);
+size_t sdr_ws_bytes_impl(int B, int S, int N, int L);
+int sdr_impl(int B, int S, int N, int L, int flags, const float* p, const float* t, float* sdr, void* ws, hipStream_t st);
+size_t recover_scale_ws_bytes_impl(int B, int S);
+int recover_scale_impl(int B, int S, int N, int flags, const float* p, const float* x, float* out, void* ws, hipStream_t st);
 int clip_adam_dev_impl(size_t n, float* p, float* g, float* m, float* v, float* scal, const float* hyper, float max_norm, float grad_scale, float beta1,
                        float beta2, float eps, float wd, int flags, hipStream_t st);
 int adam_hyper_impl(int step, float lr, float beta1, float beta2, float* out);
@@ -461,6 +467,36 @@ int nbss_pit_loss(int kind, int flags, int B, int S, int N, const float* preds, 
                   float* ws, void* stream) {
     if (!preds || !target || !loss || !perm || !ws || N <= 0) return NBSS_EINVAL;
     return pit_loss_impl(kind, flags, B, S, N, preds, target, loss, perm, dpreds, ws, (hipStream_t)stream);
+}
+
+int64_t nbss_signal_ratios_ws_bytes(int B, int S) {
+    if (B <= 0 || S <= 0) return -1;
+    return (int64_t)signal_ratios_ws_bytes_impl(B, S);
+}
+
+int nbss_signal_ratios(int B, int S, int N, const float* preds, const float* target, float* out, void* ws, void* stream) {
+    if (!preds || !target || !out || !ws) return NBSS_EINVAL;
+    return signal_ratios_impl(B, S, N, preds, target, out, ws, (hipStream_t)stream);
+}
+
+int64_t nbss_sdr_ws_bytes(int B, int S, int N, int filter_length) {
+    if (B <= 0 || S <= 0 || N <= 0 || filter_length <= 0) return -1;
+    return (int64_t)sdr_ws_bytes_impl(B, S, N, filter_length);
+}
+
+int nbss_sdr(int B, int S, int N, int filter_length, int flags, const float* preds, const float* target, float* sdr, void* ws, void* stream) {
+    if (!preds || !target || !sdr || !ws) return NBSS_EINVAL;
+    return sdr_impl(B, S, N, filter_length, flags, preds, target, sdr, ws, (hipStream_t)stream);
+}
+
+int64_t nbss_recover_scale_ws_bytes(int B, int S) {
+    if (B <= 0 || S <= 0) return -1;
+    return (int64_t)recover_scale_ws_bytes_impl(B, S);
+}
+
+int nbss_recover_scale(int B, int S, int N, int flags, const float* preds, const float* mixture, float* out, void* ws, void* stream) {
+    if (!preds || !mixture || !out || !ws) return NBSS_EINVAL;
+    return recover_scale_impl(B, S, N, flags, preds, mixture, out, ws, (hipStream_t)stream);
 }
 
 int nbss_clip_adam_step(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* scratch, float max_norm,

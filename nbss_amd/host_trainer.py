@@ -17,6 +17,7 @@ import torch
 
 def fit_generic(cfg: dict, build_module, instantiate) -> Dict[str, Any]:
     from models.arch.SpatialNet import SpatialNet
+    from models.utils.metrics import pit_reorder as _reordered, val_metrics
     tr = cfg.get("trainer", {})
     use_gpu = tr.get("accelerator", "gpu") != "cpu" and torch.cuda.is_available()
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0))) if use_gpu else torch.device("cpu")
@@ -79,15 +80,21 @@ def fit_generic(cfg: dict, build_module, instantiate) -> Dict[str, Any]:
             n += 1
             step += 1
         module.eval()
-        vtot, vn = 0.0, 0
+        vtot, vn, vsdr, vsi = 0.0, 0, 0.0, 0.0
         with torch.no_grad():
             for x, ys, paras in data.batches(1, 0, 1, 0):
-                vtot += float(module.training_step((x.to(dev), ys.to(dev), paras)))
-                vn += 1
+                # the reference's validation step (SharedTrainer.py:151-182): the loss, then SDR and SI-SDR of the estimates in target order
+                x, yr = x.to(dev), ys[:, :, module.ref_channel].to(dev).contiguous()
+                yr_hat, loss_paras = module.forward(x)
+                loss, perms, _ = module.loss(yr_hat=yr_hat, yr=yr, reorder=False, reduce_batch=True, **loss_paras)
+                sdr, si = val_metrics(_reordered(yr_hat.float(), perms), yr)
+                vtot, vn, vsdr, vsi = vtot + float(loss), vn + 1, vsdr + sdr, vsi + si
         val = vtot / max(vn, 1)
-        if sched is not None:
-            sched.step(val) if plateau else sched.step()
-        rec = {"epoch": epoch, f"train/{module.loss.name}": tot / max(n, 1), f"val/{module.loss.name}": val, "steps": n, "lr": opt.param_groups[0]["lr"],
+        vrec = {"val/sdr": vsdr / max(vn, 1), "val/si_sdr": vsi / max(vn, 1)}
+        vrec["val/metric"] = {"loss": -val, "si_sdr": vrec["val/si_sdr"], "sdr": vrec["val/sdr"]}[module.val_metric]
+        if sched is not None:  # `val_metric: loss` steps a plateau scheduler on the loss itself; sdr | si_sdr on val/metric (the reference's monitor)
+            sched.step(val if module.val_metric == "loss" else vrec["val/metric"]) if plateau else sched.step()
+        rec = {"epoch": epoch, f"train/{module.loss.name}": tot / max(n, 1), f"val/{module.loss.name}": val, **vrec, "steps": n, "lr": opt.param_groups[0]["lr"],
                "sec": time.time() - t0, "device": str(dev)}
         log.append(rec)
         if rank == 0:

@@ -12,8 +12,8 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
-from ._lib import (NBSS_BF16, NBSS_F32, NBSS_LOSS_MSE, NBSS_LOSS_PIT, NBSS_LOSS_SA_SDR, NBSS_LOSS_SCALE_INVARIANT, NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR, Cfg,
-                   Lib, NbssError)
+from ._lib import (NBSS_BF16, NBSS_F32, NBSS_LOSS_MSE, NBSS_LOSS_PIT, NBSS_LOSS_SA_SDR, NBSS_LOSS_SCALE_INVARIANT, NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR,
+                   NBSS_SCALE_NORM_IF_EXCEED_1, NBSS_SCALE_TOGETHER, NBSS_SDR_ZERO_MEAN, Cfg, Lib, NbssError)
 from .params import param_table
 
 
@@ -278,6 +278,57 @@ def pit_loss(lib, kind, preds, target, pit=True, scale_invariant=False, need_gra
     if return_items:  # workspace tail (include/nbss_hip.h): ... | per-item loss [B] | pairing coefficients [3 B S]
         return loss, perm, dp, ws[ws.numel() - B - 3 * B * S: ws.numel() - 3 * B * S].clone()
     return loss, perm, dp
+
+
+def _metric_pair(what, preds, target):
+    if preds.dim() != 3 or target.shape != preds.shape:
+        raise NbssError(f"{what}: preds {tuple(preds.shape)} and target {tuple(target.shape)} must be the same [B,S,N]")
+    return preds.shape
+
+
+def signal_ratios(lib, preds, target, ws=None):
+    """preds / target [B,S,N] fp32, estimate s paired with target s -> [B,S,3] fp32: SNR, SI-SDR, SI-SNR in dB (nbss_signal_ratios)"""
+    B, S, N = _metric_pair("signal_ratios", preds, target)
+    if ws is None:
+        nws = lib.nbss_signal_ratios_ws_bytes(B, S)
+        if nws <= 0:
+            raise NbssError(f"nbss_signal_ratios_ws_bytes(B={B}, S={S}): empty batch")
+        ws = scratch(nws, preds.device)
+    out = torch.empty(B, S, 3, dtype=torch.float32, device=preds.device)
+    lib.call("nbss_signal_ratios", B, S, N, _ptr(lib, preds, torch.float32), _ptr(lib, target, torch.float32), _ptr(lib, out), _ptr(lib, ws, torch.uint8),
+             _stream(lib, preds))
+    return out
+
+
+def sdr(lib, preds, target, filter_length: int = 512, zero_mean: bool = False, ws=None):
+    """torchmetrics' signal_distortion_ratio of every (estimate s, target s): preds / target [B,S,N] fp32 -> [B,S] fp32 in dB (nbss_sdr)"""
+    B, S, N = _metric_pair("sdr", preds, target)
+    if ws is None:
+        nws = lib.nbss_sdr_ws_bytes(B, S, N, int(filter_length))
+        if nws <= 0:
+            raise NbssError(f"nbss_sdr_ws_bytes(B={B}, S={S}, N={N}, filter_length={filter_length}): every size must be positive")
+        ws = scratch(nws, preds.device)
+    out = torch.empty(B, S, dtype=torch.float32, device=preds.device)
+    lib.call("nbss_sdr", B, S, N, int(filter_length), NBSS_SDR_ZERO_MEAN if zero_mean else 0, _ptr(lib, preds, torch.float32), _ptr(lib, target, torch.float32),
+             _ptr(lib, out), _ptr(lib, ws, torch.uint8), _stream(lib, preds))
+    return out
+
+
+def recover_scale(lib, preds, mixture, scale_src_together: bool, norm_if_exceed_1: bool = True, ws=None):
+    """preds [B,S,N], mixture [B,N] fp32 -> preds times the least-squares scales that explain the mixture (nbss_recover_scale)"""
+    if preds.dim() != 3 or mixture.shape != (preds.shape[0], preds.shape[2]):
+        raise NbssError(f"recover_scale: preds {tuple(preds.shape)} must be [B,S,N] and mixture {tuple(mixture.shape)} [B,N]")
+    B, S, N = preds.shape
+    if ws is None:
+        nws = lib.nbss_recover_scale_ws_bytes(B, S)
+        if nws <= 0:
+            raise NbssError(f"nbss_recover_scale_ws_bytes(B={B}, S={S}): empty batch")
+        ws = scratch(nws, preds.device)
+    out = torch.empty_like(preds)
+    flags = (NBSS_SCALE_TOGETHER if scale_src_together else 0) | (NBSS_SCALE_NORM_IF_EXCEED_1 if norm_if_exceed_1 else 0)
+    lib.call("nbss_recover_scale", B, S, N, flags, _ptr(lib, preds, torch.float32), _ptr(lib, mixture, torch.float32), _ptr(lib, out),
+             _ptr(lib, ws, torch.uint8), _stream(lib, preds))
+    return out
 
 
 def clip_adam_step(lib, params, grads, exp_avg, exp_avg_sq, scratch, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
