@@ -8,7 +8,8 @@ following data_loaders/sms_wsj_plus.py:157-220, utils/mix.py:122-134 (convolve),
 noises).  Everything is torch (hipFFT / rocSOLVER through torch-ROCm) and device-agnostic: the CPU tests check it against
 scipy and, when the reference tree is present, against the reference's own functions.
 The corpora (WSJ0, measured/simulated RIR sets) are not available here: `SimulatedRoomDataModule` draws band-limited random
-sources and synthetic exponentially decaying RIRs; `mix_batch` itself takes any sources / RIRs."""
+sources and, by default, synthetic exponentially decaying RIRs; with rir='ism' it draws shoebox rooms and computes their impulse
+responses by the image-source method on the device (nbss_amd/rir.py: simulate_rir).  `mix_batch` itself takes any sources / RIRs."""
 import math
 from typing import Dict, List, Optional, Tuple
 
@@ -122,7 +123,11 @@ class SimulatedRoomDataModule:
     def __init__(self, batch_size: List[int] = (2, 2), num_samples: List[int] = (64, 8, 8), audio_time_len: List[float] = (4.0, 4.0, 4.0),
                  num_channels: int = 6, num_speakers: int = 2, sample_rate: int = 8000, sir: Tuple[float, float] = (-5.0, 5.0),
                  snr: Tuple[float, float] = (0.0, 20.0), rt60: Tuple[float, float] = (0.2, 0.6), array_radius: float = 0.1, seeds: List[int] = (0, 1, 2),
-                 device: Optional[str] = None):
+                 device: Optional[str] = None, rir: str = 'synthetic', room_size_lims: Tuple[Tuple[float, float], ...] = ((3.0, 8.0), (3.0, 8.0), (3.0, 4.0)),
+                 mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8)):
+        if rir not in ('synthetic', 'ism'):
+            raise ValueError(f"rir must be 'synthetic' or 'ism', got {rir!r}")
+        self.rir, self.room_size_lims, self.mic_zlim, self.spk_zlim = rir, [tuple(l) for l in room_size_lims], tuple(mic_zlim), tuple(spk_zlim)
         self.batch_size, self.num_samples, self.audio_time_len = list(batch_size), list(num_samples), list(audio_time_len)
         self.C, self.S, self.sr, self.sir, self.snr, self.rt60, self.seeds = num_channels, num_speakers, sample_rate, sir, snr, rt60, list(seeds)
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
@@ -142,6 +147,40 @@ class SimulatedRoomDataModule:
         tail.masked_fill_(torch.arange(L, device=dev)[None, None, None, :] < delay[..., None], 0.0)
         return tail.scatter(-1, delay[..., None], 1.0)
 
+    def _ism_scene(self, B: int, gen: torch.Generator) -> Dict[str, Tensor]:
+        """B shoebox rooms drawn from `gen` (fp64, on the device): room size, RT60 (redrawn while Sabine's formula cannot reach it in that room:
+        RT60 < 0.161 V / S), wall coefficients, the array (centre at least 0.5 m from the side walls, height in mic_zlim, rotated about z) and the
+        speakers (at least 0.3 m from the side walls, height in spk_zlim), and what follows from them: image counts down to 60 dB of decay and the
+        RIR length int((max RT60 + 0.1) fs)"""
+        from nbss_amd.rir import att2t, beta_sabine, rotate_z, t2n
+        dev = self.device
+        u = lambda *shape: torch.rand(*shape, generator=gen, device=dev, dtype=torch.float64)
+        lims = torch.tensor(self.room_size_lims, dtype=torch.float64, device=dev)  # [3,2]
+        room = lims[:, 0] + (lims[:, 1] - lims[:, 0]) * u(B, 3)
+        floor = 0.161 * room.prod(-1) / (2.0 * (room[:, 0] * room[:, 1] + room[:, 0] * room[:, 2] + room[:, 1] * room[:, 2]))
+        rt = self.rt60[0] + (self.rt60[1] - self.rt60[0]) * u(B)
+        for _ in range(16):
+            again = self.rt60[0] + (self.rt60[1] - self.rt60[0]) * u(B)  # drawn every time: the stream of draws does not depend on the rooms
+            rt = torch.where(rt < floor, again, rt)
+        rt = torch.maximum(rt, floor)  # a room whose floor lies above the whole RT60 range keeps its shortest reachable RT60
+        beta = beta_sabine(room, rt)[0]
+        xy = lambda margin, *shape: margin + (room[:, None, :2] - 2.0 * margin) * u(*shape)
+        z = lambda lim, *shape: lim[0] + (lim[1] - lim[0]) * u(*shape)
+        centre = torch.cat([xy(0.5, B, 1, 2), z(self.mic_zlim, B, 1, 1)], -1)  # [B,1,3]
+        pos_rcv = centre + rotate_z(self.pos_mics.to(dev).double().expand(B, self.C, 3), 2.0 * math.pi * u(B))
+        pos_src = torch.cat([xy(0.3, B, self.S, 2), z(self.spk_zlim, B, self.S, 1)], -1)
+        return {"room_sz": room, "rt60": rt, "beta": beta, "pos_rcv": pos_rcv, "pos_src": pos_src,
+                "nb_img": t2n(att2t(60.0, rt), room).cpu(), "n_samples": int((float(rt.max()) + 0.1) * self.sr)}
+
+    def _ism_rirs(self, B: int, gen: torch.Generator) -> Tuple[Tensor, Tensor]:
+        """(reverberant, direct-path) RIRs [B,S,M,L] of B rooms drawn from `gen`: one simulate_rir call each"""
+        from nbss_amd.rir import simulate_rir
+        sc = self._ism_scene(B, gen)
+        geo = (sc["room_sz"], sc["beta"], sc["pos_src"], sc["pos_rcv"])
+        rir = simulate_rir(*geo, sc["nb_img"], sc["n_samples"], self.sr)
+        rir_dp = simulate_rir(geo[0], torch.zeros_like(geo[1]), geo[2], geo[3], (1, 1, 1), sc["n_samples"], self.sr)
+        return rir.float(), rir_dp.float()
+
     def batches(self, stage: int, rank: int = 0, world: int = 1, epoch: int = 0):
         N = int(self.audio_time_len[stage] * self.sr)
         bs = self.batch_size[min(stage, len(self.batch_size) - 1)]
@@ -154,6 +193,10 @@ class SimulatedRoomDataModule:
             src = torch.nn.functional.conv1d(src, (k / k.sum())[None, None], padding=16).reshape(bs, self.S, N) * 3.0
             sir = self.sir[0] + (self.sir[1] - self.sir[0]) * torch.rand(bs, generator=gen, device=self.device)
             snr = self.snr[0] + (self.snr[1] - self.snr[0]) * torch.rand(bs, generator=gen, device=self.device)
-            mix, tgt, paras = mix_batch(src, self._rirs(bs, gen), self.Cs, sir if self.S == 2 else None, snr, gen)
+            if self.rir == 'ism':  # the targets are the direct-path images
+                rir, rir_dp = self._ism_rirs(bs, gen)
+                mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp)
+            else:
+                mix, tgt, paras = mix_batch(src, self._rirs(bs, gen), self.Cs, sir if self.S == 2 else None, snr, gen)
             yield mix, tgt, [{"index": ix, "seed": sd, "sample_rate": self.sr, "snr": float(paras["snr"][j]), "sir": float(sir[j])}
                              for j, (ix, sd) in enumerate(chunk)]

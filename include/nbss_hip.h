@@ -234,6 +234,35 @@ int nbss_sdr(int B, int S, int N, int filter_length, int flags, const float* pre
 int64_t nbss_recover_scale_ws_bytes(int B, int S);
 int nbss_recover_scale(int B, int S, int N, int flags, const float* preds, const float* mixture, float* out, void* ws, void* stream);
 
+/* ---- Room impulse responses by the image-source method (csrc/rir.hip; nbss_amd/rir.py: simulate_rir) -----------------------------------------
+ * What the reference's generate_rirs.py takes from gpuRIR (a CUDA-only package; parity with it is not pinned, this comment is the definition):
+ * Allen & Berkley's image sources of a shoebox room with the Hann-windowed sinc of fractional delay.  Per room b of the batch:
+ *   room_sz [B][3], beta [B][6] = (x0, x1, y0, y1, z0, z1) wall reflection coefficients, pos_src [B][S][3], pos_rcv [B][M][3]: fp64 DEVICE arrays;
+ *   nb_img [B][3] = (Nx, Ny, Nz): int32 HOST array, read before the call returns.
+ * Along axis a the image index is n = i - floor(N_a / 2), i = 0 .. N_a - 1; the image coordinate is n L_a + s_a (n even) or (n + 1) L_a - s_a (n odd);
+ * wall 0 reflects floor(n / 2) times for n >= 0 and ceil(|n| / 2) times for n < 0, wall 1 ceil(n / 2) resp. floor(|n| / 2) times.
+ *   A = prod_a beta_a0^r_a0 beta_a1^r_a1 / (4 pi d)   (0^0 = 1),  d = max(|image - receiver|, 1e-3 m),  x = fs d / c
+ *   h[b][s][m][k] = sum_images A w(k - x),   w(u) = 0.5 (1 + cos(2 pi u / (tw fs))) sinc(u) for |u| < tw fs / 2, else 0
+ * Position, distance, x and its split into integer and fraction are fp64, the window fp32, the sum over the images fp64 in an order fixed by the
+ * room, (s, m) and k alone: two calls give the same bits and a room's response does not depend on the other rooms of the batch.  No atomics.
+ * h [B][S][M][n_samples] fp32: every element is written exactly once.
+ * k_d > 0: only images with x < k_d + round(tw fs) / 2 are summed (the early part in front of nbss_rir_tail); k_d = 0: all of them.
+ * Limits (NBSS_EUNSUPPORTED outside): 1 <= N_a <= 512; 1 <= n_samples <= 65536; 2 <= tw fs and tw fs + 1 <= 257; B, S, M >= 1 (B, S M <= 65535);
+ * with k_d > 0: round(tw fs) <= k_d < n_samples.
+ * ws: nbss_rir_ism_ws_bytes() bytes (exact: B headers and one fp64 wall factor per room, axis and image index; NBSS_EINVAL when ws_bytes is less;
+ * the count is negative when an N_a is outside its limits). */
+int64_t nbss_rir_ism_ws_bytes(int B, const int32_t* nb_img);
+int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
+                 const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, void* stream);
+/* The diffuse tail behind nbss_rir_ism(k_d > 0), this project's own definition: with K = round(tw fs), g^2 = mean_{k_d - K <= k < k_d} h[b][s][m][k]^2
+ * (fp64, index order), for k >= k_d
+ *   h[b][s][m][k] = g 10^(-3 (k - k_d) / (fs rt60[b])) xi(seed, b, s, m, k)
+ * xi: z(v) = splitmix64 step (v += 0x9E3779B97F4A7C15; v = (v ^ v >> 30) 0xBF58476D1CE4E5B9; v = (v ^ v >> 27) 0x94D049BB133111EB; v ^ v >> 31),
+ * key = z(z(z(seed + b) + s) + m), h1 = z(key + k), h2 = z(h1), u1 = ((h1 >> 41) + 1) / 2^23, u2 = (h2 >> 40) / 2^24,
+ * xi = sqrt(-2 ln u1) cos(2 pi u2), evaluated in fp64: the tail does not depend on the launch geometry.  rt60 [B] fp64 device array.
+ * Same limits as nbss_rir_ism with k_d > 0. */
+int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream);
+
 /* clip_grad_norm_(max_norm, L2) + torch.optim.Adam(W) step on the flat fp32 buffers
  * (configs/SpatialNet.yaml:3-4,44; general_steps.py:243-271).  grads are first multiplied by
  * grad_scale (1/world_size after a SUM all-reduce).  scratch: >= 258 floats; scratch[0] returns the

@@ -42,6 +42,8 @@ PER_FILE_FLAGS["mhsa_bwd"] = PER_FILE_FLAGS["mhsa_bwd"] + _SCHED("iterative-minr
 PER_FILE_FLAGS["tailw"] = _SCHED("max-ilp")
 # metrics.hip is fp64 arithmetic pinned to 1e-4 dB against an fp64 restatement: no reassociation, exact division and square root
 PER_FILE_FLAGS["metrics"] = ["-fno-fast-math"]
+# rir.hip splits a delay of up to 65 536 samples into integer and fraction in fp64 and is held to a few fp32 ulp per image: accurate sinf / cosf, no reassociation
+PER_FILE_FLAGS["rir"] = ["-fno-fast-math"]
 
 
 def _sources():

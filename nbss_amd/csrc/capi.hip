@@ -45,6 +45,10 @@ size_t sdr_ws_bytes_impl(int B, int S, int N, int L);
 int sdr_impl(int B, int S, int N, int L, int flags, const float* p, const float* t, float* sdr, void* ws, hipStream_t st);
 size_t recover_scale_ws_bytes_impl(int B, int S);
 int recover_scale_impl(int B, int S, int N, int flags, const float* p, const float* x, float* out, void* ws, hipStream_t st);
+int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img);
+int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
+                 const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
+int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, hipStream_t st);
 int clip_adam_dev_impl(size_t n, float* p, float* g, float* m, float* v, float* scal, const float* hyper, float max_norm, float grad_scale, float beta1,
                        float beta2, float eps, float wd, int flags, hipStream_t st);
 int adam_hyper_impl(int step, float lr, float beta1, float beta2, float* out);
@@ -497,6 +501,23 @@ int64_t nbss_recover_scale_ws_bytes(int B, int S) {
 int nbss_recover_scale(int B, int S, int N, int flags, const float* preds, const float* mixture, float* out, void* ws, void* stream) {
     if (!preds || !mixture || !out || !ws) return NBSS_EINVAL;
     return recover_scale_impl(B, S, N, flags, preds, mixture, out, ws, (hipStream_t)stream);
+}
+
+int64_t nbss_rir_ism_ws_bytes(int B, const int32_t* nb_img) {
+    if (!nb_img) return NBSS_EINVAL;
+    if (B < 1) return NBSS_EUNSUPPORTED;
+    return rir_ism_ws_bytes_impl(B, nb_img);
+}
+
+int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
+                 const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, void* stream) {
+    if (!room_sz || !beta || !pos_src || !pos_rcv || !nb_img || !h || !ws) return NBSS_EINVAL;
+    return rir_ism_impl(B, S, M, n_samples, fs, c, tw, k_d, room_sz, beta, pos_src, pos_rcv, nb_img, h, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream) {
+    if (!rt60 || !h) return NBSS_EINVAL;
+    return rir_tail_impl(B, S, M, n_samples, fs, tw, k_d, rt60, seed, h, (hipStream_t)stream);
 }
 
 int nbss_clip_adam_step(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* scratch, float max_norm,

@@ -6,6 +6,7 @@ sources on CPU tensors.  There is no other code path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional
 
@@ -13,7 +14,7 @@ import torch
 from torch import Tensor
 
 from ._lib import (NBSS_BF16, NBSS_F32, NBSS_LOSS_MSE, NBSS_LOSS_PIT, NBSS_LOSS_SA_SDR, NBSS_LOSS_SCALE_INVARIANT, NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR,
-                   NBSS_SCALE_NORM_IF_EXCEED_1, NBSS_SCALE_TOGETHER, NBSS_SDR_ZERO_MEAN, Cfg, Lib, NbssError)
+                   NBSS_SCALE_NORM_IF_EXCEED_1, NBSS_SCALE_TOGETHER, NBSS_SDR_ZERO_MEAN, _ERR, Cfg, Lib, NbssError)
 from .params import param_table
 
 
@@ -329,6 +330,50 @@ def recover_scale(lib, preds, mixture, scale_src_together: bool, norm_if_exceed_
     lib.call("nbss_recover_scale", B, S, N, flags, _ptr(lib, preds, torch.float32), _ptr(lib, mixture, torch.float32), _ptr(lib, out),
              _ptr(lib, ws, torch.uint8), _stream(lib, preds))
     return out
+
+
+def rir_tail_start(t_diff: float, fs: float) -> int:
+    """k_d = ceil(t_diff fs): the first sample of the diffuse tail (include/nbss_hip.h: nbss_rir_tail)"""
+    return int(math.ceil(float(t_diff) * float(fs) - 1e-9))
+
+
+def rir_ism(lib, room_sz, beta, pos_src, pos_rcv, nb_img, n_samples: int, fs: float, c: float = 343.0, tw: float = 8e-3, t_diff: Optional[float] = None,
+            rt60=None, seed: int = 0, ws=None, out=None):
+    """image-source room impulse responses of a batch of rooms (nbss_rir_ism, with t_diff also nbss_rir_tail): room_sz [B,3], beta [B,6],
+    pos_src [B,S,3], pos_rcv [B,M,3] (any float dtype: the kernel takes fp64), nb_img (Nx, Ny, Nz) shared or [B,3] per room (host integers)
+    -> h [B,S,M,n_samples] fp32.  t_diff (seconds, with rt60 [B] or a number) switches to the diffuse tail from sample ceil(t_diff fs) on."""
+    dev = room_sz.device
+    f64 = lambda t: t.detach().to(device=dev, dtype=torch.float64).contiguous()
+    room_sz, beta, pos_src, pos_rcv = f64(room_sz), f64(beta), f64(pos_src), f64(pos_rcv)
+    if room_sz.dim() != 2 or room_sz.shape[1] != 3 or pos_src.dim() != 3 or pos_rcv.dim() != 3 or pos_src.shape[2] != 3 or pos_rcv.shape[2] != 3:
+        raise NbssError(f"rir_ism: room_sz {tuple(room_sz.shape)} must be [B,3], pos_src {tuple(pos_src.shape)} [B,S,3], pos_rcv {tuple(pos_rcv.shape)} [B,M,3]")
+    B, S, M = room_sz.shape[0], pos_src.shape[1], pos_rcv.shape[1]
+    if beta.shape != (B, 6) or pos_src.shape[0] != B or pos_rcv.shape[0] != B:
+        raise NbssError(f"rir_ism: beta {tuple(beta.shape)} must be [B,6] and every tensor must hold B = {B} rooms")
+    nb = torch.as_tensor(nb_img, device="cpu").to(torch.int32).reshape(-1, 3)
+    nb = (nb.expand(B, 3) if nb.shape[0] == 1 else nb).contiguous()
+    if nb.shape[0] != B:
+        raise NbssError(f"rir_ism: nb_img must be (Nx, Ny, Nz) or [B,3], got {tuple(nb.shape)}")
+    nws = lib.nbss_rir_ism_ws_bytes(B, nb.data_ptr())
+    if nws < 0:
+        raise NbssError(f"nbss_rir_ism_ws_bytes failed: {_ERR.get(nws, nws)}")
+    if ws is None:
+        ws = scratch(nws, dev)
+    k_d = 0 if t_diff is None else rir_tail_start(t_diff, fs)
+    h = torch.empty(B, S, M, int(n_samples), dtype=torch.float32, device=dev) if out is None else out
+    if h.shape != (B, S, M, int(n_samples)):
+        raise NbssError(f"rir_ism: out must be [B,S,M,n_samples] = {(B, S, M, int(n_samples))}, got {tuple(h.shape)}")
+    lib.call("nbss_rir_ism", B, S, M, int(n_samples), float(fs), float(c), float(tw), k_d, _ptr(lib, room_sz), _ptr(lib, beta), _ptr(lib, pos_src),
+             _ptr(lib, pos_rcv), nb.data_ptr(), _ptr(lib, h, torch.float32), _ptr(lib, ws, torch.uint8), ws.numel(), _stream(lib, h))
+    if t_diff is not None:
+        if rt60 is None:
+            raise NbssError("rir_ism: the diffuse tail (t_diff) needs rt60")
+        rt = torch.as_tensor(rt60, dtype=torch.float64).to(dev).reshape(-1)
+        rt = (rt.expand(B) if rt.numel() == 1 else rt).contiguous()
+        if rt.numel() != B:
+            raise NbssError(f"rir_ism: rt60 must be a number or [B], got {tuple(rt.shape)}")
+        lib.call("nbss_rir_tail", B, S, M, int(n_samples), float(fs), float(tw), k_d, _ptr(lib, rt), int(seed), _ptr(lib, h), _stream(lib, h))
+    return h
 
 
 def clip_adam_step(lib, params, grads, exp_avg, exp_avg_sq, scratch, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,

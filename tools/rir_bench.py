@@ -1,0 +1,64 @@
+"""Room simulation rates (profiles/README.md, "Room simulation"): RIRs/s and ms per batch of 32 rooms with 2 sources and 6 microphones each, at 8 and
+16 kHz, RT60 0.2 / 0.6 / 1.0 s — the full image-source sum down to 60 dB, and the 15-dB switch to the diffuse tail — through nbss_amd.rir.simulate_rir
+on the device (HIP events over `reps` calls after a warm-up) beside the fp64 host path of the same function on this box's CPU (one room of the
+batch, wall clock, scaled to the batch; skipped above `host_max_images` images per room).
+    python tools/rir_bench.py [rooms] [reps] [host_max_images]          one JSON line per case; a "RIR" is one (source, receiver) response"""
+import json
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from nbss_amd.rir import array_geometry, att2t, beta_sabine, simulate_rir, t2n  # noqa: E402
+
+
+def scene(B, rt60, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    u = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)
+    lims = torch.tensor([[3.0, 8.0], [3.0, 8.0], [3.0, 4.0]], dtype=torch.float64)
+    room = lims[:, 0] + (lims[:, 1] - lims[:, 0]) * u(B, 3)
+    centre = torch.cat([0.5 + (room[:, None, :2] - 1.0) * u(B, 1, 2), 1.0 + 0.5 * u(B, 1, 1)], -1)
+    rcv = centre + array_geometry("circular", 6, 0.05)
+    src = torch.cat([0.3 + (room[:, None, :2] - 0.6) * u(B, 2, 2), 1.0 + 0.8 * u(B, 2, 1)], -1)
+    rt = torch.full((B,), rt60, dtype=torch.float64)
+    return room, beta_sabine(room, rt)[0], src, rcv, rt
+
+
+def main():
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    host_max = float(sys.argv[3]) if len(sys.argv) > 3 else 1e6
+    dev = torch.device("cuda:0")
+    for fs in (8000, 16000):
+        for rt60 in (0.2, 0.6, 1.0):
+            for att in (60.0, 15.0):
+                room, beta, src, rcv, rt = scene(B, rt60)
+                T = att2t(att, rt60)
+                nb = t2n(torch.full((B,), T, dtype=torch.float64), room)
+                n = int((rt60 + 0.1) * fs)
+                kw = dict(t_diff=T, rt60=rt, seed=1) if att < 60 else {}
+                args = [t.to(dev) for t in (room, beta, src, rcv)]
+                simulate_rir(*args, nb, n, fs, **kw)  # warm-up
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    h = simulate_rir(*args, nb, n, fs, **kw)
+                e1.record()
+                torch.cuda.synchronize()
+                ms = e0.elapsed_time(e1) / reps
+                images = float(nb.prod(-1).double().mean())
+                row = {"fs": fs, "rt60": rt60, "mode": "full ISM to 60 dB" if att == 60 else "diffuse tail after 15 dB", "rooms": B, "n_samples": n,
+                       "images_per_room": images, "device_ms_per_batch": ms, "device_rirs_per_s": B * 12 / ms * 1e3, "finite": bool(torch.isfinite(h).all())}
+                if images <= host_max:
+                    kwh = dict(t_diff=T, rt60=rt[:1], seed=1) if att < 60 else {}
+                    t0 = time.perf_counter()
+                    simulate_rir(room[:1], beta[:1], src[:1], rcv[:1], nb[:1], n, fs, **kwh)
+                    dt = time.perf_counter() - t0
+                    row.update(host_ms_per_batch=dt * B * 1e3, host_rirs_per_s=12 / dt)
+                print(json.dumps(row), flush=True)
+
+
+main()
