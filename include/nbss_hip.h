@@ -92,7 +92,7 @@ int64_t nbss_mhsa_save_bytes(const nbss_cfg* cfg);
 int nbss_mhsa_fwd(const nbss_cfg* cfg, const float* params, const void* packed, int layer, const void* x, void* y, void* o_save, void* stream);
 /* x + _tconvffn (SpatialNet.py:90,102-114,61-73).
  * t_save (optional, nbss_tconvffn_save_bytes(cfg) bytes; that is 0 — pass NULL — for the geometries / stream types whose backward
- * recomputes the chain instead): what a training-mode forward keeps for nbss_tconvffn_bwd — the bf16 outputs of the 1x1 conv and of
+ * kernel recomputes the chain itself): what a training-mode forward keeps for nbss_tconvffn_bwd — the bf16 outputs of the 1x1 conv and of
  * the three grouped T-convs (tconvffn.1 / .3 / .5 / .8 of SpatialNet.py:61-73, group-major), the LayerNorm statistics of every token
  * and the GroupNorm statistics of every (sequence, group). */
 int64_t nbss_tconvffn_save_bytes(const nbss_cfg* cfg);
@@ -106,7 +106,8 @@ int nbss_tconvffn_fwd(const nbss_cfg* cfg, const float* params, const void* pack
  * nbss_workspace_bytes(cfg) bytes (per-token LayerNorm statistics and the operands of the
  * weight-gradient contractions). */
 int64_t nbss_workspace_bytes(const nbss_cfg* cfg);
-/* t_save: the forward's saved state (see nbss_tconvffn_fwd), or NULL: the forward chain is recomputed from x */
+/* t_save: the forward's saved state (see nbss_tconvffn_fwd), or NULL: the forward chain is recomputed from x (where
+ * nbss_tconvffn_save_bytes(cfg) > 0 that costs one more forward launch: the saved state is rebuilt inside ws, then the same kernels run) */
 int nbss_tconvffn_bwd(const nbss_cfg* cfg, const float* params, float* grads, const void* packed, int layer, const void* x, const void* dy,
                       const void* t_save, void* dx, void* ws, void* stream);
 int nbss_mhsa_bwd(const nbss_cfg* cfg, const float* params, float* grads, const void* packed, int layer, const void* x, const void* dy,

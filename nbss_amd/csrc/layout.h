@@ -219,7 +219,8 @@ NBSS_HD size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
 NBSS_HD size_t fc_part_bytes(const nbss_cfg& c) { return (size_t)c.B * c.T * (NBSS_FC_PROW(c) * sizeof(float) + NBSS_FC_P16(c) * 2); }
 // T-ConvFFN backward from saved pre-activations (tconvffn_s.hip: tconvffn_bwd_q_kernel; bf16 stream, small geometry): per sequence one fp32
 // partial row (GroupNorm affine sums 2 FFN + the three conv bias sums 3 FFN) and one bf16 row (the three conv weight gradients).  The region
-// keeps the size of the earlier four-group kernel's rows, which also carried W2's bias sums (H floats) and weight gradient (FFN H bf16)
+// is larger than those rows: H floats and FFN H bf16 per sequence are unused (an earlier kernel kept W2's bias sums and weight gradient there; the size stays
+// what callers of nbss_workspace_bytes have always been told)
 NBSS_HD size_t tc_part_bytes(const nbss_cfg& c) {
     return c.dtype == NBSS_BF16 && c.H == 96 && c.T <= 256
                ? (size_t)c.B * c.F * ((5 * c.FFN + c.H) * sizeof(float) + ((size_t)3 * c.FFN * (c.FFN / c.t_groups) * c.t_ks + (size_t)c.FFN * c.H) * 2)
@@ -258,6 +259,17 @@ NBSS_HD size_t ws_part_offset(const nbss_cfg& c) {
     const size_t N = (size_t)c.B * c.F * c.T, esz = c.dtype == NBSS_BF16 ? 2 : 4;
     return ws_align(N * 2 * sizeof(float)) + ws_nops(c) * ws_align(N * c.FFN * esz) + ws_wprep_bytes(c);
 }
+
+// operand region `slot` (of ws_nops) behind the [N][2] statistics head
+NBSS_HD size_t ws_op_offset(const nbss_cfg& c, int slot) {
+    const size_t N = (size_t)c.B * c.F * c.T, esz = c.dtype == NBSS_BF16 ? 2 : 4;
+    return ws_align(N * 2 * sizeof(float)) + (size_t)slot * ws_align(N * c.FFN * esz);
+}
+// T-ConvFFN backward from saved pre-activations (bf16 stream, small geometry): it emits the h5 and da1 operands.  A backward that was handed no saved state
+// rebuilds it first, in the regions that path leaves idle: a1 | a2 | a3 (one [G][N][24] bf16 tensor = one slot each), the rebuilding forward's discarded
+// output (N H elements of the slot's N FFN), the GroupNorm statistics (64 B F bytes of the slot's 384 B F T); the LayerNorm statistics take the [N][2] head
+// of the workspace (offset 0)
+enum { WS_TC_A1 = 0, WS_TC_A2, WS_TC_A3, WS_TC_H5, WS_TC_DA1, WS_TC_Y, WS_TC_GN };
 
 // per-workgroup partial dW tiles of the wgrad kernels live behind those
 NBSS_HD size_t ws_wgpart_offset(const nbss_cfg& c) { return ws_part_offset(c) + ws_part_bytes(c); }

@@ -8,8 +8,8 @@
 // groups), so the kernel walks the groups one at a time: only [T+2][24] row buffers of the current group (2 forward,
 // 4 backward) and the group's weight fragments (double-buffered in forward) live in LDS, the H-wide input strip (as LN'ed
 // B fragments) and the H-wide output accumulators stay in registers, and the FFN-wide (2S) intermediates of the reference
-// never exist in memory.  Backward recomputes the forward chain per group and emits the eight wgrad operand tensors
-// group-major ([G][N][24], non-temporal stores); every global read of a group is issued before that group's stores.
+// never exist in memory.  Backward (fp32 stream; the bf16 stream's is tconvffn_s.hip) recomputes the forward chain per group and emits the
+// eight wgrad operand tensors ([N][FFN], non-temporal stores); every global read of a group is issued before that group's stores.
 #include "launch.h"
 #include "layout.h"
 #include "prof.h"
@@ -17,6 +17,7 @@
 #include "blocks.h"
 #include "fold.h"
 #include "side.h"
+#include "tconvffn_s.h"
 #include <cstdlib>
 
 #define TF_H 96
@@ -436,26 +437,20 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 1 ? 4 : TF_FWD_WPS) void tcon
 
 
 // ---------------------------------------------------------------------------------------------
-// Backward (data gradient).  Same decomposition as forward; the group chain is recomputed and then
+// Backward (data gradient), fp32 stream.  Same decomposition as forward; the group chain is recomputed and then
 // walked backwards.  Pre-activations stay in registers (they are only needed by the owning wave),
 // activations / gradients that neighbouring frames need go through 4 LDS buffers.  Weight
 // gradients are NOT formed here: the kernel emits the (activation, pre-activation-gradient) pairs of
 // the five linear maps as [B,F,T,FFN] tensors and wgrad.hip contracts them over all tokens.
 // LayerNorm / GroupNorm affine gradients are reduced in-kernel (shuffle + atomicAdd).
-#define TF_OPS_GM(T) (sizeof(T) == 2)
-template <class T>
 struct TfOps {  // wgrad operands, each [B*F*T][FFN]
-    T *h1, *h2, *h4, *h5, *da1, *da2, *da3, *da5;
+    float *h1, *h2, *h4, *h5, *da1, *da2, *da3, *da5;
 };
 
-template <class T>
-NBSS_DEV void store_op(T* __restrict__ op, size_t n, bool valid, int gr, size_t ntok, const f32x4& lo, const f32x4& hi) {
+NBSS_DEV void store_op(float* __restrict__ op, size_t n, bool valid, int gr, const f32x4& lo, const f32x4& hi) {
     if (!valid) return;
     const int g4 = lane_id() >> 4;
-    // bf16 stream: group-major operands [G][N][24] — the 16 frames of a strip write 768 contiguous bytes.  Token-major rows
-    // ([N][FFN], 48-byte pieces of a 384-byte row per group) made every store a partial-line write: the kernel fetched 1 GB
-    // from HBM per launch (FETCH_SIZE) for 0.2 GB of algorithmic reads.  The fp32 stream keeps [N][FFN] (generic wgrad kernel).
-    T* r = TF_OPS_GM(T) ? op + ((size_t)gr * ntok + n) * TF_CG : op + n * TF_FFN + gr * TF_CG;
+    float* r = op + n * TF_FFN + gr * TF_CG;  // token-major rows [N][FFN]: what the generic wgrad kernel reads
     store4_nt(r + 4 * g4, lo[0], lo[1], lo[2], lo[3]);
     if (g4 < 2) store4_nt(r + 16 + 4 * g4, hi[0], hi[1], hi[2], hi[3]);
 }
@@ -463,32 +458,30 @@ NBSS_DEV void store_op(T* __restrict__ op, size_t n, bool valid, int gr, size_t 
 // sum over the 16 lanes that share (lane>>4): per-channel reduction over the frames of a strip
 NBSS_DEV float sum_l15(float v) { return row_sum16(v); }
 
-template <class T>
 __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs lp, const float* __restrict__ P, float* __restrict__ part, int layer,
-                                                           const T* __restrict__ W1, const T* __restrict__ Wc1, const T* __restrict__ Wc2,
-                                                           const T* __restrict__ Wc3, const T* __restrict__ W1tn, const T* __restrict__ Wc1t,
-                                                           const T* __restrict__ Wc2t, const T* __restrict__ Wc3t, const T* __restrict__ W2t,
-                                                           const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx,
-                                                           float* __restrict__ stats, TfOps<T> ops) {
+                                                           const float* __restrict__ W1, const float* __restrict__ Wc1, const float* __restrict__ Wc2,
+                                                           const float* __restrict__ Wc3, const float* __restrict__ W1tn, const float* __restrict__ Wc1t,
+                                                           const float* __restrict__ Wc2t, const float* __restrict__ Wc3t, const float* __restrict__ W2t,
+                                                           const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
+                                                           float* __restrict__ stats, TfOps ops) {
     NBSS_LDS(smem);
     const int T_ = c.T;
     constexpr int tp = TF_TP;  // buffers always hold 16 strips so that no strip ever indexes out of bounds
-    T* buf0 = reinterpret_cast<T*>(smem);
-    T* buf1 = buf0 + (size_t)(tp + 2) * TF_CG;
-    T* buf2 = buf1 + (size_t)(tp + 2) * TF_CG;
-    T* buf3 = buf2 + (size_t)(tp + 2) * TF_CG;
+    float* buf0 = reinterpret_cast<float*>(smem);
+    float* buf1 = buf0 + (size_t)(tp + 2) * TF_CG;
+    float* buf2 = buf1 + (size_t)(tp + 2) * TF_CG;
+    float* buf3 = buf2 + (size_t)(tp + 2) * TF_CG;
     float* red = reinterpret_cast<float*>(buf3 + (size_t)(tp + 2) * TF_CG);  // [8 waves][2]
     float* aff = red + 16;  // [576] per-workgroup sums: GN weight | GN bias | LN weight | LN bias
     float* lnp = aff + TF_AFF;  // [2H] LayerNorm gamma | beta
     float* prm = lnp + 2 * TF_H;  // [6][FFN]: b1 cb1 cb2 cb3 gnw gnb
-    T* wl = reinterpret_cast<T*>(prm + 6 * TF_FFN);  // this group's weights: W1 c1 c2 c3 | W2^T c3^T c2^T c1^T W1^T, 6 fragments each
-    PHASE_BEGIN(wl + (sizeof(T) == 2 ? 48 * 512 : 0));
+    PHASE_BEGIN(prm + 6 * TF_FFN);
     const int bf = blockIdx.x;
     const int tid = threadIdx.x, lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
     const size_t n0 = (size_t)bf * T_;
-    const T* xb = x + n0 * TF_H;
-    const T* dyb = dy + n0 * TF_H;
-    T* dxb = dx + n0 * TF_H;
+    const float* xb = x + n0 * TF_H;
+    const float* dyb = dy + n0 * TF_H;
+    float* dxb = dx + n0 * TF_H;
     const float* lnw = lp.p[P_TF_LN_W];
     const float* lnb = lp.p[P_TF_LN_B];
     const float* b1_g = lp.p[P_TF_B1];
@@ -506,7 +499,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
 
     for (int i = tid; i < TF_AFF; i += blockDim.x) aff[i] = 0.f;
     if (tid < TF_CG) {
-        T* bs[4] = {buf0, buf1, buf2, buf3};
+        float* bs[4] = {buf0, buf1, buf2, buf3};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             store1(bs[i] + tid, 0.f);
@@ -555,7 +548,6 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
     const int d0 = 4 * g4, d1 = 16 + 4 * g4;
     const bool v1 = g4 < 2;
     const float cnt = (float)(TF_CG * T_);
-    const size_t ntok = (size_t)c.B * c.F * T_;
 
     lds_barrier();  // lnp / prm / halo rows are in place
     PHASE(0);
@@ -565,20 +557,17 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
     for (int gr = 0; gr < TF_G; ++gr) {
         const int cbase = gr * TF_CG;
         f32x4 a1[TF_NSW][2], a2[TF_NSW][2], a3h[TF_NSW][2], a5[TF_NSW][2], ct[TF_NSW][2];
-        // this group's 54 weight fragments: global -> LDS once per workgroup (see the forward kernel); the fp32 stream has
-        // no LDS room for them and keeps reading the packed buffer directly
-        constexpr bool STAGE = sizeof(T) == 2;
-        const T* srcs[8] = {W1, Wc1, Wc2, Wc3, W2t, Wc3t, Wc2t, Wc1t};
-        const T* wsl[8];
+        // this group's weight fragments are read from the packed buffer directly (no LDS room to stage them as the forward kernel does)
+        const float* srcs[8] = {W1, Wc1, Wc2, Wc3, W2t, Wc3t, Wc2t, Wc1t};
+        const float* wsl[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) wsl[i] = STAGE ? wl + (size_t)i * 6 * 512 : srcs[i] + (size_t)gr * 6 * 512;
+        for (int i = 0; i < 8; ++i) wsl[i] = srcs[i] + (size_t)gr * 6 * 512;
         // Every global read of the group is issued here, ahead of the group's operand stores: loads and stores share vmcnt on
         // gfx9, so a load issued after a store cannot complete before that store is acknowledged (the three phases that read
         // x, dy and the weights behind stores were 43 % of the wave time).
         // (Issuing them one phase earlier still, before the last conv phase of the previous group, spilled 20 registers and
         // was slower: 6.7 vs 6.3 ms/step.)
-        Frag<T> xr[TF_NSW][TF_KS], dr[TF_NSW][TF_KS];
-        StageRegs<T, 8> wreg;
+        Frag<float> xr[TF_NSW][TF_KS], dr[TF_NSW][TF_KS];
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si)
 #pragma unroll
@@ -589,17 +578,9 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 frag_load(dr[si][ks], dyb + (size_t)tc[si] * TF_H + ks * 32 + 8 * g4);
                 if (!tv[si]) frag_zero(dr[si][ks]);
             }
-        if (STAGE) {
-            const StageSrcs<T> wsrc = {W1, Wc1, Wc2, Wc3, W2t, Wc3t, Wc2t, Wc1t};
-            wreg.load(wsrc, (size_t)gr * 6 * 512);
-        }
         if (gr > 0) {
 #pragma unroll
-            for (int si = 0; si < TF_NSW; ++si) store_op<T>(ops.da1, n0 + tt[si], tv[si], gr - 1, ntok, pend[si][0], pend[si][1]);
-        }
-        if (STAGE) {
-            wreg.store(wl);
-            lds_barrier();
+            for (int si = 0; si < TF_NSW; ++si) store_op(ops.da1, n0 + tt[si], tv[si], gr - 1, pend[si][0], pend[si][1]);
         }
         PHASE(1);
         // ---------------- forward recompute ----------------
@@ -612,7 +593,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
             dh5[si][1] = F32X4_ZERO;
 #pragma unroll
             for (int ks = 0; ks < TF_KS; ++ks) {
-                Frag<T> uf;
+                Frag<float> uf;
                 float gm[8], bt[8];
                 load8(lnp + ks * 32 + 8 * g4, gm);
                 load8(lnp + TF_H + ks * 32 + 8 * g4, bt);
@@ -620,10 +601,10 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 for (int j = 0; j < 8; ++j) frag_set(uf, j, tv[si] ? (frag_get(xr[si][ks], j) - smean[si]) * srstd[si] * gm[j] + bt[j] : bt[j]);
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    Frag<T> a;
-                    lfrag<T>(a, wsl[0], half * 3 + ks);
+                    Frag<float> a;
+                    lfrag<float>(a, wsl[0], half * 3 + ks);
                     a1[si][half] = mma(a, uf, a1[si][half]);
-                    lfrag<T>(a, wsl[4], half * 3 + ks);
+                    lfrag<float>(a, wsl[4], half * 3 + ks);
                     dh5[si][half] = mma(a, dr[si][ks], dh5[si][half]);
                 }
             }
@@ -637,13 +618,13 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] = silu_f(a1[si][0][r]);
                 ct[si][1][r] = keep_if(v1, silu_f(a1[si][1][r]));
             }
-            store_rows<T>(buf0, tt[si], tv[si], ct[si][0], ct[si][1]);
-            store_op<T>(ops.h1, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_rows<float>(buf0, tt[si], tv[si], ct[si][0], ct[si][1]);
+            store_op(ops.h1, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(2);
         lds_barrier();
         PHASE(3);
-        conv_group<T>(wsl[1], buf0, w, a2);
+        conv_group<float>(wsl[1], buf0, w, a2);
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si) {
 #pragma unroll
@@ -653,13 +634,13 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] = silu_f(a2[si][0][r]);
                 ct[si][1][r] = keep_if(v1, silu_f(a2[si][1][r]));
             }
-            store_rows<T>(buf1, tt[si], tv[si], ct[si][0], ct[si][1]);
-            store_op<T>(ops.h2, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_rows<float>(buf1, tt[si], tv[si], ct[si][0], ct[si][1]);
+            store_op(ops.h2, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(4);
         lds_barrier();
         PHASE(5);
-        conv_group<T>(wsl[2], buf1, w, a3h);
+        conv_group<float>(wsl[2], buf1, w, a3h);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si)
@@ -704,13 +685,13 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] = silu_f(a3h[si][0][r] * gw0[r] + gnb[cbase + d0 + r]);
                 ct[si][1][r] = keep_if(v1, silu_f(a3h[si][1][r] * gw1[r] + gnb[cbase + d1 + r]));
             }
-            store_rows<T>(buf2, tt[si], tv[si], ct[si][0], ct[si][1]);
-            store_op<T>(ops.h4, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_rows<float>(buf2, tt[si], tv[si], ct[si][0], ct[si][1]);
+            store_op(ops.h4, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(8);
         lds_barrier();
         PHASE(9);
-        conv_group<T>(wsl[3], buf2, w, a5);
+        conv_group<float>(wsl[3], buf2, w, a5);
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si) {
 #pragma unroll
@@ -720,7 +701,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] = silu_f(a5[si][0][r]);
                 ct[si][1][r] = keep_if(v1, silu_f(a5[si][1][r]));
             }
-            store_op<T>(ops.h5, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_op(ops.h5, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(10);
         // ---------------- backward ----------------
@@ -732,14 +713,14 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] = dh5[si][0][r] * dsilu_f(a5[si][0][r]);
                 ct[si][1][r] = keep_if(v1, dh5[si][1][r] * dsilu_f(a5[si][1][r]));
             }
-            store_rows<T>(buf3, tt[si], tv[si], ct[si][0], ct[si][1]);
-            store_op<T>(ops.da5, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_rows<float>(buf3, tt[si], tv[si], ct[si][0], ct[si][1]);
+            store_op(ops.da5, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(11);
         lds_barrier();
         PHASE(12);
         // dh4 = conv3^T(da5) ; dn3 = dh4 * silu'(n3) ; GroupNorm backward -> da3 -> buf2
-        conv_group<T>(wsl[5], buf3, w, ct);
+        conv_group<float>(wsl[5], buf3, w, ct);
         float sa = 0.f, sb = 0.f;
         float dgw[2][4], dgb[2][4];
 #pragma unroll
@@ -796,14 +777,14 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] = rstd * (gw0[r] * ct[si][0][r] - tsa - a3h[si][0][r] * tsb);
                 ct[si][1][r] = v1 ? rstd * (gw1[r] * ct[si][1][r] - tsa - a3h[si][1][r] * tsb) : 0.f;
             }
-            store_rows<T>(buf2, tt[si], tv[si], ct[si][0], ct[si][1]);
-            store_op<T>(ops.da3, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_rows<float>(buf2, tt[si], tv[si], ct[si][0], ct[si][1]);
+            store_op(ops.da3, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(15);
         lds_barrier();
         PHASE(16);
         // dh2 = conv2^T(da3) ; da2 = dh2 * silu'(a2) -> buf1
-        conv_group<T>(wsl[6], buf2, w, ct);
+        conv_group<float>(wsl[6], buf2, w, ct);
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si) {
 #pragma unroll
@@ -811,14 +792,14 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
                 ct[si][0][r] *= dsilu_f(a2[si][0][r]);
                 ct[si][1][r] = keep_if(v1, ct[si][1][r] * dsilu_f(a2[si][1][r]));
             }
-            store_rows<T>(buf1, tt[si], tv[si], ct[si][0], ct[si][1]);
-            store_op<T>(ops.da2, n0 + tt[si], tv[si], gr, ntok, ct[si][0], ct[si][1]);
+            store_rows<float>(buf1, tt[si], tv[si], ct[si][0], ct[si][1]);
+            store_op(ops.da2, n0 + tt[si], tv[si], gr, ct[si][0], ct[si][1]);
         }
         PHASE(17);
         lds_barrier();
         PHASE(18);
         // dh1 = conv1^T(da2) ; da1 = dh1 * silu'(a1) ; du += W1[group]^T da1
-        conv_group<T>(wsl[7], buf1, w, ct);
+        conv_group<float>(wsl[7], buf1, w, ct);
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si) {
 #pragma unroll
@@ -836,7 +817,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
     }
 
 #pragma unroll
-    for (int si = 0; si < TF_NSW; ++si) store_op<T>(ops.da1, n0 + tt[si], tv[si], TF_G - 1, ntok, pend[si][0], pend[si][1]);
+    for (int si = 0; si < TF_NSW; ++si) store_op(ops.da1, n0 + tt[si], tv[si], TF_G - 1, pend[si][0], pend[si][1]);
     // du = W1^T da1 over all FFN channels, from the [N][FFN] operand this workgroup has just written (the weight-gradient
     // kernel reads the same buffer): a full barrier makes the stores of the other waves visible (never-read lines: no stale L1)
     __syncthreads();
@@ -847,13 +828,12 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
 #pragma unroll
         for (int mt = 0; mt < TF_H / 16; ++mt) du[si][mt] = F32X4_ZERO;
         for (int k6 = 0; k6 < TF_FFN / 32; ++k6) {
-            Frag<T> df;
-            const int ch = k6 * 32 + 8 * g4;  // 8-channel pieces never straddle a 24-channel group
-            frag_load(df, TF_OPS_GM(T) ? ops.da1 + ((size_t)(ch / TF_CG) * ntok + n0 + tc[si]) * TF_CG + ch % TF_CG
-                                       : ops.da1 + (n0 + tc[si]) * TF_FFN + ch);  // (frames beyond T: clamped, their du is discarded)
+            Frag<float> df;
+            const int ch = k6 * 32 + 8 * g4;
+            frag_load(df, ops.da1 + (n0 + tc[si]) * TF_FFN + ch);  // (frames beyond T: clamped, their du is discarded)
 #pragma unroll
             for (int mt = 0; mt < TF_H / 16; ++mt) {
-                Frag<T> a;
+                Frag<float> a;
                 wfrag_load(a, W1tn, mt, TF_FFN / 32, k6);
                 du[si][mt] = mma(a, df, du[si][mt]);
             }
@@ -937,59 +917,39 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
 }
 PHASE_READER(nbss_phase_read_tconvffn_bwd)
 
-int tconvffn_bwd_s_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* x, const void* dy,
-                          void* const* opsv, float* stats, int pstride, hipStream_t st);
-struct TailArgs;
 int tailw_tconvffn(const nbss_cfg& c, const LayerPtrs& lp, const void* packed, int layer, const void* x, const void* dy, void* dx, float* stats,
                    const void* da1, float* wgpart, float* G, const float* P, hipStream_t st, const Side* sd, hipStream_t* gs);
 
-// bf16 stream: data-gradient kernel of tconvffn_s.hip + the tail (du, LayerNorm backward, dx) inside the W1 weight-gradient kernel (tailw.hip)
-static int tconvffn_bwd_bf16(const nbss_cfg& c, const float* P, float* G, float* part, const void* packed, int layer, const void* x, const void* dy, void* dx,
-                             float* stats, void* const* opsv, float* wgpart, hipStream_t st, const Side* sd, hipStream_t* gs) {
-    const LayerPtrs lp = layer_ptrs(c, P, layer);
-    ProfScope ps(PK_TCF_B, st);  // both kernels of the sub-block: ONE profiler interval per nbss_tconvffn_bwd call
-    int e = tconvffn_bwd_s_launch(c, lp, part, packed, layer, x, dy, opsv, stats, 2 * TF_FFN, st);
-    if (e) return e;
-    return tailw_tconvffn(c, lp, packed, layer, x, dy, dx, stats, opsv[4], wgpart, G, P, st, sd, gs);
-}
-
-template <class T>
-static int tconvffn_bwd_t(const nbss_cfg& c, const float* P, float* part, const void* packed, int layer, const void* x, const void* dy, void* dx,
+static int tconvffn_bwd_f32(const nbss_cfg& c, const float* P, float* part, const void* packed, int layer, const void* x, const void* dy, void* dx,
                           float* stats, void* const* opsv, hipStream_t st) {
     const LayerPtrs lp = layer_ptrs(c, P, layer);
     if (c.T > TF_TP) return NBSS_EUNSUPPORTED;
-    const size_t lds = (size_t)4 * (TF_TP + 2) * TF_CG * sizeof(T) + (16 + TF_AFF + 2 * TF_H + 6 * TF_FFN) * sizeof(float) + (sizeof(T) == 2 ? (size_t)48 * 512 * sizeof(T) : 0) + PHASE_LDS_BYTES;
+    const size_t lds = (size_t)4 * (TF_TP + 2) * TF_CG * sizeof(float) + (16 + TF_AFF + 2 * TF_H + 6 * TF_FFN) * sizeof(float) + PHASE_LDS_BYTES;
     if (lds > 160 * 1024) return NBSS_EUNSUPPORTED;
-    const T* pk = (const T*)packed;
-    TfOps<T> ops;
-    ops.h1 = (T*)opsv[0]; ops.h2 = (T*)opsv[1]; ops.h4 = (T*)opsv[2]; ops.h5 = (T*)opsv[3];
-    ops.da1 = (T*)opsv[4]; ops.da2 = (T*)opsv[5]; ops.da3 = (T*)opsv[6]; ops.da5 = (T*)opsv[7];
-    int e = NBSS_SET_MAX_LDS((tconvffn_bwd_kernel<T>), lds);
+    const float* pk = (const float*)packed;
+    TfOps ops;
+    ops.h1 = (float*)opsv[0]; ops.h2 = (float*)opsv[1]; ops.h4 = (float*)opsv[2]; ops.h5 = (float*)opsv[3];
+    ops.da1 = (float*)opsv[4]; ops.da2 = (float*)opsv[5]; ops.da3 = (float*)opsv[6]; ops.da5 = (float*)opsv[7];
+    int e = NBSS_SET_MAX_LDS(tconvffn_bwd_kernel, lds);
     if (e) return e;
     dim3 grid(c.B * c.F), block(512);
     ProfScope ps(PK_TCF_B, st);
-    NBSS_LAUNCH((tconvffn_bwd_kernel<T>), grid, block, lds, st, c, lp, P, part, layer, pk + pack_off(c, layer, K_TF_W1), pk + pack_off(c, layer, K_TF_C1),
+    NBSS_LAUNCH(tconvffn_bwd_kernel, grid, block, lds, st, c, lp, P, part, layer, pk + pack_off(c, layer, K_TF_W1), pk + pack_off(c, layer, K_TF_C1),
                 pk + pack_off(c, layer, K_TF_C2), pk + pack_off(c, layer, K_TF_C3), pk + pack_off(c, layer, K_TF_W1_TN),
                 pk + pack_off(c, layer, K_TF_C1_T), pk + pack_off(c, layer, K_TF_C2_T), pk + pack_off(c, layer, K_TF_C3_T),
-                pk + pack_off(c, layer, K_TF_W2_T), (const T*)x, (const T*)dy, (T*)dx, stats, ops);
+                pk + pack_off(c, layer, K_TF_W2_T), (const float*)x, (const float*)dy, (float*)dx, stats, ops);
     return NBSS_CHECK_LAUNCH();
 }
-
-float* tconvffn_save_ln_stats(const nbss_cfg& c, void* tsave);
-int tconvffn_v_reduce16(const nbss_cfg& c, const void* part16, float* slices, float* G, const long long* offs, hipStream_t st);
-int tconvffn_bwd_q_launch(const nbss_cfg& c, const LayerPtrs& lp, float* part, const void* packed, int layer, const void* dy, void* tsave, void* op_h5, void* op_da1,
-                          hipStream_t st);
 
 // bf16 stream, from the pre-activations a training-mode forward saved (tconvffn_s.hip): data gradient + the three T-conv weight gradients in
 // tconvffn_bwd_q (a sequence's group pairs: two workgroups per CU), the tail + W1 weight gradient in tailw.hip, one fold of the per-sequence partial
 // rows, W2's weight gradient from the h5 operand through wgrad.hip
-static int tconvffn_bwd_saved(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, void* tsave,
+static int tconvffn_bwd_saved(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, const TsSave& sv,
                               void* dx, void* ws, hipStream_t st, const Side* sd) {
     const LayerPtrs lp = layer_ptrs(c, P, layer);
     const size_t N = (size_t)c.B * c.F * c.T;
-    char* base = (char*)ws + ws_align(N * 2 * sizeof(float));
-    void* op_h5 = base + (size_t)3 * ws_align(N * TF_FFN * 2);
-    void* op_da1 = base + (size_t)4 * ws_align(N * TF_FFN * 2);
+    void* op_h5 = (char*)ws + ws_op_offset(c, WS_TC_H5);
+    void* op_da1 = (char*)ws + ws_op_offset(c, WS_TC_DA1);
     float* part = (float*)((char*)ws + ws_tcpart_offset(c));
     float* wgpart = (float*)((char*)ws + ws_wgpart_offset(c));
     int e;
@@ -997,8 +957,8 @@ static int tconvffn_bwd_saved(const nbss_cfg& c, const float* P, float* G, const
     FoldScope fs(st, wgpart, WGPART_BYTES, N);  // (fold.h: the sub-block's seven fold launches leave as two, one per stage, on the gradient stream)
     {
         ProfScope ps(PK_TCF_B, st);  // both kernels of the sub-block: ONE profiler interval per nbss_tconvffn_bwd call
-        if ((e = tconvffn_bwd_q_launch(c, lp, part, packed, layer, dy, tsave, op_h5, op_da1, st))) return e;
-        if ((e = tailw_tconvffn(c, lp, packed, layer, x, dy, dx, tconvffn_save_ln_stats(c, tsave), op_da1, wgpart, G, P, st, sd, &gs))) return e;
+        if ((e = tconvffn_bwd_q_launch(c, lp, part, packed, layer, dy, sv, op_h5, op_da1, st))) return e;
+        if ((e = tailw_tconvffn(c, lp, packed, layer, x, dy, dx, sv.ln, op_da1, wgpart, G, P, st, sd, &gs))) return e;
     }
     const int convW[3] = {P_TF_C1W, P_TF_C2W, P_TF_C3W}, convBias[3] = {P_TF_C1B, P_TF_C2B, P_TF_C3B};
     AffSegs sg;  // fp32 rows: GroupNorm affine sums + the three conv bias sums
@@ -1026,24 +986,28 @@ static int tconvffn_bwd_saved(const nbss_cfg& c, const float* P, float* G, const
 int tconvffn_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* packed, int layer, const void* x, const void* dy, const void* tsave,
                       void* dx, void* ws, hipStream_t st, const Side* sd) {
     if (c.H != TF_H) return gb_tconvffn_bwd(c, P, G, layer, x, dy, dx, ws, st, sd);
-    if (tsave && c.dtype == NBSS_BF16) return tconvffn_bwd_saved(c, P, G, packed, layer, x, dy, const_cast<void*>(tsave), dx, ws, st, sd);
+    if (c.dtype == NBSS_BF16) {
+        if (tsave) return tconvffn_bwd_saved(c, P, G, packed, layer, x, dy, ts_save_ptrs(c, const_cast<void*>(tsave)), dx, ws, st, sd);
+        // no saved state (the per-block entry point alone: the walks always save): the training-mode forward rebuilds it from x in the workspace regions
+        // the saved-state path leaves idle (layout.h: WS_TC_*; its output y is discarded), unflipped and outside the walks' flip count
+        const TsSave sv = ts_save_ws(c, ws);
+        const int e = tconvffn_fwd_s_impl(c, P, packed, layer, x, (char*)ws + ws_op_offset(c, WS_TC_Y), &sv, st, nullptr, 0);
+        return e ? e : tconvffn_bwd_saved(c, P, G, packed, layer, x, dy, sv, dx, ws, st, sd);
+    }
+    // fp32 stream
     const LayerPtrs lp = layer_ptrs(c, P, layer);
-    // workspace: stats [N][2] f32 | h1 h2 h4 h5 da1 da2 da3 da5, each [N][FFN] of the stream dtype
-    const size_t N = (size_t)c.B * c.F * c.T, esz = c.dtype == NBSS_BF16 ? 2 : 4;
+    // workspace: stats [N][2] f32 | h1 h2 h4 h5 da1 da2 da3 da5, each [N][FFN] fp32
+    const size_t N = (size_t)c.B * c.F * c.T;
     float* stats = (float*)ws;
-    char* base = (char*)ws + ws_align(N * 2 * sizeof(float));
     void* ops[8];
-    for (int i = 0; i < 8; ++i) ops[i] = base + (size_t)i * ws_align(N * TF_FFN * esz);
+    for (int i = 0; i < 8; ++i) ops[i] = (char*)ws + ws_op_offset(c, i);
     float* part = (float*)((char*)ws + ws_part_offset(c));
     float* wgpart = (float*)((char*)ws + ws_wgpart_offset(c));
-    const bool fused = c.dtype == NBSS_BF16;  // the tail kernel contracted dW1 / db1 and reduced the LayerNorm affine sums
-    hipStream_t gs = st;  // parameter-gradient launches (side.h)
-    int e = c.dtype == NBSS_BF16 ? tconvffn_bwd_bf16(c, P, G, part, packed, layer, x, dy, dx, stats, ops, wgpart, st, sd, &gs)
-                                 : tconvffn_bwd_t<float>(c, P, part, packed, layer, x, dy, dx, stats, ops, st);
+    int e = tconvffn_bwd_f32(c, P, part, packed, layer, x, dy, dx, stats, ops, st);
     if (e) return e;
-    if (gs == st) gs = side_fork(sd, st);
+    const hipStream_t gs = side_fork(sd, st);  // parameter-gradient launches (side.h)
     AffSegs sg;
-    sg.n = fused ? 2 : 4;
+    sg.n = 4;
     sg.off[0] = param_off(c, layer, P_TF_GN_W); sg.cnt[0] = TF_FFN;
     sg.off[1] = param_off(c, layer, P_TF_GN_B); sg.cnt[1] = TF_FFN;
     sg.off[2] = param_off(c, layer, P_TF_LN_W); sg.cnt[2] = TF_H;
@@ -1055,10 +1019,7 @@ int tconvffn_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* p
     a.Ntok = (int)N; a.F = c.F; a.T = c.T; a.shift_stride = 1; a.shift_dim = 0;
     a.stats = nullptr; a.gamma = nullptr; a.beta = nullptr;
     // W2: dW2[H][FFN] = dy^T h5 ; db2 = colsum(dy)
-    const bool gm = c.dtype == NBSS_BF16;  // TF_OPS_GM: operands are [G][N][24]
-    const int ogw = gm ? TF_CG : 0, ogs = gm ? (int)(N * TF_CG) : 0;
     a.A = dy; a.lda = TF_H; a.MA = TF_H; a.B = ops[3]; a.ldb = TF_FFN; a.NB = TF_FFN; a.groups = 1; a.taps = 1;
-    a.b_gw = ogw; a.b_gs = ogs;
     a.dW = G + param_off(c, layer, P_TF_W2); a.dbias = G + param_off(c, layer, P_TF_B2);
     if ((e = wgrad_launch(a, c.dtype, gs))) return e;
     // the three grouped k=3 convs
@@ -1067,14 +1028,11 @@ int tconvffn_bwd_impl(const nbss_cfg& c, const float* P, float* G, const void* p
     for (int k = 0; k < 3; ++k) {
         a.A = ops[convA[k]]; a.lda = TF_FFN; a.MA = TF_FFN; a.B = ops[convB[k]]; a.ldb = TF_FFN; a.NB = TF_FFN;
         a.groups = c.t_groups; a.taps = c.t_ks;
-        a.a_gw = ogw; a.a_gs = ogs; a.b_gw = ogw; a.b_gs = ogs;
         a.dW = G + param_off(c, layer, convW[k]); a.dbias = G + param_off(c, layer, convBias[k]);
         if ((e = wgrad_launch(a, c.dtype, gs))) return e;
     }
-    if (fused) return NBSS_OK;
     // W1: dW1[FFN][H] = da1^T LN(x) ; db1 = colsum(da1)
     a.A = ops[4]; a.lda = TF_FFN; a.MA = TF_FFN; a.B = x; a.ldb = TF_H; a.NB = TF_H; a.groups = 1; a.taps = 1;
-    a.a_gw = ogw; a.a_gs = ogs; a.b_gw = 0; a.b_gs = 0;
     a.stats = stats; a.gamma = lp.p[P_TF_LN_W]; a.beta = lp.p[P_TF_LN_B];
     a.dW = G + param_off(c, layer, P_TF_W1); a.dbias = G + param_off(c, layer, P_TF_B1);
     return wgrad_launch(a, c.dtype, gs);
@@ -1093,8 +1051,6 @@ static int tconvffn_fwd_t(const nbss_cfg& c, const float* P, const void* packed,
     return NBSS_CHECK_LAUNCH();
 }
 
-int tconvffn_fwd_s_impl(const nbss_cfg& c, const float* P, const void* packed, int layer, const void* x, void* y, void* tsave, hipStream_t st, const SeqTail* tl);
-
 int tconvffn_fwd_large_impl(const nbss_cfg& c, const float* P, const void* packed, int layer, const void* x, void* y, hipStream_t st);
 
 // tsave (optional; bf16 stream, T <= 256, small geometry — tconvffn_save_bytes() > 0): the training-mode forward keeps its pre-activations there
@@ -1103,5 +1059,7 @@ int tconvffn_fwd_impl(const nbss_cfg& c, const float* P, const void* packed, int
     // bf16 stream: the streaming wave-per-group kernel (tconvffn_s.hip); fp32 stream: the group-serial kernel above
     // sequences beyond 256 frames (forward only): the chunked two-pass variant of the group-serial kernel
     if (c.T > TF_TP) return c.dtype == NBSS_BF16 ? tconvffn_fwd_t<bf16_t, 1, true>(c, P, packed, layer, x, y, st) : tconvffn_fwd_t<float, 2, true>(c, P, packed, layer, x, y, st);
-    return c.dtype == NBSS_BF16 ? tconvffn_fwd_s_impl(c, P, packed, layer, x, y, tsave, st, tl) : tconvffn_fwd_t<float, 2, false>(c, P, packed, layer, x, y, st);
+    if (c.dtype != NBSS_BF16) return tconvffn_fwd_t<float, 2, false>(c, P, packed, layer, x, y, st);
+    const TsSave sv = ts_save_ptrs(c, tsave);
+    return tconvffn_fwd_s_impl(c, P, packed, layer, x, y, tsave ? &sv : nullptr, st, tl, walk_flip_next());
 }

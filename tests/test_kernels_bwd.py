@@ -106,6 +106,30 @@ def test_tconvffn_save_is_refused_where_backward_recomputes(backend):
     assert ops.tconvffn_save(cs.lib, cs.cfg, backend.device) is None  # fp32 stream: nbss_tconvffn_save_bytes == 0
 
 
+def test_tconvffn_bwd_without_saved_state_is_the_saved_path(backend):
+    """bf16 stream, t_save = NULL: the backward rebuilds the saved state inside its workspace with the training-mode forward and then runs the
+    same kernels as with a caller's t_save — the same numbers at other addresses, every fold in a fixed order: dx and the flat gradient are
+    bitwise equal.  The rebuilt state stays inside nbss_workspace_bytes, and x is not written.
+    Shapes: T no multiple of 32 | an odd strip count | the T = 256 cap | several sequences per fold slice."""
+    for (B, F, T) in [(1, 5, 19), (1, 3, 70), (1, 2, 256), (2, 33, 40)]:
+        cs = Case(backend, B, F, T, NBSS_BF16)
+        x, _ = cs.stream(seed=20)
+        dy, _ = cs.stream(seed=120, scale=0.5)
+        x0 = x.clone()
+        nws, guard = ops.workspace(cs.lib, cs.cfg, backend.device).numel(), 4096
+        ws = torch.full((nws + guard,), 0xA5, dtype=torch.uint8, device=backend.device)
+        G = torch.zeros_like(cs.flat)
+        dx = ops.tconvffn_bwd(cs.lib, cs.cfg, cs.flat, G, cs.packed, 0, x, dy, ws)
+        assert torch.equal(ws[nws:], torch.full_like(ws[nws:], 0xA5)), (B, F, T)
+        assert torch.equal(x, x0), (B, F, T)
+        sv = ops.tconvffn_save(cs.lib, cs.cfg, backend.device)
+        ops.tconvffn_fwd(cs.lib, cs.cfg, cs.flat, cs.packed, 0, x, t_save=sv)
+        G_sv = torch.zeros_like(cs.flat)
+        dx_sv = ops.tconvffn_bwd(cs.lib, cs.cfg, cs.flat, G_sv, cs.packed, 0, x, dy, ops.workspace(cs.lib, cs.cfg, backend.device), t_save=sv)
+        assert torch.equal(dx, dx_sv), (B, F, T)
+        assert torch.equal(G, G_sv), (B, F, T)
+
+
 MH_NAMES = ["layers.0.norm_mhsa.weight", "layers.0.norm_mhsa.bias", "layers.0.mhsa.in_proj_weight", "layers.0.mhsa.in_proj_bias",
             "layers.0.mhsa.out_proj.weight", "layers.0.mhsa.out_proj.bias"]
 

@@ -39,11 +39,10 @@ def main():
         "full_bwd": lambda: ops.full_bwd(lib, cfg, flat, G, packed, 0, x, dy, ws),
         "mhsa_bwd": lambda: ops.mhsa_bwd(lib, cfg, flat, G, packed, 0, x, dy, o, ws),
         "tconvffn_bwd": lambda: ops.tconvffn_bwd(lib, cfg, flat, G, packed, 0, x, dy, ws, t_save=tsv),
-        "tconvffn_bwd_recompute": lambda: ops.tconvffn_bwd(lib, cfg, flat, G, packed, 0, x, dy, ws),
     }
     if name == "mhsa_bwd":
         fns["mhsa_fwd"]()
-    reader = getattr(lib, "nbss_phase_read_" + (sys.argv[4] if len(sys.argv) > 4 else name))  # (the single-pass bf16 attention backward shares mhsa_bwd's accumulators)
+    reader = getattr(lib, "nbss_phase_read_" + (sys.argv[4] if len(sys.argv) > 4 else name))  # (the single-pass bf16 attention backward shares mhsa_bwd's accumulators, the bf16 T-ConvFFN backward tconvffn_fwd's: one set per source file)
     reader.restype = C.c_int
     buf = (C.c_ulonglong * 32)()
     fns[name]()
