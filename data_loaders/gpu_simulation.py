@@ -1,7 +1,7 @@
 """On-GPU simulation of multichannel noisy-reverberant mixtures: the per-item numpy pipeline of the
 reference's dataset modules, batched on the device so that the loader keeps up with the HIP training step (hundreds of utterances/s
 per GPU; the reference's 10 CPU workers produce far fewer):
-    dry sources  --RIR convolution (FFT), aligned to the direct path of the reference channel-->  reverberant images / targets
+    dry sources  --RIR convolution (FFT, or convolve='native': csrc/conv1d.hip), aligned to the direct path of the reference channel-->  images / targets
     --relative scaling of speaker 2 to a sampled SIR-->  mixture  --spatially diffuse noise at a sampled SNR-->  peak scaling 0.9
 following data_loaders/sms_wsj_plus.py:157-220, utils/mix.py:122-134 (convolve), :328-346 (energy ratio), utils/diffuse_noise.py:19-93
 (spherically isotropic coherence sinc(w d / c), mixing matrices from its eigendecomposition, STFT-domain mixing of independent
@@ -36,6 +36,35 @@ def convolve_aligned(wav: Tensor, rir: Tensor, rir_target: Optional[Tensor] = No
     idx = delay[:, :, None, None] + torch.arange(N, device=wav.device)[None, None, None, :]
     idx = idx.expand(B, S, rir.shape[2], N)
     return full.gather(-1, idx), tgt.gather(-1, idx)
+
+
+CONVOLVE_MODES = ('fft', 'native')
+
+
+def convolve_aligned_native(wav: Tensor, rir: Tensor, rir_target: Optional[Tensor] = None, ref_channel: int = 0, lib=None) -> Tuple[Tensor, Tensor]:
+    """convolve_aligned by the HIP kernels of csrc/conv1d.hip: the delay by nbss_rir_delay (the lowest index of the maximum), then one direct
+    convolution per RIR set (nbss_fir_convolve) that forms only the N samples from the delay onward; without `rir_target` the same tensor is
+    returned twice.  Device tensors only: a host tensor raises ValueError (`lib` lets the tests hand in the emulator build of the same kernels)."""
+    from nbss_amd import ops
+    if lib is None:
+        if not wav.is_cuda:
+            raise ValueError("convolve='native' runs the HIP kernels and needs tensors on the device; use convolve='fft' on the host")
+        from nbss_amd._lib import hip
+        lib = hip()
+    wav, rir = wav.float().contiguous(), rir.float().contiguous()
+    delay = ops.rir_delay(lib, rir, ref_channel)
+    full = ops.fir_convolve(lib, wav, rir, delay, check=False)  # the delays come from rir_delay: inside [0, L)
+    if rir_target is None:
+        return full, full
+    if rir_target.shape[:3] != rir.shape[:3]:
+        raise ValueError(f"rir_target {tuple(rir_target.shape)} must match rir {tuple(rir.shape)} in [B,S,M]")
+    # a target response shorter than the delay would put it outside [0, L): checked by the kernel (one synchronisation) only in that case
+    return full, ops.fir_convolve(lib, wav, rir_target.float().contiguous(), delay, check=rir_target.shape[-1] != rir.shape[-1])
+
+
+def _check_convolve(convolve: str) -> None:
+    if convolve not in CONVOLVE_MODES:
+        raise ValueError(f"convolve must be 'fft' or 'native', got {convolve!r}")
 
 
 def energy_ratio_coeff(a: Tensor, b: Tensor, target_db: Tensor) -> Tensor:
@@ -92,12 +121,14 @@ def gen_diffuse_noise(noise: Tensor, L: int, Cs: Tensor, nfft: int = 256) -> Ten
 
 
 def mix_batch(cleans: Tensor, rir: Tensor, Cs: Tensor, sir_db: Optional[Tensor], snr_db: Tensor, gen: Optional[torch.Generator], rir_target: Optional[Tensor] = None,
-              nfft: int = 256, white: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Dict[str, Tensor]]:
+              nfft: int = 256, white: Optional[Tensor] = None, convolve: str = 'fft', lib=None) -> Tuple[Tensor, Tensor, Dict[str, Tensor]]:
     """cleans [B,S,N] dry sources, rir [B,S,M,L] -> (mix [B,M,N], targets [B,S,M,N], paras): steps 5-7 of SmsWsjPlusDataset.__getitem__
-    (full overlap) for a whole batch on the device of `cleans`"""
+    (full overlap) for a whole batch on the device of `cleans`.  convolve: 'fft' (torch.fft, the default) or 'native' (convolve_aligned_native:
+    the HIP kernels, device tensors only; `lib` as there)"""
+    _check_convolve(convolve)
     B, S, N = cleans.shape
     M = rir.shape[2]
-    rvbt, tgt = convolve_aligned(cleans, rir, rir_target)
+    rvbt, tgt = convolve_aligned_native(cleans, rir, rir_target, lib=lib) if convolve == 'native' else convolve_aligned(cleans, rir, rir_target)
     if sir_db is not None and S == 2:  # speaker 2 relative to speaker 1
         coeff = energy_ratio_coeff(rvbt[:, 0], rvbt[:, 1], sir_db)
         scale = torch.stack([torch.ones_like(coeff), coeff], 1)[:, :, None, None]
@@ -124,7 +155,9 @@ class SimulatedRoomDataModule:
                  num_channels: int = 6, num_speakers: int = 2, sample_rate: int = 8000, sir: Tuple[float, float] = (-5.0, 5.0),
                  snr: Tuple[float, float] = (0.0, 20.0), rt60: Tuple[float, float] = (0.2, 0.6), array_radius: float = 0.1, seeds: List[int] = (0, 1, 2),
                  device: Optional[str] = None, rir: str = 'synthetic', room_size_lims: Tuple[Tuple[float, float], ...] = ((3.0, 8.0), (3.0, 8.0), (3.0, 4.0)),
-                 mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8)):
+                 mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8), convolve: str = 'fft', conv_lib=None):
+        _check_convolve(convolve)
+        self.convolve, self.conv_lib = convolve, conv_lib  # conv_lib: the tests hand in the emulator library; None = the product library
         if rir not in ('synthetic', 'ism'):
             raise ValueError(f"rir must be 'synthetic' or 'ism', got {rir!r}")
         self.rir, self.room_size_lims, self.mic_zlim, self.spk_zlim = rir, [tuple(l) for l in room_size_lims], tuple(mic_zlim), tuple(spk_zlim)
@@ -133,6 +166,8 @@ class SimulatedRoomDataModule:
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         ang = torch.arange(num_channels) * (2 * math.pi / num_channels)
         self.pos_mics = torch.stack([array_radius * torch.cos(ang), array_radius * torch.sin(ang), torch.zeros(num_channels)], 1)
+        if convolve == 'native' and self.device.type != 'cuda' and conv_lib is None:
+            raise ValueError("convolve='native' runs the HIP kernels and needs a HIP device; use convolve='fft' (one of 'fft', 'native') on the host")
         self.Cs = diffuse_mixing_matrices(self.pos_mics, sample_rate)[1].to(torch.complex64).to(self.device)
 
     def _rirs(self, B: int, gen: torch.Generator) -> Tensor:
@@ -186,6 +221,7 @@ class SimulatedRoomDataModule:
         bs = self.batch_size[min(stage, len(self.batch_size) - 1)]
         items = rank_strided_indices(self.num_samples[stage], rank, world, epoch, self.seeds[stage], shuffle=stage == 0)
         k = torch.hann_window(33, device=self.device)
+        conv = {} if self.convolve == 'fft' else {"convolve": self.convolve, "lib": self.conv_lib}
         for i in range(0, len(items) - bs + 1, bs):
             chunk = items[i:i + bs]
             gen = torch.Generator(device=self.device).manual_seed(int(chunk[0][1]) * 1000003 + int(chunk[0][0]))
@@ -195,8 +231,8 @@ class SimulatedRoomDataModule:
             snr = self.snr[0] + (self.snr[1] - self.snr[0]) * torch.rand(bs, generator=gen, device=self.device)
             if self.rir == 'ism':  # the targets are the direct-path images
                 rir, rir_dp = self._ism_rirs(bs, gen)
-                mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp)
+                mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp, **conv)
             else:
-                mix, tgt, paras = mix_batch(src, self._rirs(bs, gen), self.Cs, sir if self.S == 2 else None, snr, gen)
+                mix, tgt, paras = mix_batch(src, self._rirs(bs, gen), self.Cs, sir if self.S == 2 else None, snr, gen, **conv)
             yield mix, tgt, [{"index": ix, "seed": sd, "sample_rate": self.sr, "snr": float(paras["snr"][j]), "sir": float(sir[j])}
                              for j, (ix, sd) in enumerate(chunk)]

@@ -264,6 +264,25 @@ int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double
  * Same limits as nbss_rir_ism with k_d > 0. */
 int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream);
 
+/* ---- RIR convolution of the on-device simulator (csrc/conv1d.hip; data_loaders/gpu_simulation.py: convolve_aligned_native) ---------------------
+ * What the reference's convolve(wav, rir, rir_target, ref_channel, align=True) keeps of its full convolutions (utils/mix.py:122-134): the N samples
+ * from the direct-path delay of the reference channel onward.
+ * nbss_rir_delay: h [B][S][M][L] fp32 -> delay [B][S] int32 = the index of the maximum of h[b][s][ref_channel][:] (mix.py:130, np.argmax); on a tie
+ * the LOWEST index wins.  A row that holds a NaN has no defined maximum (the call does not fail).  0 <= ref_channel < M, else NBSS_EINVAL.
+ * nbss_fir_convolve: x [B][S][N], h [B][S][M][L] fp32, delay [B][S] int32 (a DEVICE array) -> y [B][S][M][N] fp32,
+ *   y[b][s][m][n] = sum_{k < L} h[b][s][m][k] x[b][s][n + delay[b][s] - k],   terms whose x index lies outside [0, N) are zero
+ * (mix.py:127,133: fftconvolve(mode='full')[delay : delay + N]); only this window of the linear convolution is formed.  A direct convolution on
+ * the exact-fp32 matrix cores: every product is rounded once, the sum is an fp32 fmaf chain in an order fixed by n and L alone.  No atomics: two
+ * calls give the same bits, and an item's result does not depend on the batch.  Any N >= 1 and L >= 1; rows on 16-byte boundaries (N % 4 == 0,
+ * L % 4 == 0, base pointers aligned) are read with 16-byte loads, any other shape element by element.
+ * The delays are validated on the device: one outside [0, L) is clamped into that range and `status` (one int32 on the device, or NULL; the caller
+ * zeroes it) is set to 1; the call itself returns 0, and the caller who reads a non-zero status treats the result as NBSS_EINVAL (ops.fir_convolve).
+ * NBSS_EINVAL: N < 1, L < 1.  Limits (NBSS_EUNSUPPORTED outside): L <= 65536 (the longest response nbss_rir_ism writes), N <= 2^24, M <= 4096,
+ * B S M <= 2^22; B, S, M >= 1.  The kernel's LDS image (2048 taps of 3 microphones and the matching strip of x: 48 KB) does not grow with L, and
+ * (b, s) pairs beyond 2048 are walked by the same grid.  y may not alias x or h.  No workspace. */
+int nbss_rir_delay(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, void* stream);
+int nbss_fir_convolve(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, void* stream);
+
 /* clip_grad_norm_(max_norm, L2) + torch.optim.Adam(W) step on the flat fp32 buffers
  * (configs/SpatialNet.yaml:3-4,44; general_steps.py:243-271).  grads are first multiplied by
  * grad_scale (1/world_size after a SUM all-reduce).  scratch: >= 258 floats; scratch[0] returns the

@@ -49,6 +49,8 @@ int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img);
 int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
                  const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
 int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, hipStream_t st);
+int rir_delay_impl(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, hipStream_t st);
+int fir_convolve_impl(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, hipStream_t st);
 int clip_adam_dev_impl(size_t n, float* p, float* g, float* m, float* v, float* scal, const float* hyper, float max_norm, float grad_scale, float beta1,
                        float beta2, float eps, float wd, int flags, hipStream_t st);
 int adam_hyper_impl(int step, float lr, float beta1, float beta2, float* out);
@@ -518,6 +520,16 @@ int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double
 int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream) {
     if (!rt60 || !h) return NBSS_EINVAL;
     return rir_tail_impl(B, S, M, n_samples, fs, tw, k_d, rt60, seed, h, (hipStream_t)stream);
+}
+
+int nbss_rir_delay(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, void* stream) {
+    if (!h || !delay) return NBSS_EINVAL;
+    return rir_delay_impl(B, S, M, L, ref_channel, h, delay, (hipStream_t)stream);
+}
+
+int nbss_fir_convolve(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, void* stream) {
+    if (!x || !h || !delay || !y) return NBSS_EINVAL;
+    return fir_convolve_impl(B, S, M, N, L, x, h, delay, y, status, (hipStream_t)stream);
 }
 
 int nbss_clip_adam_step(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* scratch, float max_norm,

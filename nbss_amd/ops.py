@@ -376,6 +376,35 @@ def rir_ism(lib, room_sz, beta, pos_src, pos_rcv, nb_img, n_samples: int, fs: fl
     return h
 
 
+def rir_delay(lib, h, ref_channel: int = 0):
+    """h [B,S,M,L] fp32 -> delay [B,S] int32: the index of the maximum of h[b,s,ref_channel,:], the lowest one on a tie (nbss_rir_delay)"""
+    if h.dim() != 4:
+        raise NbssError(f"rir_delay: h {tuple(h.shape)} must be [B,S,M,L]")
+    B, S, M, L = h.shape
+    delay = torch.empty(B, S, dtype=torch.int32, device=h.device)
+    lib.call("nbss_rir_delay", B, S, M, L, int(ref_channel), _ptr(lib, h, torch.float32), _ptr(lib, delay), _stream(lib, h))
+    return delay
+
+
+def fir_convolve(lib, x, h, delay, check: bool = True, out=None):
+    """x [B,S,N], h [B,S,M,L] fp32, delay [B,S] int32 on the same device -> y [B,S,M,N] fp32 with y[b,s,m,n] = sum_k h[b,s,m,k] x[b,s,n + delay[b,s] - k]
+    (nbss_fir_convolve: the window of the linear convolution that starts at the delay).  The kernel validates the delays; with `check` the status word
+    is read back (one synchronisation) and a delay outside [0, L) raises NBSS_EINVAL.  check=False is for delays that come from rir_delay."""
+    if x.dim() != 3 or h.dim() != 4 or h.shape[:2] != x.shape[:2] or tuple(delay.shape) != tuple(x.shape[:2]):
+        raise NbssError(f"fir_convolve: x {tuple(x.shape)} must be [B,S,N], h {tuple(h.shape)} [B,S,M,L] and delay {tuple(delay.shape)} [B,S]")
+    B, S, N = x.shape
+    M, L = h.shape[2], h.shape[3]
+    y = torch.empty(B, S, M, N, dtype=torch.float32, device=x.device) if out is None else out
+    if y.shape != (B, S, M, N):
+        raise NbssError(f"fir_convolve: out must be [B,S,M,N] = {(B, S, M, N)}, got {tuple(y.shape)}")
+    status = torch.zeros(1, dtype=torch.int32, device=x.device) if check else None
+    lib.call("nbss_fir_convolve", B, S, M, N, L, _ptr(lib, x, torch.float32), _ptr(lib, h, torch.float32), _ptr(lib, delay, torch.int32),
+             _ptr(lib, y, torch.float32), _ptr(lib, status), _stream(lib, x))
+    if check and int(status.item()) != 0:
+        raise NbssError(f"nbss_fir_convolve failed: {_ERR[-1]}: a delay lies outside [0, L = {L})")
+    return y
+
+
 def clip_adam_step(lib, params, grads, exp_avg, exp_avg_sq, scratch, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                    max_norm=5.0, grad_scale=1.0, zero_grad=True, decoupled_weight_decay=False):
     lib.call("nbss_clip_adam_step", params.numel(), _ptr(lib, params, torch.float32), _ptr(lib, grads, torch.float32), _ptr(lib, exp_avg, torch.float32),
