@@ -9,7 +9,9 @@ noises).  Everything is torch (hipFFT / rocSOLVER through torch-ROCm) and device
 scipy and, when the reference tree is present, against the reference's own functions.
 The corpora (WSJ0, measured/simulated RIR sets) are not available here: `SimulatedRoomDataModule` draws band-limited random
 sources and, by default, synthetic exponentially decaying RIRs; with rir='ism' it draws shoebox rooms and computes their impulse
-responses by the image-source method on the device (nbss_amd/rir.py: simulate_rir).  `mix_batch` itself takes any sources / RIRs."""
+responses by the image-source method on the device (nbss_amd/rir.py: simulate_rir), and with moving=(vmin, vmax[, prob]) the speakers walk:
+a trajectory of responses per speaker, cross-faded along the source (utils/mix.py:197-244; convolve_traj_aligned, csrc/conv_traj.hip).
+`mix_batch` itself takes any sources / RIRs."""
 import math
 from typing import Dict, List, Optional, Tuple
 
@@ -67,6 +69,105 @@ def _check_convolve(convolve: str) -> None:
         raise ValueError(f"convolve must be 'fft' or 'native', got {convolve!r}")
 
 
+TRAJ_MODES = ('switch', 'trapezium')
+
+
+def traj_rirs_needed(N: int, hop: int, mode: str = 'trapezium') -> int:
+    """RIRs that N source samples need at `hop` samples per trajectory point: ceil(N / hop) when switched (mix.py:171-174), ceil((N + hop - 1) / hop)
+    when cross-faded (mix.py:231, len(range(0, N + hop - 1, hop)))"""
+    return -(-N // hop) if mode == 'switch' else -(-(N + hop - 1) // hop)
+
+
+def traj_weights(N: int, hop, mode: str = 'trapezium', ramp: int = 20, P: Optional[int] = None, dtype=torch.float32, device=None) -> Tensor:
+    """w [..., P, N]: the weight with which RIR p of a trajectory hears the source sample j, for `hop` (an int, or an integer tensor [...]) samples
+    per trajectory point.  With q = j // hop and r = j % hop, 'switch' (mix.py:151-194, convolve_traj) gives RIR q the weight 1; 'trapezium'
+    (mix.py:197-244, convolve_traj_with_win(..., f'trapezium{ramp}')) gives RIR q the weight down(r) and RIR q + 1 the weight up(r): the two halves
+    of the reference's window [zeros(z), arange(ramp) / (ramp - 1), ones(2 o), the ramp reversed, zeros(z)], z = (hop - ramp) // 2, o = hop - ramp - z.
+    P defaults to what the smallest hop needs; a larger P gives zero rows."""
+    if mode not in TRAJ_MODES:
+        raise ValueError(f"traj mode must be 'switch' or 'trapezium', got {mode!r}")
+    hop = torch.as_tensor(hop, device=device).long()
+    hmin = int(hop.min())
+    if hmin < 1 or (mode == 'trapezium' and (ramp < 2 or hmin <= ramp)):
+        raise ValueError(f"every hop must be >= 1, and > ramp = {ramp} >= 2 for the trapezium window; the smallest hop is {hmin}")
+    need = traj_rirs_needed(N, hmin, mode)
+    P = need if P is None else P
+    if P < need:
+        raise ValueError(f"{P} trajectory points are too few for {N} samples at {hmin} samples per point in mode {mode!r}: {need} are needed")
+    return torch.stack([_traj_weight_row(N, hop, p, mode, ramp, dtype) for p in range(P)], -2)
+
+
+def _traj_weight_row(N: int, hop: Tensor, p: int, mode: str, ramp: int, dtype) -> Tensor:
+    """w_p [..., N] of traj_weights for one trajectory point (hop an integer tensor [...], already validated)"""
+    H = hop[..., None]
+    t = torch.arange(N, device=hop.device) - p * H          # the source sample relative to the point's own segment [p H, (p + 1) H)
+    here = (t >= 0) & (t < H)
+    if mode == 'switch':
+        return here.to(dtype)
+    z = (H - ramp) // 2
+    o = H - ramp - z
+    down = ((ramp - 1 - (t - o)).to(dtype) / (ramp - 1)).clamp(0, 1)   # heard through `down` inside the own segment ...
+    up = ((t + H - z).to(dtype) / (ramp - 1)).clamp(0, 1)               # ... and through `up` inside the segment before it
+    return here.to(dtype) * down + ((t >= -H) & (t < 0)).to(dtype) * up
+
+
+def convolve_traj_aligned(wav: Tensor, rir: Tensor, hop: Tensor, rir_target: Optional[Tensor] = None, mode: str = 'trapezium', ramp: int = 20,
+                          ref_channel: int = 0, convolve: str = 'fft', lib=None) -> Tuple[Tensor, Tensor]:
+    """wav [B,S,N], rir [B,S,P,M,L] (one RIR set per trajectory point), hop [B,S] (source samples per trajectory point) -> (reverberant image, target
+    image) [B,S,M,N] of MOVING sources: the time-varying convolution of traj_weights, both cut from the direct-path delay of the reference channel at
+    the FIRST trajectory point of `rir_target` (of `rir` without one), as chime3_moving.py:202-204 does.
+    convolve: 'fft' (the default, any device: one fft_convolve of the weighted source per trajectory point, accumulated) or 'native'
+    (nbss_fir_convolve_traj, csrc/conv_traj.hip: device tensors only, `lib` as in convolve_aligned_native)."""
+    _check_convolve(convolve)
+    if mode not in TRAJ_MODES:
+        raise ValueError(f"traj mode must be 'switch' or 'trapezium', got {mode!r}")
+    if wav.dim() != 3 or rir.dim() != 5 or rir.shape[:2] != wav.shape[:2] or tuple(hop.shape) != tuple(wav.shape[:2]):
+        raise ValueError(f"wav {tuple(wav.shape)} must be [B,S,N], rir {tuple(rir.shape)} [B,S,P,M,L] and hop {tuple(hop.shape)} [B,S]")
+    if rir_target is not None and rir_target.shape[:4] != rir.shape[:4]:
+        raise ValueError(f"rir_target {tuple(rir_target.shape)} must match rir {tuple(rir.shape)} in [B,S,P,M]")
+    B, S, N = wav.shape
+    P, M = rir.shape[2], rir.shape[3]
+    first = (rir if rir_target is None else rir_target)[:, :, 0]  # [B,S,M,L']: the delay is that of the first trajectory point
+    if convolve == 'native':
+        from nbss_amd import ops
+        if lib is None:
+            if not wav.is_cuda:
+                raise ValueError("convolve='native' runs the HIP kernels and needs tensors on the device; use convolve='fft' on the host")
+            from nbss_amd._lib import hip
+            lib = hip()
+        wav, rir, hop32 = wav.float().contiguous(), rir.float().contiguous(), hop.to(torch.int32).contiguous()
+        delay = ops.rir_delay(lib, first.float().contiguous(), ref_channel)
+        # one status read-back (a synchronisation) covers the hops and P of both calls; the delay comes from the target and is inside its [0, L')
+        try:
+            full = ops.fir_convolve_traj(lib, wav, rir, hop32, delay, mode=mode, ramp=ramp, check=True)
+        except ops.NbssError as e:
+            raise ValueError(str(e)) from e
+        if rir_target is None:
+            return full, full
+        return full, ops.fir_convolve_traj(lib, wav, rir_target.float().contiguous(), hop32, delay, mode=mode, ramp=ramp, check=False)
+    hop = hop.to(wav.device).long()
+    hmin = int(hop.min())
+    if hmin < 1 or (mode == 'trapezium' and (ramp < 2 or hmin <= ramp)):
+        raise ValueError(f"every hop must be >= 1, and > ramp = {ramp} >= 2 for the trapezium window; the smallest hop is {hmin}")
+    if P < traj_rirs_needed(N, hmin, mode):
+        raise ValueError(f"{P} trajectory points are too few for {N} samples at {hmin} samples per point in mode {mode!r}: "
+                         f"{traj_rirs_needed(N, hmin, mode)} are needed")
+    delay = first[:, :, ref_channel].argmax(-1)
+    idx = (delay[:, :, None, None] + torch.arange(N, device=wav.device)[None, None, None, :]).expand(B, S, M, N)
+
+    def image(h: Tensor) -> Tensor:
+        if h.shape[-1] <= int(delay.max()):
+            raise ValueError(f"a delay of {int(delay.max())} lies outside the response of {h.shape[-1]} samples")
+        full = None
+        for p in range(P):  # the weight row of one point at a time: [B,S,N], never [B,S,P,N]
+            part = fft_convolve((wav * _traj_weight_row(N, hop, p, mode, ramp, wav.dtype))[:, :, None, :], h[:, :, p])
+            full = part if full is None else full + part
+        return full.gather(-1, idx)
+
+    full = image(rir)
+    return full, (full if rir_target is None else image(rir_target))
+
+
 def energy_ratio_coeff(a: Tensor, b: Tensor, target_db: Tensor) -> Tensor:
     """factor for `b` such that 10 log10(mean(a^2) / mean((coeff b)^2)) = target_db; a, b [B,...], target_db [B] (mix.py:328-346)"""
     ea = a.reshape(a.shape[0], -1).pow(2).mean(1)
@@ -121,14 +222,22 @@ def gen_diffuse_noise(noise: Tensor, L: int, Cs: Tensor, nfft: int = 256) -> Ten
 
 
 def mix_batch(cleans: Tensor, rir: Tensor, Cs: Tensor, sir_db: Optional[Tensor], snr_db: Tensor, gen: Optional[torch.Generator], rir_target: Optional[Tensor] = None,
-              nfft: int = 256, white: Optional[Tensor] = None, convolve: str = 'fft', lib=None) -> Tuple[Tensor, Tensor, Dict[str, Tensor]]:
+              nfft: int = 256, white: Optional[Tensor] = None, convolve: str = 'fft', lib=None, traj_hop: Optional[Tensor] = None,
+              traj_mode: str = 'trapezium', traj_ramp: int = 20) -> Tuple[Tensor, Tensor, Dict[str, Tensor]]:
     """cleans [B,S,N] dry sources, rir [B,S,M,L] -> (mix [B,M,N], targets [B,S,M,N], paras): steps 5-7 of SmsWsjPlusDataset.__getitem__
     (full overlap) for a whole batch on the device of `cleans`.  convolve: 'fft' (torch.fft, the default) or 'native' (convolve_aligned_native:
-    the HIP kernels, device tensors only; `lib` as there)"""
+    the HIP kernels, device tensors only; `lib` as there).  Moving sources: rir [B,S,P,M,L] together with traj_hop [B,S] goes through
+    convolve_traj_aligned (traj_mode, traj_ramp as there); everything after the convolution is the same."""
     _check_convolve(convolve)
     B, S, N = cleans.shape
-    M = rir.shape[2]
-    rvbt, tgt = convolve_aligned_native(cleans, rir, rir_target, lib=lib) if convolve == 'native' else convolve_aligned(cleans, rir, rir_target)
+    M = rir.shape[-2]
+    if (rir.dim() == 5) != (traj_hop is not None):
+        raise ValueError(f"a trajectory needs both rir [B,S,P,M,L] and traj_hop [B,S]; got rir {tuple(rir.shape)} and traj_hop "
+                         f"{None if traj_hop is None else tuple(traj_hop.shape)}")
+    if traj_hop is not None:
+        rvbt, tgt = convolve_traj_aligned(cleans, rir, traj_hop, rir_target, mode=traj_mode, ramp=traj_ramp, convolve=convolve, lib=lib)
+    else:
+        rvbt, tgt = convolve_aligned_native(cleans, rir, rir_target, lib=lib) if convolve == 'native' else convolve_aligned(cleans, rir, rir_target)
     if sir_db is not None and S == 2:  # speaker 2 relative to speaker 1
         coeff = energy_ratio_coeff(rvbt[:, 0], rvbt[:, 1], sir_db)
         scale = torch.stack([torch.ones_like(coeff), coeff], 1)[:, :, None, None]
@@ -155,8 +264,18 @@ class SimulatedRoomDataModule:
                  num_channels: int = 6, num_speakers: int = 2, sample_rate: int = 8000, sir: Tuple[float, float] = (-5.0, 5.0),
                  snr: Tuple[float, float] = (0.0, 20.0), rt60: Tuple[float, float] = (0.2, 0.6), array_radius: float = 0.1, seeds: List[int] = (0, 1, 2),
                  device: Optional[str] = None, rir: str = 'synthetic', room_size_lims: Tuple[Tuple[float, float], ...] = ((3.0, 8.0), (3.0, 8.0), (3.0, 4.0)),
-                 mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8), convolve: str = 'fft', conv_lib=None):
+                 mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8), convolve: str = 'fft', conv_lib=None,
+                 moving: Optional[Tuple[float, ...]] = None, traj_dist: float = 0.05):
         _check_convolve(convolve)
+        self.moving, self.traj_dist = None, float(traj_dist)
+        if moving is not None:  # (vmin, vmax) or (vmin, vmax, prob) in m/s, named after the reference's 'moving(0.12,0.4[,p])' datasets
+            if rir != 'ism':
+                raise ValueError(f"moving speakers need trajectories of image-source responses: rir must be 'ism', got {rir!r}")
+            mv = tuple(float(v) for v in moving)
+            if len(mv) not in (2, 3) or not 0.0 < mv[0] <= mv[1] or not 0.0 <= (mv[2] if len(mv) == 3 else 1.0) <= 1.0 or traj_dist <= 0:
+                raise ValueError(f"moving must be (vmin, vmax) or (vmin, vmax, prob) with 0 < vmin <= vmax and 0 <= prob <= 1, traj_dist > 0; got {moving!r}, "
+                                 f"{traj_dist!r}")
+            self.moving = (mv[0], mv[1], mv[2] if len(mv) == 3 else 1.0)
         self.convolve, self.conv_lib = convolve, conv_lib  # conv_lib: the tests hand in the emulator library; None = the product library
         if rir not in ('synthetic', 'ism'):
             raise ValueError(f"rir must be 'synthetic' or 'ism', got {rir!r}")
@@ -216,6 +335,56 @@ class SimulatedRoomDataModule:
         rir_dp = simulate_rir(geo[0], torch.zeros_like(geo[1]), geo[2], geo[3], (1, 1, 1), sc["n_samples"], self.sr)
         return rir.float(), rir_dp.float()
 
+    TRAJ_RAMP = 20         # the reference's 'trapezium20'
+    TRAJ_WAVELENGTH = 2.0  # of the lateral wobble, in metres walked
+    TRAJ_WOBBLE = 0.2      # its largest amplitude in metres: the slope stays below 0.2 * 2 pi / 2 = 0.63, adjacent points below 1.19 traj_dist
+
+    def _trajectory(self, sc: Dict[str, Tensor], P: int, gen: torch.Generator) -> Tensor:
+        """[B,S,P,3]: from each drawn speaker position, steps of traj_dist along a drawn horizontal direction with a sinusoidal lateral wobble
+        (amplitude, phase drawn), reflected back into the speaker box (0.3 m from the side walls); the height stays.  After the idea of the
+        reference's '4points+sin' trajectories (generate_rirs.py:389-446), not its draws."""
+        dev, B = self.device, sc["pos_src"].shape[0]
+        u = lambda *shape: torch.rand(*shape, generator=gen, device=dev, dtype=torch.float64)
+        theta, amp, phase = 2.0 * math.pi * u(B, self.S), self.TRAJ_WOBBLE * u(B, self.S), 2.0 * math.pi * u(B, self.S)
+        along = self.traj_dist * torch.arange(P, device=dev, dtype=torch.float64)                                   # [P]
+        side = amp[..., None] * (torch.sin(2.0 * math.pi * along / self.TRAJ_WAVELENGTH + phase[..., None]) - torch.sin(phase)[..., None])  # [B,S,P], 0 at the start
+        e = torch.stack([torch.cos(theta), torch.sin(theta)], -1)[:, :, None, :]                                    # [B,S,1,2]
+        en = torch.stack([-torch.sin(theta), torch.cos(theta)], -1)[:, :, None, :]
+        xy = sc["pos_src"][:, :, None, :2] + along[None, None, :, None] * e + side[..., None] * en                   # [B,S,P,2]
+        lo, width = 0.3, (sc["room_sz"][:, None, None, :2] - 0.6)
+        t = torch.remainder(xy - lo, 2.0 * width)                                                                   # reflect at both faces of the box
+        xy = lo + torch.where(t > width, 2.0 * width - t, t)
+        return torch.cat([xy, sc["pos_src"][:, :, None, 2:].expand(B, self.S, P, 1)], -1)
+
+    def _traj_draws(self, B: int, N: int, gen: torch.Generator) -> Tuple[Dict[str, Tensor], Tensor, Tensor, Tensor]:
+        """the scene, the samples per trajectory point hop [B,S] int32, the speeds [B,S] in m/s (0 for a speaker that stands) and the trajectory points
+        [B,S,P,3] of B items of N samples.  Every speaker draws its own speed (the reference draws one and, through a truncating zip, moves only the
+        first speaker); P is what the smallest hop of the batch needs; a standing speaker has one point P times."""
+        sc = self._ism_scene(B, gen)
+        u = lambda *shape: torch.rand(*shape, generator=gen, device=self.device, dtype=torch.float64)
+        vmin, vmax, prob = self.moving
+        speed = vmin + (vmax - vmin) * u(B, self.S)
+        walks = u(B, self.S) < prob
+        hop = torch.round(self.traj_dist / speed * self.sr).to(torch.int32)
+        hmin = int(hop.min())
+        if hmin <= self.TRAJ_RAMP:
+            raise ValueError(f"traj_dist / vmax * sample_rate = {hmin} samples per trajectory point must exceed the window's ramp of {self.TRAJ_RAMP}")
+        pts = self._trajectory(sc, traj_rirs_needed(N, hmin, 'trapezium'), gen)
+        pts = torch.where(walks[:, :, None, None], pts, pts[:, :, :1].expand_as(pts))
+        return sc, hop, torch.where(walks, speed, torch.zeros_like(speed)), pts
+
+    def _ism_traj_rirs(self, B: int, N: int, gen: torch.Generator) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """(reverberant, direct-path) RIRs [B,S,P,M,L] along the trajectories of _traj_draws, with its hop and speeds: one simulate_rir call each,
+        with the trajectory points as sources"""
+        from nbss_amd.rir import simulate_rir
+        sc, hop, speed, pts = self._traj_draws(B, N, gen)
+        P = pts.shape[2]
+        src = pts.reshape(B, self.S * P, 3)
+        rir = simulate_rir(sc["room_sz"], sc["beta"], src, sc["pos_rcv"], sc["nb_img"], sc["n_samples"], self.sr)
+        rir_dp = simulate_rir(sc["room_sz"], torch.zeros_like(sc["beta"]), src, sc["pos_rcv"], (1, 1, 1), sc["n_samples"], self.sr)
+        shape = (B, self.S, P, self.C, sc["n_samples"])
+        return rir.float().reshape(shape), rir_dp.float().reshape(shape), hop, speed
+
     def batches(self, stage: int, rank: int = 0, world: int = 1, epoch: int = 0):
         N = int(self.audio_time_len[stage] * self.sr)
         bs = self.batch_size[min(stage, len(self.batch_size) - 1)]
@@ -229,6 +398,14 @@ class SimulatedRoomDataModule:
             src = torch.nn.functional.conv1d(src, (k / k.sum())[None, None], padding=16).reshape(bs, self.S, N) * 3.0
             sir = self.sir[0] + (self.sir[1] - self.sir[0]) * torch.rand(bs, generator=gen, device=self.device)
             snr = self.snr[0] + (self.snr[1] - self.snr[0]) * torch.rand(bs, generator=gen, device=self.device)
+            if self.moving is not None:  # moving speakers: trajectories of image-source responses, cross-faded along the source
+                rir, rir_dp, hop, speed = self._ism_traj_rirs(bs, N, gen)
+                mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp, traj_hop=hop,
+                                            traj_ramp=self.TRAJ_RAMP, **conv)
+                speed = speed.tolist()
+                yield mix, tgt, [{"index": ix, "seed": sd, "sample_rate": self.sr, "snr": float(paras["snr"][j]), "sir": float(sir[j]), "speed": speed[j]}
+                                 for j, (ix, sd) in enumerate(chunk)]
+                continue
             if self.rir == 'ism':  # the targets are the direct-path images
                 rir, rir_dp = self._ism_rirs(bs, gen)
                 mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp, **conv)

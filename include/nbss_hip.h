@@ -283,6 +283,35 @@ int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int 
 int nbss_rir_delay(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, void* stream);
 int nbss_fir_convolve(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, void* stream);
 
+/* ---- RIR convolution along a trajectory: moving sources (csrc/conv_traj.hip; data_loaders/gpu_simulation.py: convolve_traj_aligned) -------------
+ * nbss_fir_convolve_traj: x [B][S][N] dry sources, h [B][S][P][M][L] one RIR set per trajectory point, hop [B][S] int32 (a DEVICE array: source
+ * samples per trajectory point), delay [B][S] int32 (a DEVICE array, as nbss_fir_convolve's) -> y [B][S][M][N], all fp32.  For item (b, s) let
+ * H = hop[b][s], d = delay[b][s], and for a source sample j in [0, N) q = j / H, r = j % H.  x[j] is heard through at most two RIRs:
+ *   mode 0 (switch; the reference's convolve_traj with an integer samples_per_rir, utils/mix.py:151-194): RIR q with weight 1;
+ *   mode 1 (trapezium; convolve_traj_with_win(..., 'trapezium{ramp}'), mix.py:197-244): RIR q with weight down(r) and RIR q + 1 with weight up(r),
+ *     with z = (H - ramp) / 2 (floor) and o = H - ramp - z:
+ *     up(r)   = 0 for r < z;  (r - z) / (ramp - 1) for z <= r < z + ramp;  1 from there on,
+ *     down(r) = 1 for r < o;  (ramp - 1 - (r - o)) / (ramp - 1) for o <= r < o + ramp;  0 from there on.
+ * With the weights w_p(j) so defined,
+ *   y[b][s][m][n] = sum_{k < L} sum_p w_p(j) h[b][s][p][m][k] x[b][s][j],   j = n + d - k,   terms with j outside [0, N) are zero:
+ * full[:, d : d + N] of the reference functions (chime3_moving.py:204, mix.py:247-252).  Mode 1 with N < H is defined by the same closed form.
+ * Required P: mode 0 ceil(N / H); mode 1 ceil((N + H - 1) / H) (the reference's len(range(0, N + hop - 1, hop))).  With that many, an index >= P is
+ * reached only with weight 0 (up(0) = 0) and is NOT read; more RIRs than required are allowed and are never read.
+ * A direct convolution on the exact-fp32 matrix cores, one pass per trajectory point that an output tile of 256 samples can hear: x w_p is rounded
+ * once to fp32, and its product with a tap is fused into the fp32 fmaf chain, so every product of the sum is rounded once; the order of an output's
+ * sum is fixed by n, L, H and d of its item alone.  No atomics, every output is stored exactly once, two calls give the same bits, an item's result
+ * does not depend on the batch it shares a launch with, and there is no workspace.  Rows on 16-byte boundaries (N % 4 == 0, L % 4 == 0, base
+ * pointers aligned) are read with 16-byte loads, any other shape element by element.
+ * The items are validated on the device: an item with H < 1, in mode 1 with H <= ramp or ramp < 2, or with a P too small for its H gets zeros in y;
+ * a delay outside [0, L) is clamped into that range, as by nbss_fir_convolve.  In both cases `status` (one int32 on the device, or NULL; the caller
+ * zeroes it) is set to 1; the call itself returns 0, and the caller who reads a non-zero status treats the result as NBSS_EINVAL
+ * (ops.fir_convolve_traj).  In mode 0 `ramp` is ignored.
+ * NBSS_EINVAL: N < 1, L < 1, P < 1, mode outside {0, 1}.  Limits (NBSS_EUNSUPPORTED outside): those of nbss_fir_convolve applied to the B S P M
+ * rows of h: L <= 65536, N <= 2^24, M <= 4096, B S P M <= 2^22; B, S, M >= 1.  The kernel's LDS image (39 KB) does not grow with L, H or P, and
+ * (b, s) pairs beyond 2048 are walked by the same grid.  y may not alias x or h. */
+int nbss_fir_convolve_traj(int B, int S, int P, int M, int N, int L, int mode, int ramp, const float* x, const float* h, const int32_t* hop,
+                           const int32_t* delay, float* y, int32_t* status, void* stream);
+
 /* clip_grad_norm_(max_norm, L2) + torch.optim.Adam(W) step on the flat fp32 buffers
  * (configs/SpatialNet.yaml:3-4,44; general_steps.py:243-271).  grads are first multiplied by
  * grad_scale (1/world_size after a SUM all-reduce).  scratch: >= 258 floats; scratch[0] returns the

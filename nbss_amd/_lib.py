@@ -94,6 +94,7 @@ SIGNATURES = {
     "nbss_rir_tail": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, _I, _P, C.c_int64, _P, _P]),
     "nbss_rir_delay": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
     "nbss_fir_convolve": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "nbss_fir_convolve_traj": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "nbss_online_encoder_step": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "nbss_online_ret_step": (_I, [_I, _I] + [_P] * 12),
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),

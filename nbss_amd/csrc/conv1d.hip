@@ -29,6 +29,7 @@
 // A delay outside [0, L) is clamped into the range and reported through the status word (a plain store of 1 by thread 0 of the workgroups that meet it).
 #include "launch.h"
 #include "layout.h"
+#include "conv_common.h"
 
 #define CONV_THREADS 256
 #define CONV_TILE 256                       // outputs of one MFMA tile: 16 rows i x 16 columns c
@@ -39,22 +40,9 @@
 #define CONV_TMAX ((CONV_QMAX + 15 + 3) / 4)  // K steps per chunk: the columns w = u + 15 = 0 .. q_count + 14, four per step
 #define CONV_HS 161                         // row of HT in floats: j = i + w <= 15 + 4 CONV_TMAX - 1 = 158
 #define CONV_XS (CONV_NT + 16 * (4 * CONV_TMAX - 1) + 20)  // strip in floats, a multiple of 4: the last read is at CONV_NT + 16 w_max - 223 + 3
-#define CONV_MAX_L 65536
-#define CONV_MAX_N (1 << 24)
-#define CONV_MAX_M 4096
-#define CONV_MAX_ROWS (1 << 22)             // B S M
-#define CONV_MAX_ITEMS 2048                 // (b, s) pairs per grid pass; a workgroup walks the others in steps of the grid
 
 static_assert(CONV_XS % 4 == 0 && (16 * CONV_HS) % 4 == 0, "the strip is staged in 16-byte pieces");
 static_assert(15 + 4 * CONV_TMAX - 1 < CONV_HS, "HT row too short");
-
-NBSS_DEV f32x4 conv_mfma(float a, float b, f32x4 c) {
-#ifdef NBSS_EMU
-    return hipemu::mfma_16x16x4_f32(a, b, c);
-#else
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#endif
-}
 
 __global__ __launch_bounds__(CONV_THREADS) void rir_delay_kernel(int BS, int M, int L, int ref, const float* __restrict__ h, int32_t* __restrict__ delay) {
     NBSS_LDS(smem);

@@ -405,6 +405,35 @@ def fir_convolve(lib, x, h, delay, check: bool = True, out=None):
     return y
 
 
+TRAJ_MODES = {'switch': 0, 'trapezium': 1}
+
+
+def fir_convolve_traj(lib, x, h, hop, delay, mode: str = 'trapezium', ramp: int = 20, check: bool = True, out=None):
+    """x [B,S,N], h [B,S,P,M,L] fp32 (one RIR set per trajectory point), hop [B,S] and delay [B,S] int32 on the same device -> y [B,S,M,N] fp32: the
+    source sample j is heard through RIR j // hop (mode 'switch') or cross-faded between RIRs j // hop and j // hop + 1 by a trapezium window with
+    `ramp` samples per slope (mode 'trapezium'), and the result is the window of the full convolution that starts at the delay
+    (nbss_fir_convolve_traj; include/nbss_hip.h has the closed form).  The kernel validates the items; with `check` the status word is read back (one
+    synchronisation) and a hop < 1, a hop <= ramp or ramp < 2 when cross-fading, too few trajectory points or a delay outside [0, L) raise NBSS_EINVAL."""
+    if mode not in TRAJ_MODES:
+        raise NbssError(f"fir_convolve_traj: mode must be 'switch' or 'trapezium', got {mode!r}")
+    if (x.dim() != 3 or h.dim() != 5 or h.shape[:2] != x.shape[:2] or tuple(hop.shape) != tuple(x.shape[:2])
+            or tuple(delay.shape) != tuple(x.shape[:2])):
+        raise NbssError(f"fir_convolve_traj: x {tuple(x.shape)} must be [B,S,N], h {tuple(h.shape)} [B,S,P,M,L], hop {tuple(hop.shape)} and "
+                        f"delay {tuple(delay.shape)} [B,S]")
+    B, S, N = x.shape
+    P, M, L = h.shape[2:]
+    y = torch.empty(B, S, M, N, dtype=torch.float32, device=x.device) if out is None else out
+    if y.shape != (B, S, M, N):
+        raise NbssError(f"fir_convolve_traj: out must be [B,S,M,N] = {(B, S, M, N)}, got {tuple(y.shape)}")
+    status = torch.zeros(1, dtype=torch.int32, device=x.device) if check else None
+    lib.call("nbss_fir_convolve_traj", B, S, P, M, N, L, TRAJ_MODES[mode], int(ramp), _ptr(lib, x, torch.float32), _ptr(lib, h, torch.float32),
+             _ptr(lib, hop, torch.int32), _ptr(lib, delay, torch.int32), _ptr(lib, y, torch.float32), _ptr(lib, status), _stream(lib, x))
+    if check and int(status.item()) != 0:
+        raise NbssError(f"nbss_fir_convolve_traj failed: {_ERR[-1]}: a hop is < 1{' or <= ramp, ramp is < 2' if mode == 'trapezium' else ''}, P = {P} "
+                        f"trajectory points are too few for a hop, or a delay lies outside [0, L = {L})")
+    return y
+
+
 def clip_adam_step(lib, params, grads, exp_avg, exp_avg_sq, scratch, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                    max_norm=5.0, grad_scale=1.0, zero_grad=True, decoupled_weight_decay=False):
     lib.call("nbss_clip_adam_step", params.numel(), _ptr(lib, params, torch.float32), _ptr(lib, grads, torch.float32), _ptr(lib, exp_avg, torch.float32),
