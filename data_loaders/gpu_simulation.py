@@ -2,7 +2,8 @@
 reference's dataset modules, batched on the device so that the loader keeps up with the HIP training step (hundreds of utterances/s
 per GPU; the reference's 10 CPU workers produce far fewer):
     dry sources  --RIR convolution (FFT, or convolve='native': csrc/conv1d.hip), aligned to the direct path of the reference channel-->  images / targets
-    --relative scaling of speaker 2 to a sampled SIR-->  mixture  --spatially diffuse noise at a sampled SNR-->  peak scaling 0.9
+    --relative scaling of speaker 2 to a sampled SIR-->  mixture  --spatially diffuse noise (torch.fft, or diffuse='native': csrc/diffuse.hip) at a sampled SNR-->
+    peak scaling 0.9
 following data_loaders/sms_wsj_plus.py:157-220, utils/mix.py:122-134 (convolve), :328-346 (energy ratio), utils/diffuse_noise.py:19-93
 (spherically isotropic coherence sinc(w d / c), mixing matrices from its eigendecomposition, STFT-domain mixing of independent
 noises).  Everything is torch (hipFFT / rocSOLVER through torch-ROCm) and device-agnostic: the CPU tests check it against
@@ -221,14 +222,40 @@ def gen_diffuse_noise(noise: Tensor, L: int, Cs: Tensor, nfft: int = 256) -> Ten
     return _istft_scipy(X, nfft)[..., :L]
 
 
+DIFFUSE_MODES = ('fft', 'native')
+
+
+def gen_diffuse_noise_native(white: Tensor, L: int, Cs: Tensor, nfft: int = 256, lib=None) -> Tensor:
+    """gen_diffuse_noise by the fused HIP kernel of csrc/diffuse.hip (nbss_diffuse_noise): white [..., M, >= L] fp32 -> [..., M, L], Cs [F,M,M] complex.
+    Device tensors only: a host tensor raises ValueError (`lib` lets the tests hand in the emulator build of the same kernel)."""
+    from nbss_amd import ops
+    if lib is None:
+        if not white.is_cuda:
+            raise ValueError("diffuse='native' runs the HIP kernel and needs tensors on the device; use diffuse='fft' on the host")
+        from nbss_amd._lib import hip
+        lib = hip()
+    if white.dim() < 2 or white.dtype != torch.float32 or white.shape[-1] < L:
+        raise ValueError(f"gen_diffuse_noise_native: white must be fp32 [..., M, >= {L}], got {tuple(white.shape)} {white.dtype}")
+    lead, M = white.shape[:-2], white.shape[-2]
+    w = white[..., :L].reshape(-1, M, L).contiguous()
+    return ops.diffuse_noise(lib, w, Cs.to(device=white.device, dtype=torch.complex64), nfft).reshape(*lead, M, L)
+
+
+def _check_diffuse(diffuse: str) -> None:
+    if diffuse not in DIFFUSE_MODES:
+        raise ValueError(f"diffuse must be 'fft' or 'native', got {diffuse!r}")
+
+
 def mix_batch(cleans: Tensor, rir: Tensor, Cs: Tensor, sir_db: Optional[Tensor], snr_db: Tensor, gen: Optional[torch.Generator], rir_target: Optional[Tensor] = None,
               nfft: int = 256, white: Optional[Tensor] = None, convolve: str = 'fft', lib=None, traj_hop: Optional[Tensor] = None,
-              traj_mode: str = 'trapezium', traj_ramp: int = 20) -> Tuple[Tensor, Tensor, Dict[str, Tensor]]:
+              traj_mode: str = 'trapezium', traj_ramp: int = 20, diffuse: str = 'fft') -> Tuple[Tensor, Tensor, Dict[str, Tensor]]:
     """cleans [B,S,N] dry sources, rir [B,S,M,L] -> (mix [B,M,N], targets [B,S,M,N], paras): steps 5-7 of SmsWsjPlusDataset.__getitem__
     (full overlap) for a whole batch on the device of `cleans`.  convolve: 'fft' (torch.fft, the default) or 'native' (convolve_aligned_native:
     the HIP kernels, device tensors only; `lib` as there).  Moving sources: rir [B,S,P,M,L] together with traj_hop [B,S] goes through
-    convolve_traj_aligned (traj_mode, traj_ramp as there); everything after the convolution is the same."""
+    convolve_traj_aligned (traj_mode, traj_ramp as there); everything after the convolution is the same.  diffuse: 'fft' (gen_diffuse_noise, the
+    default) or 'native' (gen_diffuse_noise_native: the fused HIP kernel, fp32 device tensors only, the same `lib`); `white` is drawn the same way."""
     _check_convolve(convolve)
+    _check_diffuse(diffuse)
     B, S, N = cleans.shape
     M = rir.shape[-2]
     if (rir.dim() == 5) != (traj_hop is not None):
@@ -245,7 +272,10 @@ def mix_batch(cleans: Tensor, rir: Tensor, Cs: Tensor, sir_db: Optional[Tensor],
     mix = rvbt.sum(1)
     if white is None:
         white = torch.randn(B, M, N, generator=gen, device=cleans.device, dtype=cleans.dtype)
-    noise = gen_diffuse_noise(white, N, Cs.to(cleans.device), nfft)
+    if diffuse == 'native':
+        noise = gen_diffuse_noise_native(white, N, Cs, nfft, lib=lib)
+    else:
+        noise = gen_diffuse_noise(white, N, Cs.to(cleans.device), nfft)
     noise = noise * energy_ratio_coeff(mix, noise, snr_db)[:, None, None]
     snr_real = 10 * torch.log10(mix.pow(2).sum((1, 2)) / noise.pow(2).sum((1, 2)))
     mix = mix + noise
@@ -265,8 +295,9 @@ class SimulatedRoomDataModule:
                  snr: Tuple[float, float] = (0.0, 20.0), rt60: Tuple[float, float] = (0.2, 0.6), array_radius: float = 0.1, seeds: List[int] = (0, 1, 2),
                  device: Optional[str] = None, rir: str = 'synthetic', room_size_lims: Tuple[Tuple[float, float], ...] = ((3.0, 8.0), (3.0, 8.0), (3.0, 4.0)),
                  mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8), convolve: str = 'fft', conv_lib=None,
-                 moving: Optional[Tuple[float, ...]] = None, traj_dist: float = 0.05):
+                 moving: Optional[Tuple[float, ...]] = None, traj_dist: float = 0.05, diffuse: str = 'fft'):
         _check_convolve(convolve)
+        _check_diffuse(diffuse)
         self.moving, self.traj_dist = None, float(traj_dist)
         if moving is not None:  # (vmin, vmax) or (vmin, vmax, prob) in m/s, named after the reference's 'moving(0.12,0.4[,p])' datasets
             if rir != 'ism':
@@ -277,6 +308,7 @@ class SimulatedRoomDataModule:
                                  f"{traj_dist!r}")
             self.moving = (mv[0], mv[1], mv[2] if len(mv) == 3 else 1.0)
         self.convolve, self.conv_lib = convolve, conv_lib  # conv_lib: the tests hand in the emulator library; None = the product library
+        self.diffuse = diffuse
         if rir not in ('synthetic', 'ism'):
             raise ValueError(f"rir must be 'synthetic' or 'ism', got {rir!r}")
         self.rir, self.room_size_lims, self.mic_zlim, self.spk_zlim = rir, [tuple(l) for l in room_size_lims], tuple(mic_zlim), tuple(spk_zlim)
@@ -287,6 +319,8 @@ class SimulatedRoomDataModule:
         self.pos_mics = torch.stack([array_radius * torch.cos(ang), array_radius * torch.sin(ang), torch.zeros(num_channels)], 1)
         if convolve == 'native' and self.device.type != 'cuda' and conv_lib is None:
             raise ValueError("convolve='native' runs the HIP kernels and needs a HIP device; use convolve='fft' (one of 'fft', 'native') on the host")
+        if diffuse == 'native' and self.device.type != 'cuda' and conv_lib is None:
+            raise ValueError("diffuse='native' runs the HIP kernel and needs a HIP device; use diffuse='fft' (one of 'fft', 'native') on the host")
         self.Cs = diffuse_mixing_matrices(self.pos_mics, sample_rate)[1].to(torch.complex64).to(self.device)
 
     def _rirs(self, B: int, gen: torch.Generator) -> Tensor:
@@ -391,6 +425,8 @@ class SimulatedRoomDataModule:
         items = rank_strided_indices(self.num_samples[stage], rank, world, epoch, self.seeds[stage], shuffle=stage == 0)
         k = torch.hann_window(33, device=self.device)
         conv = {} if self.convolve == 'fft' else {"convolve": self.convolve, "lib": self.conv_lib}
+        if self.diffuse != 'fft':
+            conv.update(diffuse=self.diffuse, lib=self.conv_lib)
         for i in range(0, len(items) - bs + 1, bs):
             chunk = items[i:i + bs]
             gen = torch.Generator(device=self.device).manual_seed(int(chunk[0][1]) * 1000003 + int(chunk[0][0]))

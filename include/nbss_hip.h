@@ -312,6 +312,32 @@ int nbss_fir_convolve(int B, int S, int M, int N, int L, const float* x, const f
 int nbss_fir_convolve_traj(int B, int S, int P, int M, int N, int L, int mode, int ramp, const float* x, const float* h, const int32_t* hop,
                            const int32_t* delay, float* y, int32_t* status, void* stream);
 
+/* ---- Spatially diffuse noise of the on-device simulator (csrc/diffuse.hip; data_loaders/gpu_simulation.py: gen_diffuse_noise_native) ------------
+ * nbss_diffuse_noise: white [B][M][N] fp32 (M mutually independent noises per item), Cs [F][M][M][2] fp32 (complex, interleaved re / im, shared by
+ * the batch; F = nfft / 2 + 1) -> noise [B][M][N] fp32 with the coherence the mixing matrices encode (utils/diffuse_noise.py:64-93).  For item b,
+ * with hop = nfft / 4 and w the periodic Hann window of length nfft:
+ *   1. v[m][.] = white[b][m][.] - its mean over the N samples (the mean is summed, and subtracted, in fp64).
+ *   2. v is padded with nfft / 2 zeros on each side, then with zeros on the right up to the next length Np for which (Np - nfft) is a multiple of
+ *      hop; T = (Np - nfft) / hop + 1 frames, frame t covers the padded samples [t hop, t hop + nfft).
+ *   3. Nf[m][f][t] = sum_j w[j] frame_t[m][j] e^(-2 pi i f j / nfft).  (The 1 / sum w of scipy's forward transform cancels against its inverse.)
+ *   4. X[n][f][t] = sum_m conj(Cs[f][m][n]) Nf[m][f][t]: the output channel is the LAST index of Cs.
+ *   5. g_t[n][j] = w[j] irfft(X[n][.][t])[j], the real inverse of length nfft with its 1 / nfft; the imaginary parts of bins 0 and nfft / 2 are
+ *      ignored, as torch.fft.irfft ignores them.
+ *   6. The g_t are overlap-added at hop spacing, and the padded sample p is divided by max(sum_t w^2[p - t hop], 1e-10) over the frames that cover
+ *      it: near both ends fewer than four do, and the envelope is formed from those that exist.
+ *   7. noise[b][n][i] is the padded sample i + nfft / 2, i in [0, N).
+ * Both transforms are DFT-as-GEMM on the exact-fp32 matrix cores, fused with the mix and the overlap-add in one kernel: white is read once and noise
+ * written once.  No atomics; the order of every sum is fixed by N and M alone: two calls give the same bits, and an item's result depends neither on
+ * B nor on its position in the batch.  Rows are read and written element by element: any N >= 1, no alignment demanded.  noise may not alias white.
+ * ws: nbss_diffuse_noise_ws_bytes(B, M) bytes (8-byte aligned): the packed windowed DFT matrices (525 312 bytes, rewritten by every call) and the
+ * B M row means in fp64; the count is negative for B < 1 or M < 1.
+ * NBSS_EINVAL: N < 1, B < 1, M < 1, a NULL pointer (ws included), noise overlapping white.  NBSS_EUNSUPPORTED: nfft other than 256 (the only size
+ * the simulator and the reference use), M > 16, N > 2^24, B M > 2^22.  A workgroup owns 832 output samples of all M channels of one item; its LDS
+ * image (the strip of 19 hops of every channel with the mean removed, later the overlap-add image, and the mixed spectra of four row tiles) is
+ * 9 264 M bytes: 54.3 KB at M = 6, 144.8 KB at M = 16.  Items beyond 128 are walked by the same grid. */
+int64_t nbss_diffuse_noise_ws_bytes(int B, int M);
+int nbss_diffuse_noise(int nfft, int B, int M, int N, const float* white, const float* Cs, float* ws, float* noise, void* stream);
+
 /* clip_grad_norm_(max_norm, L2) + torch.optim.Adam(W) step on the flat fp32 buffers
  * (configs/SpatialNet.yaml:3-4,44; general_steps.py:243-271).  grads are first multiplied by
  * grad_scale (1/world_size after a SUM all-reduce).  scratch: >= 258 floats; scratch[0] returns the

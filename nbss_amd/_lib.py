@@ -95,6 +95,8 @@ SIGNATURES = {
     "nbss_rir_delay": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
     "nbss_fir_convolve": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "nbss_fir_convolve_traj": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "nbss_diffuse_noise_ws_bytes": (C.c_int64, [_I, _I]),
+    "nbss_diffuse_noise": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nbss_online_encoder_step": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "nbss_online_ret_step": (_I, [_I, _I] + [_P] * 12),
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),

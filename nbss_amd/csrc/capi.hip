@@ -51,6 +51,8 @@ int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double
 int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, hipStream_t st);
 int rir_delay_impl(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, hipStream_t st);
 int fir_convolve_impl(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, hipStream_t st);
+size_t diffuse_noise_ws_bytes_impl(int B, int M);
+int diffuse_noise_impl(int nfft, int B, int M, int N, const float* white, const float* Cs, float* ws, float* noise, hipStream_t st);
 int fir_convolve_traj_impl(int B, int S, int P, int M, int N, int L, int mode, int ramp, const float* x, const float* h, const int32_t* hop, const int32_t* delay,
                            float* y, int32_t* status, hipStream_t st);
 int clip_adam_dev_impl(size_t n, float* p, float* g, float* m, float* v, float* scal, const float* hyper, float max_norm, float grad_scale, float beta1,
@@ -538,6 +540,16 @@ int nbss_fir_convolve_traj(int B, int S, int P, int M, int N, int L, int mode, i
                            float* y, int32_t* status, void* stream) {
     if (!x || !h || !hop || !delay || !y) return NBSS_EINVAL;
     return fir_convolve_traj_impl(B, S, P, M, N, L, mode, ramp, x, h, hop, delay, y, status, (hipStream_t)stream);
+}
+
+int64_t nbss_diffuse_noise_ws_bytes(int B, int M) {
+    if (B < 1 || M < 1) return NBSS_EINVAL;
+    return (int64_t)diffuse_noise_ws_bytes_impl(B, M);
+}
+
+int nbss_diffuse_noise(int nfft, int B, int M, int N, const float* white, const float* Cs, float* ws, float* noise, void* stream) {
+    if (!white || !Cs || !ws || !noise) return NBSS_EINVAL;
+    return diffuse_noise_impl(nfft, B, M, N, white, Cs, ws, noise, (hipStream_t)stream);
 }
 
 int nbss_clip_adam_step(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* scratch, float max_norm,

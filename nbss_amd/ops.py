@@ -434,6 +434,32 @@ def fir_convolve_traj(lib, x, h, hop, delay, mode: str = 'trapezium', ramp: int 
     return y
 
 
+def diffuse_noise(lib, white, Cs, nfft: int = 256, out=None):
+    """white [B,M,N] fp32 (M mutually independent noises per item), Cs [F,M,M] complex64 (F = nfft // 2 + 1; the mixing matrices of
+    diffuse_mixing_matrices, shared by the batch) on the same device -> noise [B,M,N] fp32: mean removal, STFT, X[n] = sum_m conj(Cs[f,m,n]) N[m],
+    inverse STFT, in one kernel (nbss_diffuse_noise; include/nbss_hip.h has the definition).  Arguments that do not fit raise ValueError, a negative
+    code of the library NbssError."""
+    if white.dim() != 3 or white.dtype != torch.float32 or not white.is_contiguous():
+        raise ValueError(f"diffuse_noise: white must be a contiguous fp32 [B,M,N] tensor, got {tuple(white.shape)} {white.dtype}"
+                         f"{'' if white.is_contiguous() else ', not contiguous'}")
+    B, M, N = white.shape
+    if Cs.dtype != torch.complex64 or tuple(Cs.shape) != (nfft // 2 + 1, M, M) or Cs.device != white.device:
+        raise ValueError(f"diffuse_noise: Cs must be complex64 [F,M,M] = {(nfft // 2 + 1, M, M)} on {white.device}, got {tuple(Cs.shape)} {Cs.dtype} on {Cs.device}")
+    if white.device.type != ("cpu" if _is_emu(lib) else "cuda"):
+        raise ValueError("diffuse_noise: the emulator library only takes CPU tensors" if _is_emu(lib) else
+                         "diffuse_noise: libnbss_hip.so needs tensors on a HIP device (no CPU fallback exists)")
+    y = torch.empty_like(white) if out is None else out
+    if y.shape != white.shape or y.device != white.device:
+        raise ValueError(f"diffuse_noise: out must be [B,M,N] = {(B, M, N)} on {white.device}, got {tuple(y.shape)} on {y.device}")
+    nb = lib.nbss_diffuse_noise_ws_bytes(B, M)
+    if nb < 0:
+        raise NbssError(f"nbss_diffuse_noise_ws_bytes failed: {_ERR.get(nb, nb)}")
+    ws = scratch(nb, white.device)
+    lib.call("nbss_diffuse_noise", int(nfft), B, M, N, _ptr(lib, white, torch.float32), _ptr(lib, torch.view_as_real(Cs.contiguous()), torch.float32),
+             _ptr(lib, ws), _ptr(lib, y, torch.float32), _stream(lib, white))
+    return y
+
+
 def clip_adam_step(lib, params, grads, exp_avg, exp_avg_sq, scratch, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                    max_norm=5.0, grad_scale=1.0, zero_grad=True, decoupled_weight_decay=False):
     lib.call("nbss_clip_adam_step", params.numel(), _ptr(lib, params, torch.float32), _ptr(lib, grads, torch.float32), _ptr(lib, exp_avg, torch.float32),
