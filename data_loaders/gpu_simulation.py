@@ -12,6 +12,8 @@ The corpora (WSJ0, measured/simulated RIR sets) are not available here: `Simulat
 sources and, by default, synthetic exponentially decaying RIRs; with rir='ism' it draws shoebox rooms and computes their impulse
 responses by the image-source method on the device (nbss_amd/rir.py: simulate_rir), and with moving=(vmin, vmax[, prob]) the speakers walk:
 a trajectory of responses per speaker, cross-faded along the source (utils/mix.py:197-244; convolve_traj_aligned, csrc/conv_traj.hip).
+With rir_att_diff (dB; the reference's generate_rirs.py uses 15) every room sums its images only to that much of its own decay and continues
+with the diffuse tail of nbss_rir_tail (simulate_rir with one t_diff per room); None, the default, sums every image down to 60 dB.
 `mix_batch` itself takes any sources / RIRs."""
 import math
 from typing import Dict, List, Optional, Tuple
@@ -295,9 +297,16 @@ class SimulatedRoomDataModule:
                  snr: Tuple[float, float] = (0.0, 20.0), rt60: Tuple[float, float] = (0.2, 0.6), array_radius: float = 0.1, seeds: List[int] = (0, 1, 2),
                  device: Optional[str] = None, rir: str = 'synthetic', room_size_lims: Tuple[Tuple[float, float], ...] = ((3.0, 8.0), (3.0, 8.0), (3.0, 4.0)),
                  mic_zlim: Tuple[float, float] = (1.0, 1.5), spk_zlim: Tuple[float, float] = (1.0, 1.8), convolve: str = 'fft', conv_lib=None,
-                 moving: Optional[Tuple[float, ...]] = None, traj_dist: float = 0.05, diffuse: str = 'fft'):
+                 moving: Optional[Tuple[float, ...]] = None, traj_dist: float = 0.05, diffuse: str = 'fft', rir_att_diff: Optional[float] = None):
         _check_convolve(convolve)
         _check_diffuse(diffuse)
+        self.rir_att_diff = None
+        if rir_att_diff is not None:  # dB of decay after which a room's images give way to the diffuse tail (the reference's att_diff = 15)
+            if rir != 'ism':
+                raise ValueError(f"rir_att_diff switches image-source responses to their diffuse tail: rir must be 'ism', got {rir!r}")
+            if not 0.0 < float(rir_att_diff) < 60.0:
+                raise ValueError(f"rir_att_diff must lie between 0 and the 60 dB the responses decay by, got {rir_att_diff!r}")
+            self.rir_att_diff = float(rir_att_diff)
         self.moving, self.traj_dist = None, float(traj_dist)
         if moving is not None:  # (vmin, vmax) or (vmin, vmax, prob) in m/s, named after the reference's 'moving(0.12,0.4[,p])' datasets
             if rir != 'ism':
@@ -360,12 +369,31 @@ class SimulatedRoomDataModule:
         return {"room_sz": room, "rt60": rt, "beta": beta, "pos_rcv": pos_rcv, "pos_src": pos_src,
                 "nb_img": t2n(att2t(60.0, rt), room).cpu(), "n_samples": int((float(rt.max()) + 0.1) * self.sr)}
 
+    def _ism_tail(self, sc: Dict[str, Tensor], gen: torch.Generator) -> Dict:
+        """what the reverberant simulate_rir call takes besides the scene.  Without rir_att_diff: the scene's image counts down to 60 dB, and no
+        draw from `gen`.  With it, per room b: t_diff[b] = att2t(rir_att_diff, rt60[b]), the image counts t2n(t_diff[b], room) that reach it, the
+        diffuse tail governed by rt60[b] from there to the scene's n_samples, and the tail's seed: one integer drawn from `gen`, after every draw of
+        the scene (items stay addressed by (index, seed))."""
+        if self.rir_att_diff is None:
+            return {"nb_img": sc["nb_img"]}
+        from nbss_amd.rir import TW, att2t, t2n
+        from nbss_amd.ops import rir_tail_start
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=gen, device=self.device))
+        t_diff = att2t(self.rir_att_diff, sc["rt60"])
+        K, n = int(round(TW * self.sr)), sc["n_samples"]
+        for b, (t, rt) in enumerate(zip(t_diff.tolist(), sc["rt60"].tolist())):
+            if not K <= rir_tail_start(t, self.sr) < n:
+                raise ValueError(f"rir_att_diff = {self.rir_att_diff:g} dB puts the diffuse tail of room {b} (RT60 {rt:.3f} s) at sample "
+                                 f"{rir_tail_start(t, self.sr)}, outside {K} <= k_d < {n}")
+        return {"nb_img": t2n(t_diff, sc["room_sz"]).cpu(), "t_diff": t_diff, "rt60": sc["rt60"], "seed": seed}
+
     def _ism_rirs(self, B: int, gen: torch.Generator) -> Tuple[Tensor, Tensor]:
-        """(reverberant, direct-path) RIRs [B,S,M,L] of B rooms drawn from `gen`: one simulate_rir call each"""
+        """(reverberant, direct-path) RIRs [B,S,M,L] of B rooms drawn from `gen`: one simulate_rir call each; with rir_att_diff the reverberant
+        one sums each room's images to that decay only and continues with the diffuse tail (_ism_tail)"""
         from nbss_amd.rir import simulate_rir
         sc = self._ism_scene(B, gen)
         geo = (sc["room_sz"], sc["beta"], sc["pos_src"], sc["pos_rcv"])
-        rir = simulate_rir(*geo, sc["nb_img"], sc["n_samples"], self.sr)
+        rir = simulate_rir(*geo, n_samples=sc["n_samples"], fs=self.sr, **self._ism_tail(sc, gen))
         rir_dp = simulate_rir(geo[0], torch.zeros_like(geo[1]), geo[2], geo[3], (1, 1, 1), sc["n_samples"], self.sr)
         return rir.float(), rir_dp.float()
 
@@ -409,12 +437,13 @@ class SimulatedRoomDataModule:
 
     def _ism_traj_rirs(self, B: int, N: int, gen: torch.Generator) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         """(reverberant, direct-path) RIRs [B,S,P,M,L] along the trajectories of _traj_draws, with its hop and speeds: one simulate_rir call each,
-        with the trajectory points as sources"""
+        with the trajectory points as sources.  With rir_att_diff (_ism_tail) every trajectory point is a source of its own to the kernel and so
+        gets its own tail noise xi(seed, b, s P + p, m, k): the tails of adjacent points are independent, not a continuation of one another."""
         from nbss_amd.rir import simulate_rir
         sc, hop, speed, pts = self._traj_draws(B, N, gen)
         P = pts.shape[2]
         src = pts.reshape(B, self.S * P, 3)
-        rir = simulate_rir(sc["room_sz"], sc["beta"], src, sc["pos_rcv"], sc["nb_img"], sc["n_samples"], self.sr)
+        rir = simulate_rir(sc["room_sz"], sc["beta"], src, sc["pos_rcv"], n_samples=sc["n_samples"], fs=self.sr, **self._ism_tail(sc, gen))
         rir_dp = simulate_rir(sc["room_sz"], torch.zeros_like(sc["beta"]), src, sc["pos_rcv"], (1, 1, 1), sc["n_samples"], self.sr)
         shape = (B, self.S, P, self.C, sc["n_samples"])
         return rir.float().reshape(shape), rir_dp.float().reshape(shape), hop, speed

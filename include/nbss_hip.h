@@ -263,6 +263,20 @@ int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double
  * xi = sqrt(-2 ln u1) cos(2 pi u2), evaluated in fp64: the tail does not depend on the launch geometry.  rt60 [B] fp64 device array.
  * Same limits as nbss_rir_ism with k_d > 0. */
 int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream);
+/* The same two with the switch to the tail per room (a batch draws RT60 per room, so att2t(15 dB, rt60[b]) differs from room to room):
+ * k_d [B]: int32 HOST array, read before the call returns, like nb_img.
+ * nbss_rir_ism_rooms: room b sums only the images with x < k_d[b] + round(tw fs) / 2 when k_d[b] > 0, all of them when k_d[b] = 0.  Everything said of
+ * nbss_rir_ism holds: every element of h is written exactly once, no atomics, the order of the sum is fixed by the room, (s, m) and k alone, and a
+ * room's response does not depend on the other rooms of the batch — room b is BITWISE what nbss_rir_ism gives for that room with k_d = k_d[b].
+ * The limits are those of nbss_rir_ism per room: a room with 0 < k_d[b] < round(tw fs) or k_d[b] >= n_samples makes the call return NBSS_EUNSUPPORTED
+ * (a negative k_d[b] NBSS_EINVAL) before anything is launched.  ws: nbss_rir_ism_ws_bytes() bytes, the same layout: the k_d travel in the kernel's
+ * arguments, 256 rooms per launch.
+ * nbss_rir_tail_rooms: room b gets the tail of nbss_rir_tail's definition from k_d[b] on (the same xi(seed, b, s, m, k): bitwise nbss_rir_tail with
+ * k_d = k_d[b]); a room with k_d[b] = 0 is not touched.  Same limits per room. */
+int nbss_rir_ism_rooms(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, const double* room_sz, const double* beta,
+                       const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, void* stream);
+int nbss_rir_tail_rooms(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, const double* rt60, int64_t seed, float* h,
+                        void* stream);
 
 /* ---- RIR convolution of the on-device simulator (csrc/conv1d.hip; data_loaders/gpu_simulation.py: convolve_aligned_native) ---------------------
  * What the reference's convolve(wav, rir, rir_target, ref_channel, align=True) keeps of its full convolutions (utils/mix.py:122-134): the N samples

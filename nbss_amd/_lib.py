@@ -92,6 +92,8 @@ SIGNATURES = {
     "nbss_rir_ism_ws_bytes": (C.c_int64, [_I, _P]),
     "nbss_rir_ism": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "nbss_rir_tail": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, _I, _P, C.c_int64, _P, _P]),
+    "nbss_rir_ism_rooms": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "nbss_rir_tail_rooms": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P]),
     "nbss_rir_delay": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
     "nbss_fir_convolve": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "nbss_fir_convolve_traj": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),

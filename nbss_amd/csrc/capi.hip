@@ -49,6 +49,10 @@ int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img);
 int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
                  const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
 int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, hipStream_t st);
+int rir_ism_rooms_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, const double* room_sz, const double* beta,
+                       const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
+int rir_tail_rooms_impl(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, const double* rt60, int64_t seed, float* h,
+                        hipStream_t st);
 int rir_delay_impl(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, hipStream_t st);
 int fir_convolve_impl(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, hipStream_t st);
 size_t diffuse_noise_ws_bytes_impl(int B, int M);
@@ -524,6 +528,18 @@ int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double
 int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream) {
     if (!rt60 || !h) return NBSS_EINVAL;
     return rir_tail_impl(B, S, M, n_samples, fs, tw, k_d, rt60, seed, h, (hipStream_t)stream);
+}
+
+int nbss_rir_ism_rooms(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, const double* room_sz, const double* beta,
+                       const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, void* stream) {
+    if (!k_d || !room_sz || !beta || !pos_src || !pos_rcv || !nb_img || !h || !ws) return NBSS_EINVAL;
+    return rir_ism_rooms_impl(B, S, M, n_samples, fs, c, tw, k_d, room_sz, beta, pos_src, pos_rcv, nb_img, h, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int nbss_rir_tail_rooms(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, const double* rt60, int64_t seed, float* h,
+                        void* stream) {
+    if (!k_d || !rt60 || !h) return NBSS_EINVAL;
+    return rir_tail_rooms_impl(B, S, M, n_samples, fs, tw, k_d, rt60, seed, h, (hipStream_t)stream);
 }
 
 int nbss_rir_delay(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, void* stream) {

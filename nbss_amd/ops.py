@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 from torch import Tensor
@@ -337,11 +337,35 @@ def rir_tail_start(t_diff: float, fs: float) -> int:
     return int(math.ceil(float(t_diff) * float(fs) - 1e-9))
 
 
-def rir_ism(lib, room_sz, beta, pos_src, pos_rcv, nb_img, n_samples: int, fs: float, c: float = 343.0, tw: float = 8e-3, t_diff: Optional[float] = None,
+def rir_tail_starts(t_diff, fs: float, B: int, n_samples: int, tw: float, what: str = "rir_ism") -> List[int]:
+    """k_d[b] = rir_tail_start(t_diff[b], fs) of a per-room t_diff (a sequence or a [B] tensor of positive seconds), each checked against the
+    kernels' limits round(tw fs) <= k_d[b] < n_samples; ValueError names the room.  None, NaN or a value <= 0 is no entry: a batch without a
+    tail is t_diff=None."""
+    vals = t_diff.detach().reshape(-1).tolist() if torch.is_tensor(t_diff) else list(t_diff)
+    if len(vals) != B:
+        raise ValueError(f"{what}: a per-room t_diff needs one value per room, B = {B}, got {len(vals)}")
+    K, out = int(round(float(tw) * float(fs))), []
+    for b, v in enumerate(vals):
+        if v is None or not float(v) > 0.0 or math.isinf(float(v)):
+            raise ValueError(f"{what}: t_diff[{b}] = {v!r} of room {b} must be a positive number of seconds (t_diff=None switches the tail off for every room)")
+        k_d = rir_tail_start(v, fs)
+        if not K <= k_d < int(n_samples):
+            raise ValueError(f"{what}: the diffuse tail must start at a sample k_d with {K} <= k_d < {int(n_samples)}, got {k_d} for room {b}")
+        out.append(k_d)
+    return out
+
+
+def _per_room(t_diff) -> bool:
+    """a t_diff with one value per room (a sequence, an array or a tensor with a dimension), not one number for the batch"""
+    return isinstance(t_diff, (list, tuple)) or getattr(t_diff, "ndim", 0) > 0
+
+
+def rir_ism(lib, room_sz, beta, pos_src, pos_rcv, nb_img, n_samples: int, fs: float, c: float = 343.0, tw: float = 8e-3, t_diff=None,
             rt60=None, seed: int = 0, ws=None, out=None):
     """image-source room impulse responses of a batch of rooms (nbss_rir_ism, with t_diff also nbss_rir_tail): room_sz [B,3], beta [B,6],
     pos_src [B,S,3], pos_rcv [B,M,3] (any float dtype: the kernel takes fp64), nb_img (Nx, Ny, Nz) shared or [B,3] per room (host integers)
-    -> h [B,S,M,n_samples] fp32.  t_diff (seconds, with rt60 [B] or a number) switches to the diffuse tail from sample ceil(t_diff fs) on."""
+    -> h [B,S,M,n_samples] fp32.  t_diff (seconds, with rt60 [B] or a number) switches to the diffuse tail from sample ceil(t_diff fs) on; a
+    sequence or a [B] tensor of t_diff switches per room (nbss_rir_ism_rooms, nbss_rir_tail_rooms)."""
     dev = room_sz.device
     f64 = lambda t: t.detach().to(device=dev, dtype=torch.float64).contiguous()
     room_sz, beta, pos_src, pos_rcv = f64(room_sz), f64(beta), f64(pos_src), f64(pos_rcv)
@@ -359,12 +383,17 @@ def rir_ism(lib, room_sz, beta, pos_src, pos_rcv, nb_img, n_samples: int, fs: fl
         raise NbssError(f"nbss_rir_ism_ws_bytes failed: {_ERR.get(nws, nws)}")
     if ws is None:
         ws = scratch(nws, dev)
-    k_d = 0 if t_diff is None else rir_tail_start(t_diff, fs)
+    rooms = _per_room(t_diff)
+    if rooms:
+        k_ds = torch.tensor(rir_tail_starts(t_diff, fs, B, n_samples, tw), dtype=torch.int32)  # host array, read before the calls return
+    else:
+        k_d = 0 if t_diff is None else rir_tail_start(t_diff, fs)
     h = torch.empty(B, S, M, int(n_samples), dtype=torch.float32, device=dev) if out is None else out
     if h.shape != (B, S, M, int(n_samples)):
         raise NbssError(f"rir_ism: out must be [B,S,M,n_samples] = {(B, S, M, int(n_samples))}, got {tuple(h.shape)}")
-    lib.call("nbss_rir_ism", B, S, M, int(n_samples), float(fs), float(c), float(tw), k_d, _ptr(lib, room_sz), _ptr(lib, beta), _ptr(lib, pos_src),
-             _ptr(lib, pos_rcv), nb.data_ptr(), _ptr(lib, h, torch.float32), _ptr(lib, ws, torch.uint8), ws.numel(), _stream(lib, h))
+    lib.call("nbss_rir_ism_rooms" if rooms else "nbss_rir_ism", B, S, M, int(n_samples), float(fs), float(c), float(tw), k_ds.data_ptr() if rooms else k_d,
+             _ptr(lib, room_sz), _ptr(lib, beta), _ptr(lib, pos_src), _ptr(lib, pos_rcv), nb.data_ptr(), _ptr(lib, h, torch.float32), _ptr(lib, ws, torch.uint8),
+             ws.numel(), _stream(lib, h))
     if t_diff is not None:
         if rt60 is None:
             raise NbssError("rir_ism: the diffuse tail (t_diff) needs rt60")
@@ -372,7 +401,8 @@ def rir_ism(lib, room_sz, beta, pos_src, pos_rcv, nb_img, n_samples: int, fs: fl
         rt = (rt.expand(B) if rt.numel() == 1 else rt).contiguous()
         if rt.numel() != B:
             raise NbssError(f"rir_ism: rt60 must be a number or [B], got {tuple(rt.shape)}")
-        lib.call("nbss_rir_tail", B, S, M, int(n_samples), float(fs), float(tw), k_d, _ptr(lib, rt), int(seed), _ptr(lib, h), _stream(lib, h))
+        lib.call("nbss_rir_tail_rooms" if rooms else "nbss_rir_tail", B, S, M, int(n_samples), float(fs), float(tw), k_ds.data_ptr() if rooms else k_d,
+                 _ptr(lib, rt), int(seed), _ptr(lib, h), _stream(lib, h))
     return h
 
 

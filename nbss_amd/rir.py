@@ -158,15 +158,20 @@ def _host_ism_room(room: Tensor, beta: Tensor, src: Tensor, rcv: Tensor, nb: Seq
 
 
 def _host_rir(room_sz, beta, pos_src, pos_rcv, nb, n_samples, fs, c, tw, t_diff, rt60, seed) -> Tensor:
-    from .ops import rir_tail_start
+    from .ops import _per_room, rir_tail_start, rir_tail_starts
     B = room_sz.shape[0]
     K = int(round(tw * fs))
-    k_d = 0 if t_diff is None else rir_tail_start(t_diff, fs)
-    if t_diff is not None and not (K <= k_d < n_samples):
-        raise ValueError(f"simulate_rir: the diffuse tail must start at a sample k_d with {K} <= k_d < {n_samples}, got {k_d}")
-    x_max = k_d + K / 2 if t_diff is not None else math.inf
+    if _per_room(t_diff):  # one switch per room
+        k_ds = rir_tail_starts(t_diff, fs, B, n_samples, tw, what="simulate_rir")
+    else:
+        k_d = 0 if t_diff is None else rir_tail_start(t_diff, fs)
+        if t_diff is not None and not (K <= k_d < n_samples):
+            raise ValueError(f"simulate_rir: the diffuse tail must start at a sample k_d with {K} <= k_d < {n_samples}, got {k_d}")
+        k_ds = [k_d] * B
     out = []
     for b in range(B):
+        k_d = k_ds[b]
+        x_max = k_d + K / 2 if t_diff is not None else math.inf
         h = _host_ism_room(room_sz[b], beta[b], pos_src[b], pos_rcv[b], [int(v) for v in nb[b]], n_samples, fs, c, tw, x_max)
         if t_diff is not None:
             g = h[..., k_d - K:k_d].pow(2).mean(-1).sqrt()
@@ -181,13 +186,15 @@ def _host_rir(room_sz, beta, pos_src, pos_rcv, nb, n_samples, fs, c, tw, t_diff,
 
 # ---------------------------------------------------------------- the public function
 def simulate_rir(room_sz: Tensor, beta: Tensor, pos_src: Tensor, pos_rcv: Tensor, nb_img, n_samples: int, fs: float, c: float = C_SOUND, tw: float = TW,
-                 t_diff: Optional[float] = None, rt60=None, seed: int = 0) -> Tensor:
+                 t_diff=None, rt60=None, seed: int = 0) -> Tensor:
     """Room impulse responses of one shoebox room or of a batch of rooms.
 
     room_sz [3] or [B,3] metres; beta [6] / [B,6] reflection coefficients (x0, x1, y0, y1, z0, z1); pos_src [S,3] / [B,S,3]; pos_rcv [M,3] / [B,M,3];
     nb_img (Nx, Ny, Nz) image counts per axis, shared or [B,3] per room (host integers); n_samples output length; fs sampling rate; c speed of
     sound; tw length of the windowed sinc in seconds.  t_diff (seconds, needs rt60: a number or [B]) sums only the images arriving before it
-    and continues with the diffuse tail g 10^(-3 (k - k_d) / (fs rt60)) xi(seed, b, s, m, k).
+    and continues with the diffuse tail g 10^(-3 (k - k_d) / (fs rt60)) xi(seed, b, s, m, k).  t_diff is one number for the batch or one
+    positive value per room (a sequence or a [B] tensor: nbss_rir_ism_rooms, nbss_rir_tail_rooms); None is no tail for any room.  A tail that
+    would start outside round(tw fs) <= k_d < n_samples raises ValueError, which names the room for a per-room t_diff.
     Returns [S,M,n_samples] resp. [B,S,M,n_samples]: fp32 from the HIP kernels for tensors on the device, fp64 from the host closed form otherwise.
     The direct-path response is the same call with nb_img = (1, 1, 1) and beta = 0."""
     single = room_sz.dim() == 1

@@ -8,9 +8,9 @@ writes <rir_dir>/{train,validation,test}/<index>.npz with the keys
     fs, RT60, room_sz, pos_src [S,3], pos_rcv [M,3], pos_noise [noise_num,3], rir [S,M,L], rir_dp [S,M,L], rir_noise [noise_num,M,L] (absent sources:
     empty arrays), arr_geometry, selected_channels, beta          L = int((RT60 + 0.1) fs)
 Static sources only.  Rooms are drawn and simulated in batches (--batch rooms per simulate_rir call, at the length of the batch's longest
-response, each file cut to its own L).  --attn_diff D switches every room to the diffuse tail after D dB of decay (nbss_rir_tail); the switch
-sample differs from room to room, so those responses are computed room by room while the direct paths stay batched.  Without it the images
-are summed down to 60 dB.  Numerical parity with gpuRIR is not pinned (nbss_amd/rir.py)."""
+response, each file cut to its own L).  --attn_diff D switches every room to the diffuse tail after D dB of its own decay; the switch sample
+differs from room to room, and the batch goes through simulate_rir's per-room t_diff (nbss_rir_ism_rooms, nbss_rir_tail_rooms) in one call.
+Without it the images are summed down to 60 dB.  Numerical parity with gpuRIR is not pinned (nbss_amd/rir.py)."""
 import argparse
 import json
 import math
@@ -102,12 +102,9 @@ def generate(args) -> int:
                 rir = simulate_rir(to(room), to(beta), to(pos_all), to(pos_rcv), nb, max(L), args.fs)
                 rirs = [rir[b, :, :, :L[b]] for b in range(B)]
             else:
-                rirs = []
-                for b in range(B):
-                    t_diff = float(att2t(args.attn_diff, rt[b]))
-                    nb = t2n(t_diff, room[b])
-                    rirs.append(simulate_rir(to(room[b]), to(beta[b]), to(pos_all[b]), to(pos_rcv[b]), nb, L[b], args.fs, t_diff=t_diff, rt60=float(rt[b]),
-                                             seed=args.seed + i0 + b))
+                t_diff = att2t(args.attn_diff, rt)  # [B]: every room switches after the same decay, at its own time
+                rir = simulate_rir(to(room), to(beta), to(pos_all), to(pos_rcv), t2n(t_diff, room), max(L), args.fs, t_diff=t_diff, rt60=rt, seed=args.seed + i0)
+                rirs = [rir[b, :, :, :L[b]] for b in range(B)]
             for b in range(B):
                 r = rirs[b].float().cpu().numpy()
                 d = dp[b, :, :, :L[b]].float().cpu().numpy()

@@ -2,7 +2,11 @@
 16 kHz, RT60 0.2 / 0.6 / 1.0 s — the full image-source sum down to 60 dB, and the 15-dB switch to the diffuse tail — through nbss_amd.rir.simulate_rir
 on the device (HIP events over `reps` calls after a warm-up) beside the fp64 host path of the same function on this box's CPU (one room of the
 batch, wall clock, scaled to the batch; skipped above `host_max_images` images per room).
-    python tools/rir_bench.py [rooms] [reps] [host_max_images]          one JSON line per case; a "RIR" is one (source, receiver) response"""
+    python tools/rir_bench.py [rooms] [reps] [host_max_images]          one JSON line per case; a "RIR" is one (source, receiver) response
+    python tools/rir_bench.py rooms [rooms] [reps] [rounds]             the per-room switch (nbss_rir_ism_rooms, nbss_rir_tail_rooms) at 8 kHz:
+        "equal k_d": RT60 0.6 s in every room, the scalar entry points and the _rooms entry points on the same inputs, alternating, `rounds` rounds
+        of `reps` calls each (HIP events per round; ms per call: median, min - max over the rounds) and whether the two results are the same bits;
+        "k_d per room": RT60 drawn in 0.2 - 0.6 s, t_diff[b] = att2t(15, RT60[b]), beside the full sum down to 60 dB of the same rooms"""
 import json
 import sys
 import time
@@ -26,7 +30,68 @@ def scene(B, rt60, seed=0):
     return room, beta_sabine(room, rt)[0], src, rcv, rt
 
 
+def timed(fn, reps, rounds):
+    """ms per call of fn, one figure per round of `reps` calls between two HIP events"""
+    out = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / reps)
+    return out
+
+
+def stats(ms):
+    s = sorted(ms)
+    return {"median_ms": s[len(s) // 2], "min_ms": s[0], "max_ms": s[-1]}
+
+
+def rooms_main():
+    B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 10
+    dev, fs = torch.device("cuda:0"), 8000
+    # all k_d equal: what the generalisation costs
+    room, beta, src, rcv, rt = scene(B, 0.6)
+    T = att2t(15.0, 0.6)
+    nb, n = t2n(torch.full((B,), T, dtype=torch.float64), room), int(0.7 * fs)
+    args = [t.to(dev) for t in (room, beta, src, rcv)]
+    scalar = lambda: simulate_rir(*args, nb, n, fs, t_diff=T, rt60=rt, seed=1)
+    per_room = lambda: simulate_rir(*args, nb, n, fs, t_diff=[T] * B, rt60=rt, seed=1)
+    same = bool(torch.equal(scalar().view(torch.int32), per_room().view(torch.int32)))  # also the warm-up of both
+    torch.cuda.synchronize()
+    ms = {"scalar": [], "rooms": []}
+    for _ in range(rounds):  # alternating: both see the same box
+        ms["scalar"] += timed(scalar, reps, 1)
+        ms["rooms"] += timed(per_room, reps, 1)
+    for k in ("scalar", "rooms"):
+        print(json.dumps({"case": "equal k_d", "entry": k, "fs": fs, "rt60": 0.6, "rooms": B, "n_samples": n, "k_d": int(round(T * fs)), "reps": reps,
+                          "rounds": rounds, **stats(ms[k]), "same_bits_as_scalar": same}), flush=True)
+    # k_d per room
+    g = torch.Generator().manual_seed(1)
+    rt = 0.2 + 0.4 * torch.rand(B, generator=g, dtype=torch.float64)
+    beta = beta_sabine(room, rt)[0]
+    args[1] = beta.to(dev)
+    Tb = att2t(15.0, rt)
+    nb15, nb60, n = t2n(Tb, room), t2n(att2t(60.0, rt), room), int((float(rt.max()) + 0.1) * fs)
+    per_room = lambda: simulate_rir(*args, nb15, n, fs, t_diff=Tb, rt60=rt, seed=1)
+    full = lambda: simulate_rir(*args, nb60, n, fs)
+    finite = bool(torch.isfinite(per_room()).all())
+    full()
+    torch.cuda.synchronize()
+    print(json.dumps({"case": "k_d per room", "entry": "rooms", "fs": fs, "rt60": [float(rt.min()), float(rt.max())], "rooms": B, "n_samples": n,
+                      "images_per_room": float(nb15.prod(-1).double().mean()), "reps": reps, "rounds": rounds, **stats(timed(per_room, reps, rounds)),
+                      "finite": finite}), flush=True)
+    print(json.dumps({"case": "k_d per room", "entry": "full ISM to 60 dB", "fs": fs, "rooms": B, "n_samples": n,
+                      "images_per_room": float(nb60.prod(-1).double().mean()), "reps": 1, "rounds": 3, **stats(timed(full, 1, 3))}), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "rooms":
+        return rooms_main()
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     host_max = float(sys.argv[3]) if len(sys.argv) > 3 else 1e6
