@@ -390,7 +390,8 @@ int nbss_online_advance(int32_t* pos, int C, void* stream);
 /* x += causal T-ConvFFN(x): LayerNorm -> 1x1 -> SiLU -> causal gconv -> SiLU -> causal gconv -> GroupNorm of each FRAME over (24 channels
  * x all F frequencies) -> SiLU -> causal gconv -> SiLU -> 1x1.  w1_t [96][192], w2_t [192][96] transposed; conv weights [192][24][3];
  * s1 s2 s3 [BF][2][192] = the last two input frames of the three convs; a3 [BF][C][192] and gn_sums [B + BF][C][8][2] (the per-frame
- * GroupNorm sums, then every frequency's partials: folded in frequency order, no atomics — bitwise repeatable) are scratch. */
+ * GroupNorm statistics (mean, sum of squared deviations from it), then every frequency's own pair over its 24 channels: combined in
+ * frequency order, no atomics — bitwise repeatable; formed from deviations only, so good for any |mean| / std) are scratch. */
 int nbss_online_tconvffn_step(int B, int F, int C, const float* ln_w, const float* ln_b, const float* w1_t, const float* b1, const float* c1w,
                               const float* c1b, const float* c2w, const float* c2b, const float* gn_w, const float* gn_b, const float* c3w, const float* c3b,
                               const float* w2_t, const float* b2, float* s1, float* s2, float* s3, float* a3, float* gn_sums, float* x, void* stream);

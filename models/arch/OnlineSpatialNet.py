@@ -200,12 +200,15 @@ class OnlineSpatialNet(nn.Module):
         qi = torch.arange(slen, device=device)[:, None] + (klen - slen)
         rel = qi - torch.arange(klen, device=device)[None, :]  # how many frames the key lies in the past
         inside = (rel >= 0) & (rel < self.attn_scope)
+        # additive masks in the module's own floating dtype: nn.MultiheadAttention mis-applies an fp32 mask to fp64 queries without a word
+        dt = self.decoder.weight.dtype
+        ninf = torch.full((), -torch.inf, device=device, dtype=dt)
         if self.rope == "ALiBi":
             assert batch_size is not None
-            slopes = (2.0 ** (-8 / torch.arange(1, self.num_heads + 1, device=device))).reshape(self.num_heads, 1, 1)
-            bias = torch.where(inside, -rel.abs().float(), torch.full((), -torch.inf, device=device))
+            slopes = (2.0 ** (-8 / torch.arange(1, self.num_heads + 1, device=device, dtype=dt))).reshape(self.num_heads, 1, 1)
+            bias = torch.where(inside, -rel.abs().to(dt), ninf)
             return (slopes * bias).repeat(batch_size, 1, 1)  # [batch * heads, slen, klen]
-        return torch.where(inside, 0.0, -torch.inf)
+        return torch.where(inside, torch.zeros((), device=device, dtype=dt), ninf)
 
     # ---- streaming -------------------------------------------------------------------------------------------------------------
     def init_stream(self, batch: int, device=None, dtype=torch.float32) -> Dict[str, Any]:

@@ -7,8 +7,8 @@
 //                          S_t = carry_t S_{t-1} + k_t^T v_t / sqrt(scale_t), o_t = q_t S_t with the [24 x 48] state column of a
 //                          (head, value channel) pair in the registers of its thread -> per-head RMS norm -> SiLU gate -> out_proj -> +res
 //   online_tconv_a_kernel  LayerNorm -> 1x1 (96 -> 192) + SiLU -> causal grouped conv + SiLU -> causal grouped conv (pre-GroupNorm a3),
-//                          conv states = the last two input frames of each conv; per-(frame, group) partial sums of a3, a3^2 of this
-//                          frequency are added to the cross-frequency GroupNorm statistics
+//                          conv states = the last two input frames of each conv; per-(frame, group) mean and squared deviations of a3 at this
+//                          frequency, which online_gn_fold_kernel combines into the cross-frequency GroupNorm statistics
 //   online_tconv_b_kernel  GroupNorm of each FRAME over (24 channels x all frequencies) -> SiLU -> causal conv + SiLU -> 1x1 (192 -> 96) -> +res
 // plus online_encoder_kernel (causal Conv1d k = 5 with a 4-frame state).  The cross-band blocks of a layer are per-frame operations and run
 // through the existing nbss_fconv_fwd / nbss_full_fwd kernels on the [B, F, C, H] chunk; the decoder through nbss_decoder_fwd.  All state
@@ -155,17 +155,19 @@ __global__ __launch_bounds__(ON_FFN) void online_ret_kernel(int C, const float* 
 
 // causal grouped conv (k = 3, 24 channels per group) of output channel j over the padded image in[(C + 2)][192] (rows 0, 1 = the state)
 NBSS_DEV float on_conv3(const float* __restrict__ wrow, float bias, const float* in, int c, int g) {
-    float acc = bias;
+#pragma clang fp reassociate(off)  // keeps the bias LAST under -ffast-math: a bias far above the products (a shifted GroupNorm input) then costs one
+    float acc = 0.f;               // rounding at its magnitude, not 72
 #pragma unroll
     for (int i = 0; i < ON_CG; ++i)
 #pragma unroll
         for (int kk = 0; kk < 3; ++kk) acc += wrow[i * 3 + kk] * in[(c + kk) * ON_FFN + g * ON_CG + i];
-    return acc;
+    return acc + bias;
 }
 
 // first half of the T-ConvFFN (up to the GroupNorm input).  w1_t [96][192]; conv weights [192][24][3] (the module's own layout);
-// s1, s2 [B*F][2][192]: the last two input frames of conv1 / conv2; a3 [B*F][C][192]; gn_part [B*F][C][8][2]: per-frequency partial sums /
-// sums of squares of the GroupNorm input (no atomics: an inference path has to be bitwise repeatable).
+// s1, s2 [B*F][2][192]: the last two input frames of conv1 / conv2; a3 [B*F][C][192]; gn_part [B*F][C][8][2]: this frequency's (mean, M2 = sum of
+// squared deviations from that mean) of the 24 GroupNorm inputs of a (frame, group) — never sums of squares: E[a^2] - mean^2 in fp32 loses the variance
+// once |mean| / std reaches a few hundred (no atomics: an inference path has to be bitwise repeatable).
 __global__ __launch_bounds__(ON_FFN) void online_tconv_a_kernel(int F, int C, const float* __restrict__ lw, const float* __restrict__ lb,
                                                                const float* __restrict__ w1_t, const float* __restrict__ b1,
                                                                const float* __restrict__ c1w, const float* __restrict__ c1b,
@@ -174,9 +176,8 @@ __global__ __launch_bounds__(ON_FFN) void online_tconv_a_kernel(int F, int C, co
                                                                float* __restrict__ gn_part) {
     NBSS_LDS(smem);
     float* u = reinterpret_cast<float*>(smem);   // [C][96]
-    float* h1 = u + C * ON_H;                    // [C + 2][192]
+    float* h1 = u + C * ON_H;                    // [C + 2][192], then the chunk's a3 [C][192]
     float* h2 = h1 + (C + 2) * ON_FFN;           // [C + 2][192]
-    float* red = h2 + (C + 2) * ON_FFN;          // [2][192]
     const int bf = blockIdx.x, b = bf / F, j = threadIdx.x, grp = j / ON_CG;
     on_layernorm(x + (size_t)bf * C * ON_H, C, lw, lb, u);
     h1[j] = s1[(size_t)bf * 2 * ON_FFN + j];
@@ -207,27 +208,49 @@ __global__ __launch_bounds__(ON_FFN) void online_tconv_a_kernel(int F, int C, co
     for (int c = 0; c < C; ++c) {
         const float a = on_conv3(c2w + (size_t)j * ON_CG * 3, c2b[j], h2, c, grp);
         a3[((size_t)bf * C + c) * ON_FFN + j] = a;
-        red[j] = a;
-        red[ON_FFN + j] = a * a;
-        __syncthreads();
-        if (j < 2 * ON_G) {  // threads 0..7: sums, 8..15: sums of squares, one conv group each
-            const int gg = j & 7, kind = j >> 3;
-            float s = 0.f;
-            for (int i = 0; i < ON_CG; ++i) s += red[kind * ON_FFN + gg * ON_CG + i];
-            gn_part[(((size_t)bf * C + c) * ON_G + gg) * 2 + kind] = s;  // this frequency's partial: folded in a fixed order by online_gn_fold_kernel
+        h1[c * ON_FFN + j] = a;  // (h1 is dead since the barrier after conv1: the chunk's a3 for the statistics below)
+    }
+    __syncthreads();
+    // one (frame, group) per thread, p = c * 8 + g: mean and M2 of its 24 values from their deviations from one of them, which are exact or nearly so however
+    // far the common level is from zero.  The differences are the point: -ffast-math must not fold them back into sums of the raw values.
+    for (int p = j; p < C * ON_G; p += ON_FFN) {
+#pragma clang fp reassociate(off)
+        const float* r = h1 + (p >> 3) * ON_FFN + (p & 7) * ON_CG;
+        const float piv = r[0];
+        float sd = 0.f, m2 = 0.f;
+        for (int i = 1; i < ON_CG; ++i) sd += r[i] - piv;
+        const float md = sd * (1.0f / ON_CG);
+        for (int i = 0; i < ON_CG; ++i) {
+            const float d = (r[i] - piv) - md;
+            m2 += d * d;
         }
-        __syncthreads();
+        float* out = gn_part + ((size_t)bf * C * ON_G + p) * 2;  // this frequency's pair: combined in a fixed order by online_gn_fold_kernel
+        out[0] = piv + md;
+        out[1] = m2;
     }
 }
 
-// GroupNorm statistics of a frame span all F frequencies of a batch item: the per-frequency partials are summed in frequency order (one thread
-// per (batch, frame, group, kind)), so the result does not depend on the order in which the first kernel's workgroups finished
-__global__ __launch_bounds__(64) void online_gn_fold_kernel(int F, int n_per_b, const float* __restrict__ gn_part, float* __restrict__ gn_sums) {
-    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;  // i over C * 8 * 2
+// GroupNorm statistics of a frame span all F frequencies of a batch item: the per-frequency (mean_f, M2_f) pairs over 24 values each are combined in
+// frequency order (one thread per (batch, frame, group)), so the result does not depend on the order in which the first kernel's workgroups finished.
+// With d_f = mean_f - mean_0:   mean = mean_0 + sum d_f / F,     M2 = sum M2_f + 24 (sum d_f^2 - (sum d_f)^2 / F)
+// — one pass (the kernel's time is its F dependent rounds of loads), and the only difference of sums left is between deviations from one of the means:
+// it costs at most F ulp of the between-frequency part of M2 (when frequency 0 alone carries it), whatever the common level.  Writes (mean, M2).
+__global__ __launch_bounds__(64) void online_gn_fold_kernel(int F, int n_per_b, const float* __restrict__ gn_part, float* __restrict__ gn_stat) {
+    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;  // i over C * 8
     if (i >= n_per_b) return;
-    float s = 0.f;
-    for (int f = 0; f < F; ++f) s += gn_part[((size_t)b * F + f) * n_per_b + i];
-    gn_sums[(size_t)b * n_per_b + i] = s;
+    const float* p = gn_part + ((size_t)b * F * n_per_b + i) * 2;
+    const float piv = p[0];
+    float sd = 0.f, sq = 0.f, m2 = 0.f;
+    for (int f = 0; f < F; ++f) {
+#pragma clang fp reassociate(off)
+        const float d = p[(size_t)f * n_per_b * 2] - piv;
+        sd += d;
+        sq += d * d;
+        m2 += p[(size_t)f * n_per_b * 2 + 1];
+    }
+    const float md = sd / (float)F;
+    gn_stat[((size_t)b * n_per_b + i) * 2] = piv + md;
+    gn_stat[((size_t)b * n_per_b + i) * 2 + 1] = m2 + (float)ON_CG * fmaxf(sq - sd * md, 0.f);
 }
 
 // second half: GroupNorm of each frame over (24 channels x F frequencies), SiLU, causal conv3 + SiLU, 1x1 (192 -> 96), residual
@@ -244,8 +267,8 @@ __global__ __launch_bounds__(ON_FFN) void online_tconv_b_kernel(int F, int C, co
     const float cnt = (float)(ON_CG * F), gwj = gw[j], gbj = gb[j];
     for (int c = 0; c < C; ++c) {
         const float* sm = gn_sums + (((size_t)b * C + c) * ON_G + grp) * 2;
-        const float mean = sm[0] / cnt;
-        const float rstd = rsqrtf(fmaxf(sm[1] / cnt - mean * mean, 0.f) + 1e-5f);
+        const float mean = sm[0];
+        const float rstd = rsqrtf(sm[1] / cnt + 1e-5f);
         h4[(2 + c) * ON_FFN + j] = on_silu((a3[((size_t)bf * C + c) * ON_FFN + j] - mean) * rstd * gwj + gbj);
     }
     __syncthreads();
@@ -401,11 +424,11 @@ int nbss_online_tconvffn_step(int B, int F, int C, const float* ln_w, const floa
     hipStream_t st = (hipStream_t)stream;
     int e;
     float* gn_part = gn_sums + (size_t)B * C * ON_G * 2;  // [B*F][C][8][2] behind the sums
-    const size_t lds_a = ((size_t)C * ON_H + 2 * (size_t)(C + 2) * ON_FFN + 2 * ON_FFN) * sizeof(float);
+    const size_t lds_a = ((size_t)C * ON_H + 2 * (size_t)(C + 2) * ON_FFN) * sizeof(float);
     if ((e = NBSS_SET_MAX_LDS(online_tconv_a_kernel, lds_a))) return e;
     NBSS_LAUNCH(online_tconv_a_kernel, dim3(B * F), dim3(ON_FFN), lds_a, st, F, C, ln_w, ln_b, w1_t, b1, c1w, c1b, c2w, c2b, s1, s2, (const float*)x, a3, gn_part);
     if ((e = NBSS_CHECK_LAUNCH())) return e;
-    NBSS_LAUNCH(online_gn_fold_kernel, dim3((C * ON_G * 2 + 63) / 64, B), dim3(64), 0, st, F, C * ON_G * 2, (const float*)gn_part, gn_sums);
+    NBSS_LAUNCH(online_gn_fold_kernel, dim3((C * ON_G + 63) / 64, B), dim3(64), 0, st, F, C * ON_G, (const float*)gn_part, gn_sums);
     if ((e = NBSS_CHECK_LAUNCH())) return e;
     const size_t lds_b = ((size_t)(C + 2) * ON_FFN + (size_t)C * ON_FFN) * sizeof(float);
     if ((e = NBSS_SET_MAX_LDS(online_tconv_b_kernel, lds_b))) return e;

@@ -130,7 +130,9 @@ def _native_net(seed=5, **over):
     return net
 
 
-@pytest.mark.parametrize("chunk,over", [(8, {}), (5, {}), (16, {"attention": "ret(2,not_share_qk)"}), (8, {"attention": "mhsa(11)"}), (4, {"attention": "mhsa(40)"})])
+@pytest.mark.parametrize("chunk,over", [(8, {}), (5, {}), (16, {"attention": "ret(2,not_share_qk)"}), (8, {"attention": "mhsa(11)"}), (4, {"attention": "mhsa(40)"}),
+                                        (1, {}), (25, {}), (32, {}), (32, {"attention": "ret(2,not_share_qk)"}), (8, {"attention": "mhsa(3)"}),
+                                        (32, {"attention": "mhsa(1)"})])
 def test_native_streaming_step_matches_module(backend, chunk, over):
     """the HIP streaming step (encoder / retention / T-ConvFFN kernels of csrc/online.hip + the cross-band kernels), chunk by chunk, against the
     module's own whole-utterance forward (parallel retention) and its torch streaming step (the module itself is pinned to the reference by
