@@ -22,6 +22,9 @@ import torch
 from torch import Tensor
 
 from data_loaders.synthetic import rank_strided_indices
+from nbss_amd import ops
+from nbss_amd.ops import TRAJ_MODES
+from nbss_amd.rir import TW, att2t, beta_sabine, rotate_z, simulate_rir, t2n
 
 
 def fft_convolve(x: Tensor, h: Tensor) -> Tensor:
@@ -46,16 +49,21 @@ def convolve_aligned(wav: Tensor, rir: Tensor, rir_target: Optional[Tensor] = No
 CONVOLVE_MODES = ('fft', 'native')
 
 
+def _native_lib(lib, t: Tensor, what: str):
+    """the library of a native path: `lib` when one is handed in (the tests' emulator build), else the product library, which takes device tensors only"""
+    if lib is not None:
+        return lib
+    if not t.is_cuda:
+        raise ValueError(f"{what}='native' runs the HIP kernels and needs tensors on the device; use {what}='fft' on the host")
+    from nbss_amd._lib import hip
+    return hip()
+
+
 def convolve_aligned_native(wav: Tensor, rir: Tensor, rir_target: Optional[Tensor] = None, ref_channel: int = 0, lib=None) -> Tuple[Tensor, Tensor]:
     """convolve_aligned by the HIP kernels of csrc/conv1d.hip: the delay by nbss_rir_delay (the lowest index of the maximum), then one direct
     convolution per RIR set (nbss_fir_convolve) that forms only the N samples from the delay onward; without `rir_target` the same tensor is
     returned twice.  Device tensors only: a host tensor raises ValueError (`lib` lets the tests hand in the emulator build of the same kernels)."""
-    from nbss_amd import ops
-    if lib is None:
-        if not wav.is_cuda:
-            raise ValueError("convolve='native' runs the HIP kernels and needs tensors on the device; use convolve='fft' on the host")
-        from nbss_amd._lib import hip
-        lib = hip()
+    lib = _native_lib(lib, wav, 'convolve')
     wav, rir = wav.float().contiguous(), rir.float().contiguous()
     delay = ops.rir_delay(lib, rir, ref_channel)
     full = ops.fir_convolve(lib, wav, rir, delay, check=False)  # the delays come from rir_delay: inside [0, L)
@@ -72,13 +80,22 @@ def _check_convolve(convolve: str) -> None:
         raise ValueError(f"convolve must be 'fft' or 'native', got {convolve!r}")
 
 
-TRAJ_MODES = ('switch', 'trapezium')
-
-
 def traj_rirs_needed(N: int, hop: int, mode: str = 'trapezium') -> int:
     """RIRs that N source samples need at `hop` samples per trajectory point: ceil(N / hop) when switched (mix.py:171-174), ceil((N + hop - 1) / hop)
     when cross-faded (mix.py:231, len(range(0, N + hop - 1, hop)))"""
     return -(-N // hop) if mode == 'switch' else -(-(N + hop - 1) // hop)
+
+
+def _check_traj(N: int, hmin: int, P: Optional[int], mode: str, ramp: int) -> int:
+    """the checks of a trajectory of P responses (None: as many as needed) for N samples at no fewer than hmin samples per point -> P"""
+    if mode not in TRAJ_MODES:
+        raise ValueError(f"traj mode must be 'switch' or 'trapezium', got {mode!r}")
+    if hmin < 1 or (mode == 'trapezium' and (ramp < 2 or hmin <= ramp)):
+        raise ValueError(f"every hop must be >= 1, and > ramp = {ramp} >= 2 for the trapezium window; the smallest hop is {hmin}")
+    need = traj_rirs_needed(N, hmin, mode)
+    if P is not None and P < need:
+        raise ValueError(f"{P} trajectory points are too few for {N} samples at {hmin} samples per point in mode {mode!r}: {need} are needed")
+    return need if P is None else P
 
 
 def traj_weights(N: int, hop, mode: str = 'trapezium', ramp: int = 20, P: Optional[int] = None, dtype=torch.float32, device=None) -> Tensor:
@@ -87,16 +104,8 @@ def traj_weights(N: int, hop, mode: str = 'trapezium', ramp: int = 20, P: Option
     (mix.py:197-244, convolve_traj_with_win(..., f'trapezium{ramp}')) gives RIR q the weight down(r) and RIR q + 1 the weight up(r): the two halves
     of the reference's window [zeros(z), arange(ramp) / (ramp - 1), ones(2 o), the ramp reversed, zeros(z)], z = (hop - ramp) // 2, o = hop - ramp - z.
     P defaults to what the smallest hop needs; a larger P gives zero rows."""
-    if mode not in TRAJ_MODES:
-        raise ValueError(f"traj mode must be 'switch' or 'trapezium', got {mode!r}")
     hop = torch.as_tensor(hop, device=device).long()
-    hmin = int(hop.min())
-    if hmin < 1 or (mode == 'trapezium' and (ramp < 2 or hmin <= ramp)):
-        raise ValueError(f"every hop must be >= 1, and > ramp = {ramp} >= 2 for the trapezium window; the smallest hop is {hmin}")
-    need = traj_rirs_needed(N, hmin, mode)
-    P = need if P is None else P
-    if P < need:
-        raise ValueError(f"{P} trajectory points are too few for {N} samples at {hmin} samples per point in mode {mode!r}: {need} are needed")
+    P = _check_traj(N, int(hop.min()), P, mode, ramp)
     return torch.stack([_traj_weight_row(N, hop, p, mode, ramp, dtype) for p in range(P)], -2)
 
 
@@ -122,8 +131,6 @@ def convolve_traj_aligned(wav: Tensor, rir: Tensor, hop: Tensor, rir_target: Opt
     convolve: 'fft' (the default, any device: one fft_convolve of the weighted source per trajectory point, accumulated) or 'native'
     (nbss_fir_convolve_traj, csrc/conv_traj.hip: device tensors only, `lib` as in convolve_aligned_native)."""
     _check_convolve(convolve)
-    if mode not in TRAJ_MODES:
-        raise ValueError(f"traj mode must be 'switch' or 'trapezium', got {mode!r}")
     if wav.dim() != 3 or rir.dim() != 5 or rir.shape[:2] != wav.shape[:2] or tuple(hop.shape) != tuple(wav.shape[:2]):
         raise ValueError(f"wav {tuple(wav.shape)} must be [B,S,N], rir {tuple(rir.shape)} [B,S,P,M,L] and hop {tuple(hop.shape)} [B,S]")
     if rir_target is not None and rir_target.shape[:4] != rir.shape[:4]:
@@ -132,15 +139,11 @@ def convolve_traj_aligned(wav: Tensor, rir: Tensor, hop: Tensor, rir_target: Opt
     P, M = rir.shape[2], rir.shape[3]
     first = (rir if rir_target is None else rir_target)[:, :, 0]  # [B,S,M,L']: the delay is that of the first trajectory point
     if convolve == 'native':
-        from nbss_amd import ops
-        if lib is None:
-            if not wav.is_cuda:
-                raise ValueError("convolve='native' runs the HIP kernels and needs tensors on the device; use convolve='fft' on the host")
-            from nbss_amd._lib import hip
-            lib = hip()
+        lib = _native_lib(lib, wav, 'convolve')
         wav, rir, hop32 = wav.float().contiguous(), rir.float().contiguous(), hop.to(torch.int32).contiguous()
         delay = ops.rir_delay(lib, first.float().contiguous(), ref_channel)
-        # one status read-back (a synchronisation) covers the hops and P of both calls; the delay comes from the target and is inside its [0, L')
+        # the mode is checked by ops, the hops and P by the kernel: one status read-back (a synchronisation) covers both calls; the delay comes from
+        # the target and is inside its [0, L')
         try:
             full = ops.fir_convolve_traj(lib, wav, rir, hop32, delay, mode=mode, ramp=ramp, check=True)
         except ops.NbssError as e:
@@ -149,12 +152,7 @@ def convolve_traj_aligned(wav: Tensor, rir: Tensor, hop: Tensor, rir_target: Opt
             return full, full
         return full, ops.fir_convolve_traj(lib, wav, rir_target.float().contiguous(), hop32, delay, mode=mode, ramp=ramp, check=False)
     hop = hop.to(wav.device).long()
-    hmin = int(hop.min())
-    if hmin < 1 or (mode == 'trapezium' and (ramp < 2 or hmin <= ramp)):
-        raise ValueError(f"every hop must be >= 1, and > ramp = {ramp} >= 2 for the trapezium window; the smallest hop is {hmin}")
-    if P < traj_rirs_needed(N, hmin, mode):
-        raise ValueError(f"{P} trajectory points are too few for {N} samples at {hmin} samples per point in mode {mode!r}: "
-                         f"{traj_rirs_needed(N, hmin, mode)} are needed")
+    _check_traj(N, int(hop.min()), P, mode, ramp)
     delay = first[:, :, ref_channel].argmax(-1)
     idx = (delay[:, :, None, None] + torch.arange(N, device=wav.device)[None, None, None, :]).expand(B, S, M, N)
 
@@ -230,12 +228,7 @@ DIFFUSE_MODES = ('fft', 'native')
 def gen_diffuse_noise_native(white: Tensor, L: int, Cs: Tensor, nfft: int = 256, lib=None) -> Tensor:
     """gen_diffuse_noise by the fused HIP kernel of csrc/diffuse.hip (nbss_diffuse_noise): white [..., M, >= L] fp32 -> [..., M, L], Cs [F,M,M] complex.
     Device tensors only: a host tensor raises ValueError (`lib` lets the tests hand in the emulator build of the same kernel)."""
-    from nbss_amd import ops
-    if lib is None:
-        if not white.is_cuda:
-            raise ValueError("diffuse='native' runs the HIP kernel and needs tensors on the device; use diffuse='fft' on the host")
-        from nbss_amd._lib import hip
-        lib = hip()
+    lib = _native_lib(lib, white, 'diffuse')
     if white.dim() < 2 or white.dtype != torch.float32 or white.shape[-1] < L:
         raise ValueError(f"gen_diffuse_noise_native: white must be fp32 [..., M, >= {L}], got {tuple(white.shape)} {white.dtype}")
     lead, M = white.shape[:-2], white.shape[-2]
@@ -349,7 +342,6 @@ class SimulatedRoomDataModule:
         RT60 < 0.161 V / S), wall coefficients, the array (centre at least 0.5 m from the side walls, height in mic_zlim, rotated about z) and the
         speakers (at least 0.3 m from the side walls, height in spk_zlim), and what follows from them: image counts down to 60 dB of decay and the
         RIR length int((max RT60 + 0.1) fs)"""
-        from nbss_amd.rir import att2t, beta_sabine, rotate_z, t2n
         dev = self.device
         u = lambda *shape: torch.rand(*shape, generator=gen, device=dev, dtype=torch.float64)
         lims = torch.tensor(self.room_size_lims, dtype=torch.float64, device=dev)  # [3,2]
@@ -376,26 +368,27 @@ class SimulatedRoomDataModule:
         the scene (items stay addressed by (index, seed))."""
         if self.rir_att_diff is None:
             return {"nb_img": sc["nb_img"]}
-        from nbss_amd.rir import TW, att2t, t2n
-        from nbss_amd.ops import rir_tail_start
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=gen, device=self.device))
         t_diff = att2t(self.rir_att_diff, sc["rt60"])
-        K, n = int(round(TW * self.sr)), sc["n_samples"]
-        for b, (t, rt) in enumerate(zip(t_diff.tolist(), sc["rt60"].tolist())):
-            if not K <= rir_tail_start(t, self.sr) < n:
-                raise ValueError(f"rir_att_diff = {self.rir_att_diff:g} dB puts the diffuse tail of room {b} (RT60 {rt:.3f} s) at sample "
-                                 f"{rir_tail_start(t, self.sr)}, outside {K} <= k_d < {n}")
+        try:
+            ops.rir_tail_starts(t_diff, self.sr, len(t_diff), sc["n_samples"], TW)
+        except ops.RirTailError as e:  # said again in the data module's terms
+            raise ValueError(f"rir_att_diff = {self.rir_att_diff:g} dB puts the diffuse tail of room {e.room} (RT60 {float(sc['rt60'][e.room]):.3f} s) at "
+                             f"sample {e.k_d}, outside {int(round(TW * self.sr))} <= k_d < {sc['n_samples']}") from e
         return {"nb_img": t2n(t_diff, sc["room_sz"]).cpu(), "t_diff": t_diff, "rt60": sc["rt60"], "seed": seed}
 
-    def _ism_rirs(self, B: int, gen: torch.Generator) -> Tuple[Tensor, Tensor]:
-        """(reverberant, direct-path) RIRs [B,S,M,L] of B rooms drawn from `gen`: one simulate_rir call each; with rir_att_diff the reverberant
-        one sums each room's images to that decay only and continues with the diffuse tail (_ism_tail)"""
-        from nbss_amd.rir import simulate_rir
-        sc = self._ism_scene(B, gen)
-        geo = (sc["room_sz"], sc["beta"], sc["pos_src"], sc["pos_rcv"])
-        rir = simulate_rir(*geo, n_samples=sc["n_samples"], fs=self.sr, **self._ism_tail(sc, gen))
-        rir_dp = simulate_rir(geo[0], torch.zeros_like(geo[1]), geo[2], geo[3], (1, 1, 1), sc["n_samples"], self.sr)
+    def _ism_pair(self, sc: Dict[str, Tensor], pos_src: Tensor, gen: torch.Generator) -> Tuple[Tensor, Tensor]:
+        """(reverberant, direct-path) fp32 RIRs [B, sources, M, L] of the scene's rooms for the sources pos_src [B, sources, 3]: one simulate_rir call
+        each; with rir_att_diff the reverberant one sums each room's images to that decay only and continues with the diffuse tail (_ism_tail)"""
+        kw = dict(pos_src=pos_src, pos_rcv=sc["pos_rcv"], n_samples=sc["n_samples"], fs=self.sr)
+        rir = simulate_rir(sc["room_sz"], sc["beta"], **self._ism_tail(sc, gen), **kw)
+        rir_dp = simulate_rir(sc["room_sz"], torch.zeros_like(sc["beta"]), nb_img=(1, 1, 1), **kw)
         return rir.float(), rir_dp.float()
+
+    def _ism_rirs(self, B: int, gen: torch.Generator) -> Tuple[Tensor, Tensor]:
+        """(reverberant, direct-path) RIRs [B,S,M,L] of B rooms drawn from `gen` (_ism_pair)"""
+        sc = self._ism_scene(B, gen)
+        return self._ism_pair(sc, sc["pos_src"], gen)
 
     TRAJ_RAMP = 20         # the reference's 'trapezium20'
     TRAJ_WAVELENGTH = 2.0  # of the lateral wobble, in metres walked
@@ -436,26 +429,20 @@ class SimulatedRoomDataModule:
         return sc, hop, torch.where(walks, speed, torch.zeros_like(speed)), pts
 
     def _ism_traj_rirs(self, B: int, N: int, gen: torch.Generator) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-        """(reverberant, direct-path) RIRs [B,S,P,M,L] along the trajectories of _traj_draws, with its hop and speeds: one simulate_rir call each,
-        with the trajectory points as sources.  With rir_att_diff (_ism_tail) every trajectory point is a source of its own to the kernel and so
+        """(reverberant, direct-path) RIRs [B,S,P,M,L] along the trajectories of _traj_draws, with its hop and speeds: _ism_pair with the
+        trajectory points as sources.  With rir_att_diff (_ism_tail) every trajectory point is a source of its own to the kernel and so
         gets its own tail noise xi(seed, b, s P + p, m, k): the tails of adjacent points are independent, not a continuation of one another."""
-        from nbss_amd.rir import simulate_rir
         sc, hop, speed, pts = self._traj_draws(B, N, gen)
         P = pts.shape[2]
-        src = pts.reshape(B, self.S * P, 3)
-        rir = simulate_rir(sc["room_sz"], sc["beta"], src, sc["pos_rcv"], n_samples=sc["n_samples"], fs=self.sr, **self._ism_tail(sc, gen))
-        rir_dp = simulate_rir(sc["room_sz"], torch.zeros_like(sc["beta"]), src, sc["pos_rcv"], (1, 1, 1), sc["n_samples"], self.sr)
+        rir, rir_dp = self._ism_pair(sc, pts.reshape(B, self.S * P, 3), gen)
         shape = (B, self.S, P, self.C, sc["n_samples"])
-        return rir.float().reshape(shape), rir_dp.float().reshape(shape), hop, speed
+        return rir.reshape(shape), rir_dp.reshape(shape), hop, speed
 
     def batches(self, stage: int, rank: int = 0, world: int = 1, epoch: int = 0):
         N = int(self.audio_time_len[stage] * self.sr)
         bs = self.batch_size[min(stage, len(self.batch_size) - 1)]
         items = rank_strided_indices(self.num_samples[stage], rank, world, epoch, self.seeds[stage], shuffle=stage == 0)
         k = torch.hann_window(33, device=self.device)
-        conv = {} if self.convolve == 'fft' else {"convolve": self.convolve, "lib": self.conv_lib}
-        if self.diffuse != 'fft':
-            conv.update(diffuse=self.diffuse, lib=self.conv_lib)
         for i in range(0, len(items) - bs + 1, bs):
             chunk = items[i:i + bs]
             gen = torch.Generator(device=self.device).manual_seed(int(chunk[0][1]) * 1000003 + int(chunk[0][0]))
@@ -463,18 +450,17 @@ class SimulatedRoomDataModule:
             src = torch.nn.functional.conv1d(src, (k / k.sum())[None, None], padding=16).reshape(bs, self.S, N) * 3.0
             sir = self.sir[0] + (self.sir[1] - self.sir[0]) * torch.rand(bs, generator=gen, device=self.device)
             snr = self.snr[0] + (self.snr[1] - self.snr[0]) * torch.rand(bs, generator=gen, device=self.device)
+            kw, speed = {}, None
             if self.moving is not None:  # moving speakers: trajectories of image-source responses, cross-faded along the source
                 rir, rir_dp, hop, speed = self._ism_traj_rirs(bs, N, gen)
-                mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp, traj_hop=hop,
-                                            traj_ramp=self.TRAJ_RAMP, **conv)
-                speed = speed.tolist()
-                yield mix, tgt, [{"index": ix, "seed": sd, "sample_rate": self.sr, "snr": float(paras["snr"][j]), "sir": float(sir[j]), "speed": speed[j]}
-                                 for j, (ix, sd) in enumerate(chunk)]
-                continue
-            if self.rir == 'ism':  # the targets are the direct-path images
+                kw = dict(rir_target=rir_dp, traj_hop=hop, traj_ramp=self.TRAJ_RAMP)
+            elif self.rir == 'ism':  # the targets are the direct-path images
                 rir, rir_dp = self._ism_rirs(bs, gen)
-                mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, rir_target=rir_dp, **conv)
+                kw = dict(rir_target=rir_dp)
             else:
-                mix, tgt, paras = mix_batch(src, self._rirs(bs, gen), self.Cs, sir if self.S == 2 else None, snr, gen, **conv)
-            yield mix, tgt, [{"index": ix, "seed": sd, "sample_rate": self.sr, "snr": float(paras["snr"][j]), "sir": float(sir[j])}
+                rir = self._rirs(bs, gen)
+            mix, tgt, paras = mix_batch(src, rir, self.Cs, sir if self.S == 2 else None, snr, gen, convolve=self.convolve, diffuse=self.diffuse,
+                                        lib=self.conv_lib, **kw)
+            more = [{}] * bs if speed is None else [{"speed": v} for v in speed.tolist()]
+            yield mix, tgt, [{"index": ix, "seed": sd, "sample_rate": self.sr, "snr": float(paras["snr"][j]), "sir": float(sir[j]), **more[j]}
                              for j, (ix, sd) in enumerate(chunk)]

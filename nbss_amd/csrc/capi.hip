@@ -46,13 +46,10 @@ int sdr_impl(int B, int S, int N, int L, int flags, const float* p, const float*
 size_t recover_scale_ws_bytes_impl(int B, int S);
 int recover_scale_impl(int B, int S, int N, int flags, const float* p, const float* x, float* out, void* ws, hipStream_t st);
 int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img);
-int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
-                 const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
-int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, hipStream_t st);
-int rir_ism_rooms_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, const double* room_sz, const double* beta,
-                       const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
-int rir_tail_rooms_impl(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, const double* rt60, int64_t seed, float* h,
-                        hipStream_t st);
+int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, bool broadcast, const double* room_sz,
+                 const double* beta, const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
+int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, bool broadcast, const double* rt60, int64_t seed, float* h,
+                  hipStream_t st);
 int rir_delay_impl(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, hipStream_t st);
 int fir_convolve_impl(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, hipStream_t st);
 size_t diffuse_noise_ws_bytes_impl(int B, int M);
@@ -522,24 +519,24 @@ int64_t nbss_rir_ism_ws_bytes(int B, const int32_t* nb_img) {
 int nbss_rir_ism(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
                  const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, void* stream) {
     if (!room_sz || !beta || !pos_src || !pos_rcv || !nb_img || !h || !ws) return NBSS_EINVAL;
-    return rir_ism_impl(B, S, M, n_samples, fs, c, tw, k_d, room_sz, beta, pos_src, pos_rcv, nb_img, h, ws, ws_bytes, (hipStream_t)stream);
+    return rir_ism_impl(B, S, M, n_samples, fs, c, tw, &k_d, true, room_sz, beta, pos_src, pos_rcv, nb_img, h, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int nbss_rir_tail(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, void* stream) {
     if (!rt60 || !h) return NBSS_EINVAL;
-    return rir_tail_impl(B, S, M, n_samples, fs, tw, k_d, rt60, seed, h, (hipStream_t)stream);
+    return rir_tail_impl(B, S, M, n_samples, fs, tw, &k_d, true, rt60, seed, h, (hipStream_t)stream);
 }
 
 int nbss_rir_ism_rooms(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, const double* room_sz, const double* beta,
                        const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, void* stream) {
     if (!k_d || !room_sz || !beta || !pos_src || !pos_rcv || !nb_img || !h || !ws) return NBSS_EINVAL;
-    return rir_ism_rooms_impl(B, S, M, n_samples, fs, c, tw, k_d, room_sz, beta, pos_src, pos_rcv, nb_img, h, ws, ws_bytes, (hipStream_t)stream);
+    return rir_ism_impl(B, S, M, n_samples, fs, c, tw, k_d, false, room_sz, beta, pos_src, pos_rcv, nb_img, h, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int nbss_rir_tail_rooms(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, const double* rt60, int64_t seed, float* h,
                         void* stream) {
     if (!k_d || !rt60 || !h) return NBSS_EINVAL;
-    return rir_tail_rooms_impl(B, S, M, n_samples, fs, tw, k_d, rt60, seed, h, (hipStream_t)stream);
+    return rir_tail_impl(B, S, M, n_samples, fs, tw, k_d, false, rt60, seed, h, (hipStream_t)stream);
 }
 
 int nbss_rir_delay(int B, int S, int M, int L, int ref_channel, const float* h, int32_t* delay, void* stream) {

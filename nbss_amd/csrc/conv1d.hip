@@ -31,18 +31,12 @@
 #include "layout.h"
 #include "conv_common.h"
 
-#define CONV_THREADS 256
 #define CONV_TILE 256                       // outputs of one MFMA tile: 16 rows i x 16 columns c
 #define CONV_C 2                            // tiles per wave
 #define CONV_NT (4 * CONV_C * CONV_TILE)    // outputs per workgroup
-#define CONV_QMAX 128                       // tap blocks per chunk
-#define CONV_KT (16 * CONV_QMAX)            // taps per chunk
-#define CONV_TMAX ((CONV_QMAX + 15 + 3) / 4)  // K steps per chunk: the columns w = u + 15 = 0 .. q_count + 14, four per step
-#define CONV_HS 161                         // row of HT in floats: j = i + w <= 15 + 4 CONV_TMAX - 1 = 158
 #define CONV_XS (CONV_NT + 16 * (4 * CONV_TMAX - 1) + 20)  // strip in floats, a multiple of 4: the last read is at CONV_NT + 16 w_max - 223 + 3
 
-static_assert(CONV_XS % 4 == 0 && (16 * CONV_HS) % 4 == 0, "the strip is staged in 16-byte pieces");
-static_assert(15 + 4 * CONV_TMAX - 1 < CONV_HS, "HT row too short");
+static_assert(CONV_XS % 4 == 0, "the strip is staged in 16-byte pieces");
 
 __global__ __launch_bounds__(CONV_THREADS) void rir_delay_kernel(int BS, int M, int L, int ref, const float* __restrict__ h, int32_t* __restrict__ delay) {
     NBSS_LDS(smem);
@@ -81,7 +75,6 @@ __global__ __launch_bounds__(CONV_THREADS) void fir_convolve_kernel(int BS, int 
     NBSS_LDS(smem);
     float* HT = reinterpret_cast<float*>(smem);      // [MB][16][CONV_HS]
     float* XS = HT + MB * 16 * CONV_HS;              // [CONV_XS], 16-byte aligned: 16 CONV_HS floats are a multiple of 16 bytes
-    constexpr int W = VEC ? 4 : 1;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = wave_id_u();
     const int li = lane & 15, kk = lane >> 4;
     const int n0 = (int)blockIdx.x * CONV_NT, m0 = (int)blockIdx.y * MB;
@@ -108,34 +101,7 @@ __global__ __launch_bounds__(CONV_THREADS) void fir_convolve_kernel(int BS, int 
             const int g = n0 - k0 + 225 - 16 * wmax + d, g4 = g & ~3, o = g - g4;
             const int xlen = CONV_NT + 16 * wmax + 20;  // <= CONV_XS, a multiple of 4
             __syncthreads();                            // the previous chunk's (or item's) readers are done
-            // ---- stage the zero columns of HT: j < 15 and j >= 15 + qn
-            {
-                const int pad = CONV_HS - qn;
-                for (int e = tid; e < MB * 16 * pad; e += CONV_THREADS) {
-                    const int rowi = e / pad, pj = e - rowi * pad;
-                    HT[rowi * CONV_HS + (pj < 15 ? pj : pj + qn)] = 0.f;
-                }
-            }
-            // ---- stage the taps, transposed: h[m][k0 + 16 q + r] -> HT[m][r][15 + q]; taps beyond L and microphones beyond M are zero
-            {
-                const int per_m = qn * (16 / W);
-                for (int e = tid; e < MB * per_m; e += CONV_THREADS) {
-                    const int m = e / per_m, rem = e - m * per_m, q = rem / (16 / W), r = (rem - q * (16 / W)) * W;
-                    const int k = k0 + 16 * q + r;
-                    const bool in = m0 + m < M && k < L;  // VEC: L % 4 == 0 and k % 4 == 0, so a piece is inside or outside as a whole
-                    float v[W];
-                    if (VEC) {
-                        f32x4 t = F32X4_ZERO;
-                        if (in) t = *reinterpret_cast<const f32x4*>(hrow + (size_t)m * L + k);
-#pragma unroll
-                        for (int z = 0; z < W; ++z) v[z] = t[z];
-                    } else {
-                        v[0] = in ? hrow[(size_t)m * L + k] : 0.f;
-                    }
-#pragma unroll
-                    for (int z = 0; z < W; ++z) HT[(m * 16 + r + z) * CONV_HS + 15 + q] = v[z];
-                }
-            }
+            conv_stage_taps<MB, VEC>(HT, hrow, m0, M, L, k0, qn, tid);
             // ---- stage the strip of x
             if (VEC) {
                 for (int p = tid * 4; p < xlen; p += CONV_THREADS * 4) {
@@ -206,30 +172,17 @@ int rir_delay_impl(int B, int S, int M, int L, int ref_channel, const float* h, 
     return NBSS_CHECK_LAUNCH();
 }
 
-template <int MB>
-static int conv_launch(bool vec, dim3 grid, size_t lds, hipStream_t st, int BS, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y,
-                       int32_t* status) {
-    if (vec)
-        NBSS_LAUNCH((fir_convolve_kernel<MB, true>), grid, dim3(CONV_THREADS), lds, st, BS, M, N, L, x, h, delay, y, status);
-    else
-        NBSS_LAUNCH((fir_convolve_kernel<MB, false>), grid, dim3(CONV_THREADS), lds, st, BS, M, N, L, x, h, delay, y, status);
-    return NBSS_CHECK_LAUNCH();
-}
-
 int fir_convolve_impl(int B, int S, int M, int N, int L, const float* x, const float* h, const int32_t* delay, float* y, int32_t* status, hipStream_t st) {
     if (N < 1) return NBSS_EINVAL;
     int e = conv_check_rows(B, S, M, L);
     if (e) return e;
     if (N > CONV_MAX_N) return NBSS_EUNSUPPORTED;
     const int BS = B * S;
-    // microphones per workgroup: 3 (the six-microphone arrays take two groups), fewer where 3 would idle a third or more of the accumulators
-    const int MB = (M == 1) ? 1 : (M == 2 || M == 4) ? 2 : 3;
-    const bool vec = N % 4 == 0 && L % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(h)) & 15) == 0;
+    const int MB = conv_mic_group(M);
     const dim3 grid(cdiv(N, CONV_NT), cdiv(M, MB), BS < CONV_MAX_ITEMS ? BS : CONV_MAX_ITEMS);
     const size_t lds = ((size_t)MB * 16 * CONV_HS + CONV_XS) * sizeof(float);  // 48.4 KB at MB = 3: under the 64 KB a kernel gets without asking
-    switch (MB) {
-        case 1: return conv_launch<1>(vec, grid, lds, st, BS, M, N, L, x, h, delay, y, status);
-        case 2: return conv_launch<2>(vec, grid, lds, st, BS, M, N, L, x, h, delay, y, status);
-        default: return conv_launch<3>(vec, grid, lds, st, BS, M, N, L, x, h, delay, y, status);
-    }
+    return conv_dispatch(MB, conv_vec(N, L, x, h), [&](auto mb, auto vec) {
+        NBSS_LAUNCH((fir_convolve_kernel<decltype(mb)::value, decltype(vec)::value>), grid, dim3(CONV_THREADS), lds, st, BS, M, N, L, x, h, delay, y, status);
+        return NBSS_CHECK_LAUNCH();
+    });
 }

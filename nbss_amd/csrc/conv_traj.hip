@@ -26,17 +26,11 @@
 #include "layout.h"
 #include "conv_common.h"
 
-#define TRAJ_THREADS 256
 #define TRAJ_NT 256                          // outputs per workgroup: one MFMA tile, 16 rows i x 16 columns c
-#define TRAJ_QMAX 128                        // tap blocks per chunk
-#define TRAJ_KT (16 * TRAJ_QMAX)             // taps per chunk
-#define TRAJ_TMAX ((TRAJ_QMAX + 15 + 3) / 4) // K steps per chunk: the columns w = u + 15 = 0 .. q_count + 14, four per step
-#define TRAJ_HS 161                          // row of HT in floats: j = i + w <= 15 + 4 TRAJ_TMAX - 1 = 158
-#define TRAJ_XS (16 * (4 * TRAJ_TMAX - 1) + 36)  // strip in floats, a multiple of 4: one tile reads up to li + 15 + 16 w_max + the alignment remainder = 33 + 16 w_max
+#define TRAJ_XS (16 * (4 * CONV_TMAX - 1) + 36)  // strip in floats, a multiple of 4: one tile reads up to li + 15 + 16 w_max + the alignment remainder = 33 + 16 w_max
 
-static_assert(TRAJ_XS % 4 == 0 && (16 * TRAJ_HS) % 4 == 0, "the strip is staged in 16-byte pieces");
-static_assert(15 + 4 * TRAJ_TMAX - 1 < TRAJ_HS, "HT row too short");
-static_assert(3 * TRAJ_NT <= 16 * TRAJ_HS, "the partial sums of waves 1..3 lie over the HT image of as many microphones");
+static_assert(TRAJ_XS % 4 == 0, "the strip is staged in 16-byte pieces");
+static_assert(3 * TRAJ_NT <= 16 * CONV_HS, "the partial sums of waves 1..3 lie over the HT image of as many microphones");
 
 struct TrajWin {  // the window of one item
     int mode, H, ramp, z, o;
@@ -51,14 +45,13 @@ NBSS_DEV float traj_weight(const TrajWin& w, int t) {
 }
 
 template <int MB, bool VEC>
-__global__ __launch_bounds__(TRAJ_THREADS) void fir_convolve_traj_kernel(int BS, int P, int M, int N, int L, int mode, int ramp, const float* __restrict__ x,
+__global__ __launch_bounds__(CONV_THREADS) void fir_convolve_traj_kernel(int BS, int P, int M, int N, int L, int mode, int ramp, const float* __restrict__ x,
                                                                          const float* __restrict__ h, const int32_t* __restrict__ hop,
                                                                          const int32_t* __restrict__ delay, float* __restrict__ y,
                                                                          int32_t* __restrict__ status) {
     NBSS_LDS(smem);
-    float* HT = reinterpret_cast<float*>(smem);      // [MB][16][TRAJ_HS]; after the last point RED [3][MB][4][64]
-    float* XS = HT + MB * 16 * TRAJ_HS;              // [TRAJ_XS], 16-byte aligned: 16 TRAJ_HS floats are a multiple of 16 bytes
-    constexpr int W = VEC ? 4 : 1;
+    float* HT = reinterpret_cast<float*>(smem);      // [MB][16][CONV_HS]; after the last point RED [3][MB][4][64]
+    float* XS = HT + MB * 16 * CONV_HS;              // [TRAJ_XS], 16-byte aligned: 16 CONV_HS floats are a multiple of 16 bytes
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = wave_id_u();
     const int li = lane & 15, kk = lane >> 4;
     const int n0 = (int)blockIdx.x * TRAJ_NT, m0 = (int)blockIdx.y * MB;
@@ -104,45 +97,18 @@ __global__ __launch_bounds__(TRAJ_THREADS) void fir_convolve_traj_kernel(int BS,
             const int a = (int)sa, b = (int)sb;       // the support [a, b), inside [0, N)
             const int klo = n0 + d - (b - 1) > 0 ? n0 + d - (b - 1) : 0, khi = nlast + d - a < L - 1 ? nlast + d - a : L - 1;
             const float* hrow = h + (((size_t)bs * P + p) * M + m0) * (size_t)L;
-            for (int k0 = klo & ~15; k0 <= khi; k0 += TRAJ_KT) {
+            for (int k0 = klo & ~15; k0 <= khi; k0 += CONV_KT) {
                 const int left = khi + 1 - k0;
-                const int qn = left >= TRAJ_KT ? TRAJ_QMAX : (left + 15) >> 4;  // tap blocks of this chunk
+                const int qn = left >= CONV_KT ? CONV_QMAX : (left + 15) >> 4;  // tap blocks of this chunk
                 const int T = (qn + 15 + 3) >> 2, wmax = 4 * T - 1;
                 // the strip: x indices from g = n0 - k0 + 225 - 16 wmax + d, staged from g4 = g rounded down to a multiple of 4
                 const int g = n0 - k0 + 225 - 16 * wmax + d, g4 = g & ~3, oa = g - g4;
                 const int xlen = 16 * wmax + 36;            // <= TRAJ_XS, a multiple of 4: the last word read is 33 + 16 wmax
                 __syncthreads();                            // the previous chunk's (or item's) readers are done
-                // ---- stage the zero columns of HT: j < 15 and j >= 15 + qn
-                {
-                    const int pad = TRAJ_HS - qn;
-                    for (int e = tid; e < MB * 16 * pad; e += TRAJ_THREADS) {
-                        const int rowi = e / pad, pj = e - rowi * pad;
-                        HT[rowi * TRAJ_HS + (pj < 15 ? pj : pj + qn)] = 0.f;
-                    }
-                }
-                // ---- stage the taps, transposed: h[p][m][k0 + 16 q + r] -> HT[m][r][15 + q]; taps beyond L and microphones beyond M are zero
-                {
-                    const int per_m = qn * (16 / W);
-                    for (int e = tid; e < MB * per_m; e += TRAJ_THREADS) {
-                        const int m = e / per_m, rem = e - m * per_m, q = rem / (16 / W), r = (rem - q * (16 / W)) * W;
-                        const int k = k0 + 16 * q + r;
-                        const bool in = m0 + m < M && k < L;  // VEC: L % 4 == 0 and k % 4 == 0, so a piece is inside or outside as a whole
-                        float v[W];
-                        if (VEC) {
-                            f32x4 t = F32X4_ZERO;
-                            if (in) t = *reinterpret_cast<const f32x4*>(hrow + (size_t)m * L + k);
-#pragma unroll
-                            for (int e4 = 0; e4 < W; ++e4) v[e4] = t[e4];
-                        } else {
-                            v[0] = in ? hrow[(size_t)m * L + k] : 0.f;
-                        }
-#pragma unroll
-                        for (int e4 = 0; e4 < W; ++e4) HT[(m * 16 + r + e4) * TRAJ_HS + 15 + q] = v[e4];
-                    }
-                }
+                conv_stage_taps<MB, VEC>(HT, hrow, m0, M, L, k0, qn, tid);
                 // ---- stage the strip of x w_p: zero outside the support [a, b) (a select, not a product with 0)
                 if (VEC) {
-                    for (int s4 = tid * 4; s4 < xlen; s4 += TRAJ_THREADS * 4) {
+                    for (int s4 = tid * 4; s4 < xlen; s4 += CONV_THREADS * 4) {
                         const int gi = g4 + s4;  // a multiple of 4, as N is: the piece is inside or outside [0, N) as a whole
                         f32x4 t = F32X4_ZERO;
                         if (gi + 3 >= a && gi < b) {  // a >= 0 and b <= N: such a piece lies inside [0, N)
@@ -154,7 +120,7 @@ __global__ __launch_bounds__(TRAJ_THREADS) void fir_convolve_traj_kernel(int BS,
                         *reinterpret_cast<f32x4*>(XS + s4) = t;
                     }
                 } else {
-                    for (int s1 = tid; s1 < xlen; s1 += TRAJ_THREADS) {
+                    for (int s1 = tid; s1 < xlen; s1 += CONV_THREADS) {
                         const int gi = g4 + s1;
                         XS[s1] = (gi >= a && gi < b) ? xrow[gi] * traj_weight(win, (int)((long long)gi - c0)) : 0.f;
                     }
@@ -170,7 +136,7 @@ __global__ __launch_bounds__(TRAJ_THREADS) void fir_convolve_traj_kernel(int BS,
                         for (int r = 0; r < 16; ++r) {
                             float av[MB];
 #pragma unroll
-                            for (int m = 0; m < MB; ++m) av[m] = pa[(m * 16 + r) * TRAJ_HS];
+                            for (int m = 0; m < MB; ++m) av[m] = pa[(m * 16 + r) * CONV_HS];
                             const float bv = pb[-r];
 #pragma unroll
                             for (int m = 0; m < MB; ++m) acc[m] = conv_mfma(av[m], bv, acc[m]);
@@ -210,30 +176,18 @@ __global__ __launch_bounds__(TRAJ_THREADS) void fir_convolve_traj_kernel(int BS,
 }
 
 // ---------------- host side ----------------
-template <int MB>
-static int traj_launch(bool vec, dim3 grid, size_t lds, hipStream_t st, int BS, int P, int M, int N, int L, int mode, int ramp, const float* x, const float* h,
-                       const int32_t* hop, const int32_t* delay, float* y, int32_t* status) {
-    if (vec)
-        NBSS_LAUNCH((fir_convolve_traj_kernel<MB, true>), grid, dim3(TRAJ_THREADS), lds, st, BS, P, M, N, L, mode, ramp, x, h, hop, delay, y, status);
-    else
-        NBSS_LAUNCH((fir_convolve_traj_kernel<MB, false>), grid, dim3(TRAJ_THREADS), lds, st, BS, P, M, N, L, mode, ramp, x, h, hop, delay, y, status);
-    return NBSS_CHECK_LAUNCH();
-}
-
 int fir_convolve_traj_impl(int B, int S, int P, int M, int N, int L, int mode, int ramp, const float* x, const float* h, const int32_t* hop, const int32_t* delay,
                            float* y, int32_t* status, hipStream_t st) {
     if (N < 1 || L < 1 || P < 1 || mode < 0 || mode > 1) return NBSS_EINVAL;
     if (B < 1 || S < 1 || M < 1) return NBSS_EUNSUPPORTED;
     if (L > CONV_MAX_L || M > CONV_MAX_M || N > CONV_MAX_N || (int64_t)B * S * P * M > CONV_MAX_ROWS) return NBSS_EUNSUPPORTED;
     const int BS = B * S;
-    // microphones per workgroup as in fir_convolve_impl: a function of M alone, so an item's sum order does not depend on the batch
-    const int MB = (M == 1) ? 1 : (M == 2 || M == 4) ? 2 : 3;
-    const bool vec = N % 4 == 0 && L % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(h)) & 15) == 0;
+    const int MB = conv_mic_group(M);
     const dim3 grid(cdiv(N, TRAJ_NT), cdiv(M, MB), BS < CONV_MAX_ITEMS ? BS : CONV_MAX_ITEMS);
-    const size_t lds = ((size_t)MB * 16 * TRAJ_HS + TRAJ_XS) * sizeof(float);  // 39.3 KB at MB = 3: four workgroups share a CU's 160 KB
-    switch (MB) {
-        case 1: return traj_launch<1>(vec, grid, lds, st, BS, P, M, N, L, mode, ramp, x, h, hop, delay, y, status);
-        case 2: return traj_launch<2>(vec, grid, lds, st, BS, P, M, N, L, mode, ramp, x, h, hop, delay, y, status);
-        default: return traj_launch<3>(vec, grid, lds, st, BS, P, M, N, L, mode, ramp, x, h, hop, delay, y, status);
-    }
+    const size_t lds = ((size_t)MB * 16 * CONV_HS + TRAJ_XS) * sizeof(float);  // 39.3 KB at MB = 3: four workgroups share a CU's 160 KB
+    return conv_dispatch(MB, conv_vec(N, L, x, h), [&](auto mb, auto vec) {
+        NBSS_LAUNCH((fir_convolve_traj_kernel<decltype(mb)::value, decltype(vec)::value>), grid, dim3(CONV_THREADS), lds, st, BS, P, M, N, L, mode, ramp, x, h, hop,
+                    delay, y, status);
+        return NBSS_CHECK_LAUNCH();
+    });
 }

@@ -13,13 +13,12 @@
 //                     The order of the sum is fixed by the room, the pair (source, receiver) and the tile alone: two launches give the same bits, and a
 //                     room's response does not depend on the rooms it shares a launch with.  The terms are fp32, the accumulator is fp64 (one rounding
 //                     at the store).  Every output element is stored exactly once, by its own thread; no atomics.
-//                     rir_ism_rooms_kernel is the same body with the cut-off x_max taken per room: the host's k_d[b] travel by value in the kernel's
-//                     arguments (RirRoomCuts, RIR_ROOMS_PER_LAUNCH rooms per launch; more rooms take more launches), so nothing is written to memory
-//                     for them and the workspace keeps its layout.
+//                     The cut-off x_max is per room: the host's k_d[b] travel by value in the kernel's arguments (RirRoomCuts, RIR_ROOMS_PER_LAUNCH
+//                     rooms per launch; more rooms take more launches), so nothing is written to memory for them and the workspace keeps its
+//                     layout.  The scalar entry points (nbss_rir_ism, nbss_rir_tail) are the same launches with every cut equal.
 //   rir_tail_kernel   one workgroup per (room, source, receiver): g^2 = mean of the K samples before k_d (fp64, fixed order), then for k >= k_d
 //                     g 10^(-3 (k - k_d) / (fs RT60)) xi(seed, b, s, m, k) with xi a Box-Muller Gaussian from a splitmix64 counter hash, all in fp64.
-//
-//                     rir_tail_rooms_kernel: the same body, k_d per room from RirRoomCuts; the workgroups of a room with k_d = 0 return at once.
+//                     k_d per room from RirRoomCuts; the workgroups of a room with k_d = 0 return at once.
 //
 // hann(u) sinc(u) with u = k - x:  0.5 (1 + cos(2 pi u / T)) = cos^2(pi u / T) (no cancellation at the window's ends) and
 // sin(pi u) = -(-1)^(k - xi) sin(pi xf).  With |xf| <= 1/2 the fp32 u = (k - xi) - xf is exact for k = xi and good to half an ulp elsewhere.
@@ -34,7 +33,7 @@
 #define RIR_MAX_WIN 256                   // Tw fs + 1 <= 257
 #define RIR_PI 3.14159265358979323846
 #define RIR_MIN_DIST 1e-3
-#define RIR_ROOMS_PER_LAUNCH 256          // per-room k_d of one launch of the _rooms kernels: 1 KB of kernel arguments (tests/test_rir_rooms_kernels.py passes it)
+#define RIR_ROOMS_PER_LAUNCH 256          // per-room k_d of one launch: 1 KB of kernel arguments (tests/test_rir_rooms_kernels.py passes it)
 
 struct RirRoomCuts {  // k_d of the rooms room0 .. room0 + RIR_ROOMS_PER_LAUNCH - 1 of a launch, passed by value
     int32_t v[RIR_ROOMS_PER_LAUNCH];
@@ -220,19 +219,11 @@ NBSS_DEV void rir_ism_body(int room, int s, int m, int S, int M, int n_samples, 
     if (k < n_samples) out[k] = (float)acc;
 }
 
-__global__ __launch_bounds__(RIR_TILE) void rir_ism_kernel(int S, int M, int n_samples, double fs_over_c, double Tk, double x_max,
+// rooms room0 + blockIdx.z; half_K = round(Tk) / 2: room b admits x < k_d[b] + half_K, every image when k_d[b] = 0
+__global__ __launch_bounds__(RIR_TILE) void rir_ism_kernel(int S, int M, int n_samples, double fs_over_c, double Tk, double half_K, int room0, RirRoomCuts cuts,
                                                            const double* __restrict__ room_sz, const double* __restrict__ pos_src,
                                                            const double* __restrict__ pos_rcv, const int32_t* __restrict__ hdr,
                                                            const double* __restrict__ table, float* __restrict__ h) {
-    rir_ism_body((int)blockIdx.z, (int)blockIdx.y / M, (int)blockIdx.y % M, S, M, n_samples, fs_over_c, Tk, x_max, room_sz, pos_src, pos_rcv, hdr, table, h);
-}
-
-// rooms room0 + blockIdx.z; half_K = round(Tk) / 2: room b admits x < k_d[b] + half_K, every image when k_d[b] = 0
-__global__ __launch_bounds__(RIR_TILE) void rir_ism_rooms_kernel(int S, int M, int n_samples, double fs_over_c, double Tk, double half_K, int room0,
-                                                                 RirRoomCuts cuts, const double* __restrict__ room_sz,
-                                                                 const double* __restrict__ pos_src, const double* __restrict__ pos_rcv,
-                                                                 const int32_t* __restrict__ hdr, const double* __restrict__ table,
-                                                                 float* __restrict__ h) {
     const int k_d = cuts.v[blockIdx.z];
     const double x_max = k_d > 0 ? (double)k_d + half_K : 1e300;
     rir_ism_body(room0 + (int)blockIdx.z, (int)blockIdx.y / M, (int)blockIdx.y % M, S, M, n_samples, fs_over_c, Tk, x_max, room_sz, pos_src, pos_rcv, hdr, table,
@@ -254,9 +245,14 @@ NBSS_DEV double rir_gauss(uint64_t key_bsm, int k) {
     return sqrt(-2.0 * log(u1)) * cos(2.0 * RIR_PI * u2);
 }
 
-// the workgroup of row = (room, s, m) of h
-NBSS_DEV void rir_tail_body(int room, int s, int m, int n_samples, int K, int k_d, double fs, uint64_t seed, const double* __restrict__ rt60,
-                            float* __restrict__ row) {
+// grid (S M, rooms of the launch): the workgroup of row (room0 + blockIdx.y, s, m) of h with the room's own k_d; k_d = 0 leaves the room as it is
+// (uniform per workgroup: no barrier is skipped)
+__global__ __launch_bounds__(256) void rir_tail_kernel(int S, int M, int n_samples, int K, int room0, RirRoomCuts cuts, double fs, uint64_t seed,
+                                                       const double* __restrict__ rt60, float* __restrict__ h) {
+    const int k_d = cuts.v[blockIdx.y];
+    if (k_d == 0) return;
+    const int room = room0 + (int)blockIdx.y, s = (int)blockIdx.x / M, m = (int)blockIdx.x % M;
+    float* row = h + ((size_t)room * (size_t)(S * M) + (size_t)blockIdx.x) * (size_t)n_samples;
     NBSS_LDS(smem);
     double* sq = reinterpret_cast<double*>(smem);  // [K]
     double* gs = sq + RIR_MAX_WIN;                 // [1]
@@ -278,21 +274,6 @@ NBSS_DEV void rir_tail_body(int room, int s, int m, int n_samples, int K, int k_
         row[kq] = (float)(g * exp(-rate * (double)(kq - k_d)) * rir_gauss(key, kq));
 }
 
-__global__ __launch_bounds__(256) void rir_tail_kernel(int S, int M, int n_samples, int K, int k_d, double fs, uint64_t seed, const double* __restrict__ rt60,
-                                                       float* __restrict__ h) {
-    const int room = (int)blockIdx.x / (S * M), sm = (int)blockIdx.x % (S * M);
-    rir_tail_body(room, sm / M, sm % M, n_samples, K, k_d, fs, seed, rt60, h + (size_t)blockIdx.x * (size_t)n_samples);
-}
-
-// grid (S M, rooms of the launch): room room0 + blockIdx.y with its own k_d; k_d = 0 leaves the room as it is (uniform per workgroup: no barrier is skipped)
-__global__ __launch_bounds__(256) void rir_tail_rooms_kernel(int S, int M, int n_samples, int K, int room0, RirRoomCuts cuts, double fs, uint64_t seed,
-                                                             const double* __restrict__ rt60, float* __restrict__ h) {
-    const int k_d = cuts.v[blockIdx.y];
-    if (k_d == 0) return;
-    const int room = room0 + (int)blockIdx.y, sm = (int)blockIdx.x;
-    rir_tail_body(room, sm / M, sm % M, n_samples, K, k_d, fs, seed, rt60, h + ((size_t)room * (size_t)(S * M) + (size_t)sm) * (size_t)n_samples);
-}
-
 // ---------------- host side ----------------
 static int rir_check_common(int B, int S, int M, int n_samples, double fs, double tw) {
     if (!(fs > 0.0) || !(tw > 0.0)) return NBSS_EINVAL;
@@ -301,9 +282,29 @@ static int rir_check_common(int B, int S, int M, int n_samples, double fs, doubl
     return 0;
 }
 
-static int rir_check_tail(int n_samples, double fs, double tw, int k_d) {
-    const int K = (int)llrint(tw * fs);
-    return (k_d < K || k_d >= n_samples) ? NBSS_EUNSUPPORTED : 0;
+// The cuts of a call: one k_d per room, or with `broadcast` one for every room (the scalar entry points).  A negative cut is NBSS_EINVAL, a tail
+// start outside [K, n_samples) NBSS_EUNSUPPORTED; k_d = 0 is "no tail" except with need_tail (nbss_rir_tail), where every cut must be a tail start.
+static int rir_check_cuts(int B, int n_samples, double fs, double tw, const int32_t* k_d, bool broadcast, bool need_tail) {
+    const int nk = broadcast ? 1 : B, K = (int)llrint(tw * fs);
+    for (int b = 0; b < nk && !need_tail; ++b)
+        if (k_d[b] < 0) return NBSS_EINVAL;
+    for (int b = 0; b < nk; ++b)
+        if ((need_tail || k_d[b] > 0) && (k_d[b] < K || k_d[b] >= n_samples)) return NBSS_EUNSUPPORTED;
+    return 0;
+}
+
+// launch(room0, rooms, cuts, any room with a tail) -> return code, once per RIR_ROOMS_PER_LAUNCH rooms
+template <class F>
+static int rir_for_launches(int B, const int32_t* k_d, bool broadcast, F launch) {
+    for (int room0 = 0; room0 < B; room0 += RIR_ROOMS_PER_LAUNCH) {
+        const int nr = B - room0 < RIR_ROOMS_PER_LAUNCH ? B - room0 : RIR_ROOMS_PER_LAUNCH;
+        RirRoomCuts cuts = {};
+        bool any = false;
+        for (int i = 0; i < nr; ++i) any |= (cuts.v[i] = k_d[broadcast ? 0 : room0 + i]) > 0;
+        const int e = launch(room0, nr, cuts, any);
+        if (e) return e;
+    }
+    return 0;
 }
 
 int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img) {
@@ -312,16 +313,13 @@ int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img) {
     return (int64_t)rir_ws_bytes_host(B, nb_img);
 }
 
-// the checks of both ISM entry points and the wall-factor tables of every room into ws
-static int rir_ism_prepare(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, int k_d_stride, const double* beta,
-                           const int32_t* nb_img, void* ws, int64_t ws_bytes, hipStream_t st) {
+// nbss_rir_ism (broadcast: k_d points at its one cut) and nbss_rir_ism_rooms: the checks, the wall-factor tables of every room into ws, the launches
+int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, bool broadcast, const double* room_sz,
+                 const double* beta, const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st) {
     int e = rir_check_common(B, S, M, n_samples, fs, tw);
     if (e) return e;
     if (!(c > 0.0)) return NBSS_EINVAL;
-    for (int b = 0; b < (k_d_stride ? B : 1); ++b)
-        if (k_d[b * k_d_stride] < 0) return NBSS_EINVAL;
-    for (int b = 0; b < (k_d_stride ? B : 1); ++b)
-        if (k_d[b * k_d_stride] > 0 && (e = rir_check_tail(n_samples, fs, tw, k_d[b * k_d_stride]))) return e;
+    if ((e = rir_check_cuts(B, n_samples, fs, tw, k_d, broadcast, false))) return e;
     const int64_t need = rir_ism_ws_bytes_impl(B, nb_img);
     if (need < 0) return (int)need;
     if (ws_bytes < need) return NBSS_EINVAL;
@@ -334,72 +332,26 @@ static int rir_ism_prepare(int B, int S, int M, int n_samples, double fs, double
         if ((e = NBSS_CHECK_LAUNCH())) return e;
         first += Nx + Ny + Nz;
     }
-    return 0;
+    const size_t lds = sizeof(RirEntry) * RIR_TILE * RIR_SLOTS + sizeof(int) * (RIR_TILE + 2);  // 49 KB: three workgroups per CU
+    const double Tk = tw * fs, half_K = 0.5 * (double)llrint(Tk);
+    return rir_for_launches(B, k_d, broadcast, [&](int room0, int nr, const RirRoomCuts& cuts, bool) {
+        NBSS_LAUNCH(rir_ism_kernel, dim3(cdiv(n_samples, RIR_TILE), S * M, nr), dim3(RIR_TILE), lds, st, S, M, n_samples, fs / c, Tk, half_K, room0, cuts, room_sz,
+                    pos_src, pos_rcv, hdr, table, h);
+        return NBSS_CHECK_LAUNCH();
+    });
 }
 
-static const size_t RIR_ISM_LDS = sizeof(RirEntry) * RIR_TILE * RIR_SLOTS + sizeof(int) * (RIR_TILE + 2);  // 49 KB: three workgroups per CU
-
-int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, int k_d, const double* room_sz, const double* beta,
-                 const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st) {
-    const int32_t kd = k_d;
-    const int e = rir_ism_prepare(B, S, M, n_samples, fs, c, tw, &kd, 0, beta, nb_img, ws, ws_bytes, st);
-    if (e) return e;
-    const int32_t* hdr = reinterpret_cast<const int32_t*>(ws);
-    const double* table = reinterpret_cast<const double*>(reinterpret_cast<const char*>(ws) + (size_t)B * 16);
-    const double Tk = tw * fs;
-    const double x_max = k_d > 0 ? (double)k_d + 0.5 * (double)llrint(Tk) : 1e300;
-    NBSS_LAUNCH(rir_ism_kernel, dim3(cdiv(n_samples, RIR_TILE), S * M, B), dim3(RIR_TILE), RIR_ISM_LDS, st, S, M, n_samples, fs / c, Tk, x_max, room_sz, pos_src,
-                pos_rcv, hdr, table, h);
-    return NBSS_CHECK_LAUNCH();
-}
-
-int rir_ism_rooms_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, const double* room_sz, const double* beta,
-                       const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st) {
-    int e = rir_ism_prepare(B, S, M, n_samples, fs, c, tw, k_d, 1, beta, nb_img, ws, ws_bytes, st);
-    if (e) return e;
-    const int32_t* hdr = reinterpret_cast<const int32_t*>(ws);
-    const double* table = reinterpret_cast<const double*>(reinterpret_cast<const char*>(ws) + (size_t)B * 16);
-    const double Tk = tw * fs;
-    const double half_K = 0.5 * (double)llrint(Tk);
-    for (int room0 = 0; room0 < B; room0 += RIR_ROOMS_PER_LAUNCH) {
-        const int nr = B - room0 < RIR_ROOMS_PER_LAUNCH ? B - room0 : RIR_ROOMS_PER_LAUNCH;
-        RirRoomCuts cuts = {};
-        for (int i = 0; i < nr; ++i) cuts.v[i] = k_d[room0 + i];
-        NBSS_LAUNCH(rir_ism_rooms_kernel, dim3(cdiv(n_samples, RIR_TILE), S * M, nr), dim3(RIR_TILE), RIR_ISM_LDS, st, S, M, n_samples, fs / c, Tk, half_K, room0,
-                    cuts, room_sz, pos_src, pos_rcv, hdr, table, h);
-        if ((e = NBSS_CHECK_LAUNCH())) return e;
-    }
-    return 0;
-}
-
-int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, int k_d, const double* rt60, int64_t seed, float* h, hipStream_t st) {
+// nbss_rir_tail (broadcast: one cut, which must be a tail start) and nbss_rir_tail_rooms; a launch in which no room has a tail is skipped
+int rir_tail_impl(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, bool broadcast, const double* rt60, int64_t seed, float* h,
+                  hipStream_t st) {
     int e = rir_check_common(B, S, M, n_samples, fs, tw);
     if (e) return e;
-    if ((e = rir_check_tail(n_samples, fs, tw, k_d))) return e;
-    if ((int64_t)B * S * M > 0x7fffffff) return NBSS_EUNSUPPORTED;
+    if ((e = rir_check_cuts(B, n_samples, fs, tw, k_d, broadcast, broadcast))) return e;
     const int K = (int)llrint(tw * fs);
-    NBSS_LAUNCH(rir_tail_kernel, dim3(B * S * M), dim3(256), (RIR_MAX_WIN + 1) * sizeof(double), st, S, M, n_samples, K, k_d, fs, (uint64_t)seed, rt60, h);
-    return NBSS_CHECK_LAUNCH();
-}
-
-int rir_tail_rooms_impl(int B, int S, int M, int n_samples, double fs, double tw, const int32_t* k_d, const double* rt60, int64_t seed, float* h,
-                        hipStream_t st) {
-    int e = rir_check_common(B, S, M, n_samples, fs, tw);
-    if (e) return e;
-    for (int b = 0; b < B; ++b)
-        if (k_d[b] < 0) return NBSS_EINVAL;
-    for (int b = 0; b < B; ++b)
-        if (k_d[b] > 0 && (e = rir_check_tail(n_samples, fs, tw, k_d[b]))) return e;
-    const int K = (int)llrint(tw * fs);
-    for (int room0 = 0; room0 < B; room0 += RIR_ROOMS_PER_LAUNCH) {
-        const int nr = B - room0 < RIR_ROOMS_PER_LAUNCH ? B - room0 : RIR_ROOMS_PER_LAUNCH;
-        RirRoomCuts cuts = {};
-        bool any = false;
-        for (int i = 0; i < nr; ++i) any |= (cuts.v[i] = k_d[room0 + i]) > 0;
-        if (!any) continue;
-        NBSS_LAUNCH(rir_tail_rooms_kernel, dim3(S * M, nr), dim3(256), (RIR_MAX_WIN + 1) * sizeof(double), st, S, M, n_samples, K, room0, cuts, fs,
-                    (uint64_t)seed, rt60, h);
-        if ((e = NBSS_CHECK_LAUNCH())) return e;
-    }
-    return 0;
+    return rir_for_launches(B, k_d, broadcast, [&](int room0, int nr, const RirRoomCuts& cuts, bool any) {
+        if (!any) return 0;
+        NBSS_LAUNCH(rir_tail_kernel, dim3(S * M, nr), dim3(256), (RIR_MAX_WIN + 1) * sizeof(double), st, S, M, n_samples, K, room0, cuts, fs, (uint64_t)seed, rt60,
+                    h);
+        return NBSS_CHECK_LAUNCH();
+    });
 }

@@ -337,22 +337,32 @@ def rir_tail_start(t_diff: float, fs: float) -> int:
     return int(math.ceil(float(t_diff) * float(fs) - 1e-9))
 
 
+class RirTailError(ValueError):
+    """a diffuse tail that would start at sample `k_d`, outside round(tw fs) <= k_d < n_samples, in room `room` (None for one t_diff for the batch)"""
+
+    def __init__(self, msg: str, room: Optional[int], k_d: int):
+        super().__init__(msg)
+        self.room, self.k_d = room, k_d
+
+
 def rir_tail_starts(t_diff, fs: float, B: int, n_samples: int, tw: float, what: str = "rir_ism") -> List[int]:
     """k_d[b] = rir_tail_start(t_diff[b], fs) of a per-room t_diff (a sequence or a [B] tensor of positive seconds), each checked against the
-    kernels' limits round(tw fs) <= k_d[b] < n_samples; ValueError names the room.  None, NaN or a value <= 0 is no entry: a batch without a
-    tail is t_diff=None."""
-    vals = t_diff.detach().reshape(-1).tolist() if torch.is_tensor(t_diff) else list(t_diff)
-    if len(vals) != B:
+    kernels' limits round(tw fs) <= k_d[b] < n_samples; ValueError (RirTailError for the limits) names the room.  None, NaN or a value <= 0 is
+    no entry: a batch without a tail is t_diff=None.  One number for the batch is checked once and gives B equal entries."""
+    rooms = _per_room(t_diff)
+    vals = [t_diff] if not rooms else t_diff.detach().reshape(-1).tolist() if torch.is_tensor(t_diff) else list(t_diff)
+    if rooms and len(vals) != B:
         raise ValueError(f"{what}: a per-room t_diff needs one value per room, B = {B}, got {len(vals)}")
     K, out = int(round(float(tw) * float(fs))), []
     for b, v in enumerate(vals):
-        if v is None or not float(v) > 0.0 or math.isinf(float(v)):
+        if rooms and (v is None or not float(v) > 0.0 or math.isinf(float(v))):
             raise ValueError(f"{what}: t_diff[{b}] = {v!r} of room {b} must be a positive number of seconds (t_diff=None switches the tail off for every room)")
         k_d = rir_tail_start(v, fs)
         if not K <= k_d < int(n_samples):
-            raise ValueError(f"{what}: the diffuse tail must start at a sample k_d with {K} <= k_d < {int(n_samples)}, got {k_d} for room {b}")
+            raise RirTailError(f"{what}: the diffuse tail must start at a sample k_d with {K} <= k_d < {int(n_samples)}, got {k_d}"
+                               f"{f' for room {b}' if rooms else ''}", b if rooms else None, k_d)
         out.append(k_d)
-    return out
+    return out if rooms else out * B
 
 
 def _per_room(t_diff) -> bool:
@@ -416,6 +426,20 @@ def rir_delay(lib, h, ref_channel: int = 0):
     return delay
 
 
+def _conv_run(lib, fn: str, x, M: int, out, check: bool, call, why: str):
+    """what fir_convolve and fir_convolve_traj share: the output [B,S,M,N] (`out`, checked, or a new tensor), the status word, the library call
+    call(y pointer, status pointer) and, with `check`, the read-back: a status other than 0 raises NBSS_EINVAL with `why`"""
+    B, S, N = x.shape
+    y = torch.empty(B, S, M, N, dtype=torch.float32, device=x.device) if out is None else out
+    if y.shape != (B, S, M, N):
+        raise NbssError(f"{fn}: out must be [B,S,M,N] = {(B, S, M, N)}, got {tuple(y.shape)}")
+    status = torch.zeros(1, dtype=torch.int32, device=x.device) if check else None
+    call(_ptr(lib, y, torch.float32), _ptr(lib, status))
+    if check and int(status.item()) != 0:
+        raise NbssError(f"nbss_{fn} failed: {_ERR[-1]}: {why}")
+    return y
+
+
 def fir_convolve(lib, x, h, delay, check: bool = True, out=None):
     """x [B,S,N], h [B,S,M,L] fp32, delay [B,S] int32 on the same device -> y [B,S,M,N] fp32 with y[b,s,m,n] = sum_k h[b,s,m,k] x[b,s,n + delay[b,s] - k]
     (nbss_fir_convolve: the window of the linear convolution that starts at the delay).  The kernel validates the delays; with `check` the status word
@@ -424,15 +448,9 @@ def fir_convolve(lib, x, h, delay, check: bool = True, out=None):
         raise NbssError(f"fir_convolve: x {tuple(x.shape)} must be [B,S,N], h {tuple(h.shape)} [B,S,M,L] and delay {tuple(delay.shape)} [B,S]")
     B, S, N = x.shape
     M, L = h.shape[2], h.shape[3]
-    y = torch.empty(B, S, M, N, dtype=torch.float32, device=x.device) if out is None else out
-    if y.shape != (B, S, M, N):
-        raise NbssError(f"fir_convolve: out must be [B,S,M,N] = {(B, S, M, N)}, got {tuple(y.shape)}")
-    status = torch.zeros(1, dtype=torch.int32, device=x.device) if check else None
-    lib.call("nbss_fir_convolve", B, S, M, N, L, _ptr(lib, x, torch.float32), _ptr(lib, h, torch.float32), _ptr(lib, delay, torch.int32),
-             _ptr(lib, y, torch.float32), _ptr(lib, status), _stream(lib, x))
-    if check and int(status.item()) != 0:
-        raise NbssError(f"nbss_fir_convolve failed: {_ERR[-1]}: a delay lies outside [0, L = {L})")
-    return y
+    call = lambda y, status: lib.call("nbss_fir_convolve", B, S, M, N, L, _ptr(lib, x, torch.float32), _ptr(lib, h, torch.float32),
+                                      _ptr(lib, delay, torch.int32), y, status, _stream(lib, x))
+    return _conv_run(lib, "fir_convolve", x, M, out, check, call, f"a delay lies outside [0, L = {L})")
 
 
 TRAJ_MODES = {'switch': 0, 'trapezium': 1}
@@ -452,16 +470,11 @@ def fir_convolve_traj(lib, x, h, hop, delay, mode: str = 'trapezium', ramp: int 
                         f"delay {tuple(delay.shape)} [B,S]")
     B, S, N = x.shape
     P, M, L = h.shape[2:]
-    y = torch.empty(B, S, M, N, dtype=torch.float32, device=x.device) if out is None else out
-    if y.shape != (B, S, M, N):
-        raise NbssError(f"fir_convolve_traj: out must be [B,S,M,N] = {(B, S, M, N)}, got {tuple(y.shape)}")
-    status = torch.zeros(1, dtype=torch.int32, device=x.device) if check else None
-    lib.call("nbss_fir_convolve_traj", B, S, P, M, N, L, TRAJ_MODES[mode], int(ramp), _ptr(lib, x, torch.float32), _ptr(lib, h, torch.float32),
-             _ptr(lib, hop, torch.int32), _ptr(lib, delay, torch.int32), _ptr(lib, y, torch.float32), _ptr(lib, status), _stream(lib, x))
-    if check and int(status.item()) != 0:
-        raise NbssError(f"nbss_fir_convolve_traj failed: {_ERR[-1]}: a hop is < 1{' or <= ramp, ramp is < 2' if mode == 'trapezium' else ''}, P = {P} "
-                        f"trajectory points are too few for a hop, or a delay lies outside [0, L = {L})")
-    return y
+    call = lambda y, status: lib.call("nbss_fir_convolve_traj", B, S, P, M, N, L, TRAJ_MODES[mode], int(ramp), _ptr(lib, x, torch.float32),
+                                      _ptr(lib, h, torch.float32), _ptr(lib, hop, torch.int32), _ptr(lib, delay, torch.int32), y, status, _stream(lib, x))
+    return _conv_run(lib, "fir_convolve_traj", x, M, out, check, call,
+                     f"a hop is < 1{' or <= ramp, ramp is < 2' if mode == 'trapezium' else ''}, P = {P} trajectory points are too few for a hop, or a "
+                     f"delay lies outside [0, L = {L})")
 
 
 def diffuse_noise(lib, white, Cs, nfft: int = 256, out=None):

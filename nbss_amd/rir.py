@@ -158,16 +158,10 @@ def _host_ism_room(room: Tensor, beta: Tensor, src: Tensor, rcv: Tensor, nb: Seq
 
 
 def _host_rir(room_sz, beta, pos_src, pos_rcv, nb, n_samples, fs, c, tw, t_diff, rt60, seed) -> Tensor:
-    from .ops import _per_room, rir_tail_start, rir_tail_starts
+    from .ops import rir_tail_starts
     B = room_sz.shape[0]
     K = int(round(tw * fs))
-    if _per_room(t_diff):  # one switch per room
-        k_ds = rir_tail_starts(t_diff, fs, B, n_samples, tw, what="simulate_rir")
-    else:
-        k_d = 0 if t_diff is None else rir_tail_start(t_diff, fs)
-        if t_diff is not None and not (K <= k_d < n_samples):
-            raise ValueError(f"simulate_rir: the diffuse tail must start at a sample k_d with {K} <= k_d < {n_samples}, got {k_d}")
-        k_ds = [k_d] * B
+    k_ds = [0] * B if t_diff is None else rir_tail_starts(t_diff, fs, B, n_samples, tw, what="simulate_rir")  # one number, or one switch per room
     out = []
     for b in range(B):
         k_d = k_ds[b]

@@ -229,3 +229,32 @@ def test_more_rooms_than_one_launch(backend):
         f1 = both(backend, lead(geo, b), nbs[:b + 1], n, k_ds[b], seed=2)[1]
         assert same(full[b], f1[b]), b
         assert float(early[b].abs().max()) > 1e-2  # the direct path is there
+
+
+def test_scalar_entry_points_split_their_launches(backend):
+    """259 rooms through nbss_rir_ism and nbss_rir_tail with one k_d: the scalar entry points are the per-room launches with every cut equal, so
+    they too take a second launch after 256 rooms.  Rooms on both sides of the seam are the bits of the _rooms entry points; rooms of the second
+    launch meet the bars of this file against the host closed form."""
+    B, k_d, seed = ROOMS_PER_LAUNCH + 3, 150, 4
+    geo = scene(B, seed=2, S=1, M=1)
+    nbs = [(3, 3, 3)] * B
+    e_s, f_s = both(backend, geo, nbs, N, k_d, seed)
+    e_r, f_r = both(backend, geo, nbs, N, [k_d] * B, seed)
+    assert torch.isfinite(f_s).all()
+    for b in (0, ROOMS_PER_LAUNCH - 1, ROOMS_PER_LAUNCH, B - 1):
+        assert same(e_s[b], e_r[b]) and same(f_s[b], f_r[b]), b
+        assert not same(f_s[b, ..., k_d:], e_s[b, ..., k_d:])  # the tail is written
+    host = simulate_rir(*geo[:4], nbs, N, FS, t_diff=k_d / FS, rt60=geo[4], seed=seed)
+    worst, worst_t = 0.0, 0.0
+    for b in (ROOMS_PER_LAUNCH, B - 1):
+        mag = ref_magnitudes(geo[0][b].numpy(), geo[1][b].numpy(), geo[2][b].numpy(), geo[3][b].numpy(), nbs[b], N, k_d + K / 2)
+        err = np.abs(f_s[b, ..., :k_d].double().numpy() - host[b, ..., :k_d].numpy())
+        worst = max(worst, float((err / (4e-6 * mag[..., :k_d] + 1e-9)).max()))
+        row = f_s[b, 0, 0].double().numpy()
+        g = math.sqrt(float(np.mean(row[k_d - K:k_d] ** 2)))  # fp64 mean square of the kernel's own early part
+        assert g > 0
+        kk = np.arange(k_d, N)
+        closed = g * 10.0 ** (-3.0 * (kk - k_d) / (FS * float(geo[4][b]))) * tail_gauss(seed, b, 0, 0, kk)
+        worst_t = max(worst_t, float(np.abs(row[k_d:] - closed).max()) / g, float(np.abs(row[k_d:] - host[b, 0, 0, k_d:].numpy()).max()) / g)
+    print(f"{backend.name} scalar k_d over two launches: worst early |h - h_host| / (4e-6 S + 1e-9) = {worst:.3f}, worst tail |h - closed form| / g = {worst_t:.3e}")
+    assert worst <= 1.0 and worst_t <= 1e-5

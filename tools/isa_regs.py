@@ -3,10 +3,12 @@ import re, subprocess, sys, tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from nbss_amd.build import PER_FILE_FLAGS  # noqa: E402  (rir.hip and metrics.hip are built with -fno-fast-math: the registers are those of that build)
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -ffast-math -fno-finite-math-only -Wno-unused-variable -Wno-unused-but-set-variable -Wno-pass-failed -S --cuda-device-only".split()
 for stem in [a for a in sys.argv[1:] if not a.startswith("-D")]:
     out = Path(tempfile.gettempdir()) / f"{stem}.s"
-    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *[a for a in sys.argv if a.startswith("-D")], "-o", str(out), str(ROOT / "nbss_amd" / "csrc" / f"{stem}.hip")], check=True, stderr=subprocess.DEVNULL)
+    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *PER_FILE_FLAGS.get(stem, []), *[a for a in sys.argv if a.startswith("-D")], "-o", str(out), str(ROOT / "nbss_amd" / "csrc" / f"{stem}.hip")], check=True, stderr=subprocess.DEVNULL)
     s = out.read_text()
     for b in s.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", b).group(1)

@@ -5,7 +5,9 @@ batch, wall clock, scaled to the batch; skipped above `host_max_images` images p
     python tools/rir_bench.py [rooms] [reps] [host_max_images]          one JSON line per case; a "RIR" is one (source, receiver) response
     python tools/rir_bench.py rooms [rooms] [reps] [rounds]             the per-room switch (nbss_rir_ism_rooms, nbss_rir_tail_rooms) at 8 kHz:
         "equal k_d": RT60 0.6 s in every room, the scalar entry points and the _rooms entry points on the same inputs, alternating, `rounds` rounds
-        of `reps` calls each (HIP events per round; ms per call: median, min - max over the rounds) and whether the two results are the same bits;
+        of `reps` calls each (HIP events per round; ms per call: median, min - max over the rounds) and whether the two results are the same bits.
+        Both run the same kernels (rir.hip has one image-source and one tail kernel, k_d per room; a scalar k_d is broadcast on the host), so
+        the pair now times one kernel through two entry points: it stays as the guard of the broadcast path, in bits and in time;
         "k_d per room": RT60 drawn in 0.2 - 0.6 s, t_diff[b] = att2t(15, RT60[b]), beside the full sum down to 60 dB of the same rooms"""
 import json
 import sys
