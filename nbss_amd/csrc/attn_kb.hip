@@ -19,13 +19,14 @@
 // (sequence, head) is 4 workgroups at T = 251 instead of 1: 1 032 workgroups for one 129-frequency utterance on 256 CUs).  The 16-byte row padding moves
 // consecutive rows 100 (fp32) / 52 (bf16) banks apart instead of 96 / 48: the 16 rows a ds_read_b128 group touches land on distinct banks but for one pair.
 // Transposed operands (token axis as the K dimension) are read as in the siblings: ds_read_b64_tr_b16 for bf16, element gathers for fp32 (conflict-free:
-// 16 consecutive words x 4 rows that are 400 words apart).
+// 16 consecutive words x 4 rows that are 400 words apart).  Staging, fragments, softmax steps and stores are attn_tiles.h's, with LD = DH + 16 bytes.
 // Tail rows of a block (>= T) are staged as zeros and their scores masked, so any T >= 1 works; the training launchers keep the narrow-band cap of 256 frames.
 //
 // Long sequences (nbss_nb_attention_long_fwd: inference on whole utterances, T <= 4096): the same forward kernel, also instantiated for the narrow heads
 // (DH = 24, 48) the whole-head kernels of gb_attn.hip serve up to 256 frames.  K steps (DH + 31) / 32 with zero fragment lanes from DH on, (DH + 15) / 16
 // output tiles whose rows >= DH are never stored; the backward kernels stay at whole 32-wide K steps (DH = 96).
 #include "kb.h"
+#include "attn_tiles.h"
 #include "layout.h"
 #include "blocks.h"
 #include "nb.h"
@@ -36,7 +37,6 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
                                                                float* __restrict__ lse, float* __restrict__ Dv, int Tn, int H, int heads) {
     static_assert(DH % 8 == 0 && (DH % 32 == 0 || !BWD), "the backward takes whole 32-wide K steps");
     constexpr int KS = (DH + 31) / 32, MTD = (DH + 15) / 16, LD = DH + 16 / sizeof(T), JT = KB_BLK / 16;
-    constexpr bool WHOLE = DH % 32 == 0;  // else: fragment lanes with d0 = 32 ks + 8 g4 >= DH are zeros
     NBSS_LDS(smem);
     T* Ks = reinterpret_cast<T*>(smem);  // [KB_BLK][LD]
     T* Vs = Ks + (size_t)KB_BLK * LD;    // [KB_BLK][LD]
@@ -51,93 +51,59 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
     const bool qv = q < Tn;
     const size_t nq = n0 + (qv ? q : 0);
     const float scale = rsqrtf((float)DH);
-    Frag<T> qf[KS], dof[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        frag_zero(qf[ks]);
-        frag_zero(dof[ks]);
-        if (qv && (WHOLE || 32 * ks + 8 * g4 < DH)) {
-            frag_load(qf[ks], qkv + nq * ld + head * DH + 32 * ks + 8 * g4);
-            if (BWD) frag_load(dof[ks], dO + nq * H + head * DH + 32 * ks + 8 * g4);
-        }
-    }
+    Frag<T> qf[KS], dof[KS];  // (DH % 32 != 0: fragment lanes from DH on are zeros)
+    at_frag_rows<T, DH>(qf, qkv + nq * ld + head * DH, qv);
+    at_frag_rows<T, DH>(dof, BWD ? dO + nq * H + head * DH : nullptr, BWD && qv);
     // ---- sweep 1: O^T = V^T P^T with the running max m and running sum l of the lane's query (the same in its 4 lane groups) ----
     // BWD: D = rowsum(P dP) runs along like l (the same rescale), from the dP tiles of the block — not rowsum(dO o O) afterwards: the same sums as the siblings,
     // and exact where the softmax is (one key: D == dP bit for bit, so dS == 0)
-    float m = -3.0e38f, l = 0.f, dsum = 0.f;
+    float m = AT_NEG, l = 0.f, dsum = 0.f;
     f32x4 oacc[MTD];
 #pragma unroll
     for (int mt = 0; mt < MTD; ++mt) oacc[mt] = F32X4_ZERO;
     for (int b = 0; b < NB; ++b) {
         if (b) lds_barrier();
-        kb_stage<T, DH>(Ks, kbase, ld, b * KB_BLK, Tn);
-        kb_stage<T, DH>(Vs, vbase, ld, b * KB_BLK, Tn);
+        at_stage<T, DH, LD, KB_THREADS>(Ks, kbase, ld, b * KB_BLK, KB_BLK, Tn);
+        at_stage<T, DH, LD, KB_THREADS>(Vs, vbase, ld, b * KB_BLK, KB_BLK, Tn);
         __syncthreads();
         if (!wave_on) continue;
         // S^T tiles: rows = keys 64 b + 16 jt + 4 g4 + r, column = the lane's query
         f32x4 st[JT], dp[JT];
-        float bm = -3.0e38f;
+        float bm = AT_NEG;
 #pragma unroll
         for (int jt = 0; jt < JT; ++jt) {
             st[jt] = dp[jt] = F32X4_ZERO;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 Frag<T> kf, vf;
-                if constexpr (!WHOLE) frag_zero(kf);
-                if (WHOLE || 32 * ks + 8 * g4 < DH) frag_load(kf, Ks + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
+                at_frag_row<T, DH>(kf, Ks + (size_t)(16 * jt + l15) * LD, ks);
                 st[jt] = mma(kf, qf[ks], st[jt]);
                 if (BWD) {
-                    frag_load(vf, Vs + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
+                    at_frag_row<T, DH>(vf, Vs + (size_t)(16 * jt + l15) * LD, ks);
                     dp[jt] = mma(vf, dof[ks], dp[jt]);
                 }
             }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool kv = b * KB_BLK + 16 * jt + 4 * g4 + r < Tn;
-                st[jt][r] = kv ? st[jt][r] * scale : -3.0e38f;
-                bm = fmaxf(bm, st[jt][r]);
-            }
+            bm = fmaxf(bm, at_mask_scale_max<1>(st + jt, b * KB_BLK + 16 * jt, Tn, scale));
         }
         const float mn = fmaxf(m, wave_max16(bm));  // (every block holds at least one valid key: finite from the first block on)
-        const float alpha = __expf(m - mn);
-        float ps = 0.f, pd = 0.f;
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool kv = b * KB_BLK + 16 * jt + 4 * g4 + r < Tn;
-                st[jt][r] = kv ? __expf(st[jt][r] - mn) : 0.f;
-                ps += st[jt][r];
-                if (BWD) pd += st[jt][r] * dp[jt][r];
-            }
-        l = l * alpha + wave_sum16(ps);
+        float pd = 0.f;
+        const float ps = at_exp_sum<JT, BWD>(st, b * KB_BLK, Tn, mn, dp, &pd);
+        const float alpha = at_online_rescale<MTD>(m, l, oacc, mn, wave_sum16(ps));
         if (BWD) dsum = dsum * alpha + wave_sum16(pd);
-        m = mn;
-#pragma unroll
-        for (int mt = 0; mt < MTD; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) oacc[mt][r] *= alpha;
 #pragma unroll
         for (int kk = 0; kk < JT / 2; ++kk) {
             Frag<T> pf;
             frag_from_c2(pf, st[2 * kk], st[2 * kk + 1]);
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) {
-                Frag<T> vt;
-                kb_frag_t<T, DH>(vt, Vs, 32 * kk, mt);
-                oacc[mt] = mma(vt, pf, oacc[mt]);
-            }
+            at_mma_t<T, DH, LD>(oacc, Vs, 32 * kk, pf);
         }
     }
     const float inv = 1.0f / l;
     if (wave_on) {
 #pragma unroll
-        for (int mt = 0; mt < MTD; ++mt) {
-            const int d = 16 * mt + 4 * g4;
+        for (int mt = 0; mt < MTD; ++mt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) oacc[mt][r] *= inv;
-            if (qv && (DH % 16 == 0 || d < DH)) store4(O + nq * H + head * DH + d, oacc[mt][0], oacc[mt][1], oacc[mt][2], oacc[mt][3]);
-        }
+        if (qv) at_store_row<T, DH>(O + nq * H + head * DH, oacc);
     }
     if (!BWD) return;
     dsum *= inv;  // D = rowsum(P dP) = rowsum(dO o O)
@@ -153,8 +119,8 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
     for (int b = NB - 1; b >= 0; --b) {
         if (b != NB - 1) {
             lds_barrier();
-            kb_stage<T, DH>(Ks, kbase, ld, b * KB_BLK, Tn);
-            kb_stage<T, DH>(Vs, vbase, ld, b * KB_BLK, Tn);
+            at_stage<T, DH, LD, KB_THREADS>(Ks, kbase, ld, b * KB_BLK, KB_BLK, Tn);
+            at_stage<T, DH, LD, KB_THREADS>(Vs, vbase, ld, b * KB_BLK, KB_BLK, Tn);
             __syncthreads();
         }
         if (!wave_on) continue;
@@ -165,8 +131,8 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 Frag<T> kf, vf;
-                frag_load(kf, Ks + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
-                frag_load(vf, Vs + (size_t)(16 * jt + l15) * LD + 32 * ks + 8 * g4);
+                at_frag_row<T, DH>(kf, Ks + (size_t)(16 * jt + l15) * LD, ks);
+                at_frag_row<T, DH>(vf, Vs + (size_t)(16 * jt + l15) * LD, ks);
                 s = mma(kf, qf[ks], s);
                 dp = mma(vf, dof[ks], dp);
             }
@@ -181,19 +147,10 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_q_kernel(const T* __restri
         for (int kk = 0; kk < JT / 2; ++kk) {
             Frag<T> dsf;
             frag_from_c2(dsf, ds[2 * kk], ds[2 * kk + 1]);
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) {
-                Frag<T> kt;
-                kb_frag_t<T, DH>(kt, Ks, 32 * kk, mt);
-                qacc[mt] = mma(kt, dsf, qacc[mt]);
-            }
+            at_mma_t<T, DH, LD>(qacc, Ks, 32 * kk, dsf);
         }
     }
-    if (wave_on && qv) {
-#pragma unroll
-        for (int mt = 0; mt < MTD; ++mt)
-            store4(dqkv + nq * ld + head * DH + 16 * mt + 4 * g4, qacc[mt][0], qacc[mt][1], qacc[mt][2], qacc[mt][3]);
-    }
+    if (wave_on && qv) at_store_row<T, DH>(dqkv + nq * ld + head * DH, qacc);
 }
 
 template <class T, int DH>
@@ -216,22 +173,15 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_k_kernel(const T* __restri
     const size_t nk = n0 + (kv ? key : 0);
     const float scale = rsqrtf((float)DH);
     Frag<T> kf[KS], vf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        frag_zero(kf[ks]);
-        frag_zero(vf[ks]);
-        if (kv) {
-            frag_load(kf[ks], qkv + nk * ld + H + head * DH + 32 * ks + 8 * g4);
-            frag_load(vf[ks], qkv + nk * ld + 2 * H + head * DH + 32 * ks + 8 * g4);
-        }
-    }
+    at_frag_rows<T, DH>(kf, qkv + nk * ld + H + head * DH, kv);
+    at_frag_rows<T, DH>(vf, qkv + nk * ld + 2 * H + head * DH, kv);
     f32x4 kacc[MTD], vacc[MTD];
 #pragma unroll
     for (int mt = 0; mt < MTD; ++mt) kacc[mt] = vacc[mt] = F32X4_ZERO;
     for (int b = 0; b < NB; ++b) {
         if (b) lds_barrier();
-        kb_stage<T, DH>(Qs, qkv + n0 * ld + head * DH, ld, b * KB_BLK, Tn);
-        kb_stage<T, DH>(dOs, dO + n0 * H + head * DH, H, b * KB_BLK, Tn);
+        at_stage<T, DH, LD, KB_THREADS>(Qs, qkv + n0 * ld + head * DH, ld, b * KB_BLK, KB_BLK, Tn);
+        at_stage<T, DH, LD, KB_THREADS>(dOs, dO + n0 * H + head * DH, H, b * KB_BLK, KB_BLK, Tn);
         if (threadIdx.x < KB_BLK) {
             const int t = b * KB_BLK + (int)threadIdx.x;
             ls[threadIdx.x] = t < Tn ? lse[(n0 + t) * heads + head] : 0.f;
@@ -250,8 +200,8 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_k_kernel(const T* __restri
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     Frag<T> qf, dof;
-                    frag_load(qf, Qs + (size_t)(16 * it + l15) * LD + 32 * ks + 8 * g4);
-                    frag_load(dof, dOs + (size_t)(16 * it + l15) * LD + 32 * ks + 8 * g4);
+                    at_frag_row<T, DH>(qf, Qs + (size_t)(16 * it + l15) * LD, ks);
+                    at_frag_row<T, DH>(dof, dOs + (size_t)(16 * it + l15) * LD, ks);
                     s = mma(qf, kf[ks], s);
                     dpv = mma(dof, vf[ks], dpv);
                 }
@@ -267,23 +217,13 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_k_kernel(const T* __restri
             Frag<T> pf, dsf;
             frag_from_c2(pf, pt[0], pt[1]);
             frag_from_c2(dsf, dst[0], dst[1]);
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) {
-                Frag<T> dot, qt;
-                kb_frag_t<T, DH>(dot, dOs, 32 * kk, mt);
-                kb_frag_t<T, DH>(qt, Qs, 32 * kk, mt);
-                vacc[mt] = mma(dot, pf, vacc[mt]);
-                kacc[mt] = mma(qt, dsf, kacc[mt]);
-            }
+            at_mma_t<T, DH, LD>(vacc, dOs, 32 * kk, pf);
+            at_mma_t<T, DH, LD>(kacc, Qs, 32 * kk, dsf);
         }
     }
     if (wave_on && kv) {
-#pragma unroll
-        for (int mt = 0; mt < MTD; ++mt) {
-            const int d = 16 * mt + 4 * g4;
-            store4(dqkv + nk * ld + H + head * DH + d, kacc[mt][0], kacc[mt][1], kacc[mt][2], kacc[mt][3]);
-            store4(dqkv + nk * ld + 2 * H + head * DH + d, vacc[mt][0], vacc[mt][1], vacc[mt][2], vacc[mt][3]);
-        }
+        at_store_row<T, DH>(dqkv + nk * ld + H + head * DH, kacc);
+        at_store_row<T, DH>(dqkv + nk * ld + 2 * H + head * DH, vacc);
     }
 }
 
@@ -308,20 +248,16 @@ static int kb_attn_bwd(long nseq, int Tn, int H, int heads, const void* qkv, con
 // head width 96 (nb_blocks.hip dispatches here: nb_attention_fwd_impl / nb_attention_bwd_impl); same tensors and workspace pieces as the narrow kernels
 int nb_attention_kb_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st) {
     if (heads <= 0 || H != heads * 96 || Tn > KB_TMAX || heads > 65535) return NBSS_EUNSUPPORTED;
-    return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 96>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 96>(nseq, Tn, H, heads, qkv, o, st);
+    return AT_DISPATCH(dtype, kb_attn_fwd, 96, nseq, Tn, H, heads, qkv, o, st);
 }
 int nb_attention_kb_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, const void* dO, void* O, void* dqkv, float* lse, float* Dv, hipStream_t st) {
     if (heads <= 0 || H != heads * 96 || Tn > KB_TMAX || heads > 65535) return NBSS_EUNSUPPORTED;
-    return dtype == NBSS_BF16 ? kb_attn_bwd<bf16_t, 96>(nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st)
-                              : kb_attn_bwd<float, 96>(nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st);
+    return AT_DISPATCH(dtype, kb_attn_bwd, 96, nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st);
 }
 // forward on long sequences (nbss_nb_attention_long_fwd): the key-blocked kernel at every head width the narrow-band networks use, T <= KB_TLONG
 int nb_attention_long_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st) {
     if (heads <= 0 || H % heads) return NBSS_EINVAL;
     if (Tn > KB_TLONG || heads > 65535) return NBSS_EUNSUPPORTED;
     const int dh = H / heads;
-    if (dh == 96) return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 96>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 96>(nseq, Tn, H, heads, qkv, o, st);
-    if (dh == 48) return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 48>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 48>(nseq, Tn, H, heads, qkv, o, st);
-    if (dh == 24) return dtype == NBSS_BF16 ? kb_attn_fwd<bf16_t, 24>(nseq, Tn, H, heads, qkv, o, st) : kb_attn_fwd<float, 24>(nseq, Tn, H, heads, qkv, o, st);
-    return NBSS_EUNSUPPORTED;
+    return dh == 96 ? AT_DISPATCH(dtype, kb_attn_fwd, 96, nseq, Tn, H, heads, qkv, o, st) : AT_DISPATCH_NARROW(dtype, dh, kb_attn_fwd, nseq, Tn, H, heads, qkv, o, st);
 }

@@ -1,6 +1,9 @@
 // attn_relpos.hip — attention with Transformer-XL relative positions, forward and backward: the narrow-band conformer NBC (nbss_nb_attention_relpos_*).
-// Whole-head kernels on the LDS images of gb.h (ga_stage / ga_frag_t), as gb_attn.hip's; nothing in SpatialNet uses them.
+// Whole-head kernels as gb_attn.hip's, on the LDS images of attn_tiles.h (at_stage / at_frag_t); nothing in SpatialNet uses them.
+// These kernels keep their own inline K-step loops (content MFMA and the two position MFMAs under one d0 guard), softmax steps and stores: written on
+// at_pos_tiles / at_frag_row / at_mask_scale_max the forward at width 24 and the NBC training step measured 1 - 5 % slower (profiles/README.md).
 #include "gb.h"
+#include "attn_tiles.h"
 #include "nb.h"
 
 // Attention forward with Transformer-XL relative positions (the narrow-band conformer NBC: models/arch/NBC.py:106-143 in the reference):
@@ -23,9 +26,9 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_relpos_kernel(const T* __r
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
     const size_t n0 = (size_t)seq * Tn;
     const int ld = 3 * H;
-    ga_stage<T, DH>(Ks, qkv + n0 * ld + H + head * DH, ld, Tn, TP);
-    ga_stage<T, DH>(Vs, qkv + n0 * ld + 2 * H + head * DH, ld, Tn, TP);
-    ga_stage<T, DH>(Ps, pos + head * DH, H, NR, RP);
+    at_stage<T, DH, DH, GB_THREADS>(Ks, qkv + n0 * ld + H + head * DH, ld, 0, TP, Tn);
+    at_stage<T, DH, DH, GB_THREADS>(Vs, qkv + n0 * ld + 2 * H + head * DH, ld, 0, TP, Tn);
+    at_stage<T, DH, DH, GB_THREADS>(Ps, pos + head * DH, H, 0, RP, NR);
     __syncthreads();
     for (int qt = w; qt < NT; qt += GB_THREADS / 64) {
         const int q = qt * 16 + l15;
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_relpos_kernel(const T* __r
 #pragma unroll
                 for (int mt = 0; mt < MTD; ++mt) {
                     Frag<T> vt;
-                    ga_frag_t<T, DH>(vt, Vs, 32 * kk, mt);
+                    at_frag_t<T, DH, DH>(vt, Vs, 32 * kk, mt);
                     oacc[mt] = mma(vt, pf, oacc[mt]);
                 }
             }
@@ -159,7 +162,7 @@ template <class T, int DH>
 NBSS_DEV void rel_stage_pos(T* Ps, const T* __restrict__ pos, int H, int head, int Tn) {
     const int RPP = rel_rpp(Tn);
     for (int i = threadIdx.x; i < RB_PAD * DH; i += GB_THREADS) store1(Ps + i, 0.f);
-    ga_stage<T, DH>(Ps + RB_PAD * DH, pos + head * DH, H, 2 * Tn - 1, RPP - RB_PAD);
+    at_stage<T, DH, DH, GB_THREADS>(Ps + RB_PAD * DH, pos + head * DH, H, 0, RPP - RB_PAD, 2 * Tn - 1);
 }
 // rows t of the head's q slice + a per-head bias [DH] (q + u, q + v: rounded to the stream dtype like the forward's fragments), zero rows up to TP
 template <class T, int DH>
@@ -227,8 +230,8 @@ __global__ __launch_bounds__(GB_THREADS) void rel_bwd_q_kernel(RelBwd a) {
     const T* qkv = reinterpret_cast<const T*>(a.qkv);
     const T* dO = reinterpret_cast<const T*>(a.dO);
     T* dqkv = reinterpret_cast<T*>(a.dqkv);
-    ga_stage<T, DH>(Ks, qkv + n0 * ld + H + head * DH, ld, Tn, TP);
-    ga_stage<T, DH>(Vs, qkv + n0 * ld + 2 * H + head * DH, ld, Tn, TP);
+    at_stage<T, DH, DH, GB_THREADS>(Ks, qkv + n0 * ld + H + head * DH, ld, 0, TP, Tn);
+    at_stage<T, DH, DH, GB_THREADS>(Vs, qkv + n0 * ld + 2 * H + head * DH, ld, 0, TP, Tn);
     rel_stage_pos<T, DH>(Ps, reinterpret_cast<const T*>(a.pos), H, head, Tn);
     __syncthreads();
     const float scale = a.scale, keep = a.keep;
@@ -330,7 +333,7 @@ __global__ __launch_bounds__(GB_THREADS) void rel_bwd_q_kernel(RelBwd a) {
 #pragma unroll
                 for (int mt = 0; mt < MTD; ++mt) {
                     Frag<T> kt;
-                    ga_frag_t<T, DH>(kt, Ks, 32 * kk, mt);
+                    at_frag_t<T, DH, DH>(kt, Ks, 32 * kk, mt);
                     qc_acc[mt] = mma(kt, dsf, qc_acc[mt]);
                 }
                 // position part, tile by tile: E[query][offset r' = i - j + 15] = dS -> dq += P[rb + r']^T E
@@ -351,7 +354,7 @@ __global__ __launch_bounds__(GB_THREADS) void rel_bwd_q_kernel(RelBwd a) {
 #pragma unroll
                         for (int mt = 0; mt < MTD; ++mt) {
                             Frag<T> pt;
-                            ga_frag_t<T, DH>(pt, Ps, rbp, mt);
+                            at_frag_t<T, DH, DH>(pt, Ps, rbp, mt);
                             qp_acc[mt] = mma(pt, ef, qp_acc[mt]);
                         }
                     }
@@ -461,7 +464,7 @@ NBSS_DEV void rel_stage_common(const RelBwd& a, int seq, int head, T* Qu, T* Qv,
     const T* qkv = reinterpret_cast<const T*>(a.qkv);
     if (Qu) rel_stage_qb<T, DH>(Qu, qkv + n0 * 3 * H + head * DH, 3 * H, a.ub + head * DH, Tn, TP);
     rel_stage_qb<T, DH>(Qv, qkv + n0 * 3 * H + head * DH, 3 * H, a.vb + head * DH, Tn, TP);
-    if (dOs) ga_stage<T, DH>(dOs, reinterpret_cast<const T*>(a.dO) + n0 * H + head * DH, H, Tn, TP);
+    if (dOs) at_stage<T, DH, DH, GB_THREADS>(dOs, reinterpret_cast<const T*>(a.dO) + n0 * H + head * DH, H, 0, TP, Tn);
     rel_stage_pos<T, DH>(Ps, reinterpret_cast<const T*>(a.pos), H, head, Tn);
     for (int t = threadIdx.x; t < TP; t += GB_THREADS) {
         ls[t] = t < Tn ? a.lse[(n0 + t) * heads + head] : 0.f;
@@ -521,8 +524,8 @@ __global__ __launch_bounds__(GB_THREADS) void rel_bwd_k_kernel(RelBwd a) {
 #pragma unroll
             for (int mt = 0; mt < MTD; ++mt) {
                 Frag<T> dot, qt;
-                ga_frag_t<T, DH>(dot, dOs, 32 * kk, mt);
-                ga_frag_t<T, DH>(qt, Qu, 32 * kk, mt);
+                at_frag_t<T, DH, DH>(dot, dOs, 32 * kk, mt);
+                at_frag_t<T, DH, DH>(qt, Qu, 32 * kk, mt);
                 vacc[mt] = mma(dot, pf, vacc[mt]);
                 kacc[mt] = mma(qt, dsf, kacc[mt]);
             }
@@ -598,7 +601,7 @@ __global__ __launch_bounds__(GB_THREADS) void rel_bwd_r_kernel(RelBwd a) {
 #pragma unroll
                 for (int mt = 0; mt < MTD; ++mt) {
                     Frag<T> qt;
-                    ga_frag_t<T, DH>(qt, Qv, 16 * it, mt);
+                    at_frag_t<T, DH, DH>(qt, Qv, 16 * it, mt);
                     acc[mt] = mma(qt, ef, acc[mt]);
                 }
             }
@@ -658,13 +661,7 @@ int nb_attention_relpos_fwd_impl(int dtype, long nseq, int Tn, int H, int heads,
                                  hipStream_t st, const uint32_t* mask, float keep) {
     if (heads <= 0 || H % heads) return NBSS_EINVAL;
     const int dh = H / heads;
-    if (dh == 48)
-        return dtype == NBSS_BF16 ? nb_attn_relpos<bf16_t, 48>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st, mask, keep)
-                                  : nb_attn_relpos<float, 48>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st, mask, keep);
-    if (dh == 24)
-        return dtype == NBSS_BF16 ? nb_attn_relpos<bf16_t, 24>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st, mask, keep)
-                                  : nb_attn_relpos<float, 24>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st, mask, keep);
-    return NBSS_EUNSUPPORTED;
+    return AT_DISPATCH_NARROW(dtype, dh, nb_attn_relpos, nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st, mask, keep);
 }
 // backward of the relative-position attention: ws = lse [N][heads] | D [N][heads] | du/dvb shares [nseq][heads][2][dh] | dP shares [nseq][heads][32 NT][dh] (fp32)
 size_t nb_relpos_bwd_ws_bytes_impl(long nseq, int Tn, int H, int heads) {
@@ -706,7 +703,5 @@ int nb_attention_relpos_bwd_impl(int dtype, long nseq, int Tn, int H, int heads,
     if (heads <= 0 || H % heads) return NBSS_EINVAL;
     const int dh = H / heads;
     RelBwd a = {qkv, pos, dO, ub, vb, mask, dqkv, nullptr, nullptr, nullptr, nullptr, scale, keep, Tn, H, heads};
-    if (dh == 48) return dtype == NBSS_BF16 ? nb_relpos_bwd<bf16_t, 48>(nseq, a, dpos, du, dvb, ws, st) : nb_relpos_bwd<float, 48>(nseq, a, dpos, du, dvb, ws, st);
-    if (dh == 24) return dtype == NBSS_BF16 ? nb_relpos_bwd<bf16_t, 24>(nseq, a, dpos, du, dvb, ws, st) : nb_relpos_bwd<float, 24>(nseq, a, dpos, du, dvb, ws, st);
-    return NBSS_EUNSUPPORTED;
+    return AT_DISPATCH_NARROW(dtype, dh, nb_relpos_bwd, nseq, a, dpos, du, dvb, ws, st);
 }

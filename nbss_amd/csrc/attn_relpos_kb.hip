@@ -9,8 +9,11 @@
 // LDS, read back along the diagonal r' = i - j + 15.
 // LDS: 256 rows x (DH + 16 bytes of padding) + the head's u | v + 4 x 2 KB: 61.8 KB in fp32 at DH = 48 (two workgroups per CU), 25 KB in bf16 at DH = 24.
 // The 256 rows are 256 x PR 16-byte pieces, PR per thread: all of a block's global reads are issued before its LDS stores, none of them inside a branch
-// (addresses are clamped into the tensors, the values of rows outside replaced by zeros).  Every output element has one writer, no atomics.
+// (addresses are clamped into the tensors, the values of rows outside replaced by zeros) — this kernel's own staging, not at_stage.  Of attn_tiles.h it
+// uses the transposed fragments (at_frag_t) and the dispatch; its K-step loop, softmax steps and store stay inline: on the shared helpers the width-48
+// instances measured 2 % slower (profiles/README.md).  Every output element has one writer, no atomics.
 #include "kb.h"
+#include "attn_tiles.h"
 #include "layout.h"
 #include "nb.h"
 
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(KB_THREADS) void kb_attn_relpos_kernel(const T* __r
 #pragma unroll
             for (int mt = 0; mt < MTD; ++mt) {
                 Frag<T> vt;
-                kb_frag_t<T, DH>(vt, Vs, 32 * kk, mt);
+                at_frag_t<T, DH, LD>(vt, Vs, 32 * kk, mt);
                 oacc[mt] = mma(vt, pf, oacc[mt]);
             }
         }
@@ -175,11 +178,5 @@ int nb_attention_relpos_long_fwd_impl(int dtype, long nseq, int Tn, int H, int h
     if (heads <= 0 || H % heads) return NBSS_EINVAL;
     if (Tn > KB_TLONG || heads > 65535) return NBSS_EUNSUPPORTED;
     const int dh = H / heads;
-    if (dh == 48)
-        return dtype == NBSS_BF16 ? kb_attn_relpos<bf16_t, 48>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st)
-                                  : kb_attn_relpos<float, 48>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st);
-    if (dh == 24)
-        return dtype == NBSS_BF16 ? kb_attn_relpos<bf16_t, 24>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st)
-                                  : kb_attn_relpos<float, 24>(nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st);
-    return NBSS_EUNSUPPORTED;
+    return AT_DISPATCH_NARROW(dtype, dh, kb_attn_relpos, nseq, Tn, H, heads, qkv, pos, ub, vb, scale, o, st);
 }

@@ -2,7 +2,8 @@
 // building blocks) are sequenced from.  One tensor pass each, every intermediate in the caller's workspace:
 //   gb_gemm.hip   weight re-lay + tap_gemm: every per-token linear map, the grouped convolutions along F and along T, the LinearGroup and their data gradients
 //   gb_rows.hip   LayerNorm / GroupNorm / GroupBatchNorm forward and backward, SiLU / PReLU backward, the full-band transposes, the decoder's column padding
-//   gb_attn.hip   whole-head attention (head widths 24 and 48): forward alone, and forward + backward in two kernels per (sequence, head)
+//   gb_attn.hip   whole-head attention (head widths 24 and 48): forward alone, and forward + backward in two kernels per (sequence, head); the device
+//                 helpers of its kernels (LDS images, fragments, softmax steps) are attn_tiles.h's, shared with the other attention sources
 // Every launcher is a template on the stream type (float, bf16_t), takes untyped tensor pointers, the stream last, and returns an NBSS_* code; the file
 // that defines it instantiates it for both types.
 #pragma once
@@ -134,31 +135,3 @@ int gb_attn_launch(const nbss_cfg& c, const void* qkv, const void* dO, void* O, 
 // the forward alone
 template <class T, int DH>
 int nb_attn_fwd(long nseq, int Tn, int H, int heads, const void* qkv, void* o, hipStream_t st);
-
-// ---- device helpers of the whole-head attention kernels (gb_attn.hip, attn_relpos.hip): a head's rows as row-major [token][DH] LDS images ------
-NBSS_DEV int ga_perm_k(int g4, int j) { return j < 4 ? 4 * g4 + j : 16 + 4 * g4 + (j - 4); }
-
-// A fragment whose K dimension is the token axis (permuted order: two stacked C tiles), rows = channels 16 mt + l15, from a row-major
-// [token][DH] LDS image: bf16 through two transposing reads (ds_read_b64_tr_b16), fp32 element by element
-template <class T, int DH>
-NBSS_DEV void ga_frag_t(Frag<T>& f, const T* img, int tok0, int mt) {
-    const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4;
-    if constexpr (sizeof(T) == 2) {
-        frag_load_tr(f, img + (size_t)(tok0 + 4 * g4 + (l15 >> 2)) * DH + 16 * mt + 4 * (l15 & 3), DH);
-    } else {
-        const int d = 16 * mt + l15;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) frag_set(f, j, d < DH ? load1(img + (size_t)(tok0 + ga_perm_k(g4, j)) * DH + d) : 0.f);
-    }
-}
-// rows of the head's [Tn][DH] slice of a [N][ld] tensor into a row-major image, zero rows up to TP: 16-byte pieces
-template <class T, int DH>
-NBSS_DEV void ga_stage(T* img, const T* src, int ld, int Tn, int TP) {
-    constexpr int VE = 16 / sizeof(T), PR = DH / VE;
-    for (int e = threadIdx.x; e < TP * PR; e += GB_THREADS) {
-        const int t = e / PR, pc = e % PR;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (t < Tn) v = *reinterpret_cast<const u32x4*>(src + (size_t)t * ld + pc * VE);
-        *reinterpret_cast<u32x4*>(img + (size_t)t * DH + pc * VE) = v;
-    }
-}

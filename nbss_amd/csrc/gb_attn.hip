@@ -3,8 +3,10 @@
 // scores = q k^T / sqrt(DH), softmax over the keys, O = P V.
 //   kernel Q (queries are the MFMA N dimension; K, V of the head in LDS):  O, lse = log sum exp, D = rowsum(P dP), dQ
 //   kernel K (keys are the N dimension; Q, dO of the head in LDS):         dK, dV
-// Transposed operands (V^T, K^T, Q^T, dO^T: the token axis as K dimension) are gathered from the row-major LDS images element by element.
+// The row-major [TP][DH] LDS images, their transposed reads (V^T, K^T, Q^T, dO^T: the token axis as K dimension), the softmax steps and the store of the
+// output tiles are attn_tiles.h's, shared with the key-blocked and the relative-position kernels.
 #include "gb.h"
+#include "attn_tiles.h"
 
 // BWD = false: the forward alone (O; dO / dqkv / lse / Dv are not touched) — the attention of the narrow-band building blocks (nbss_nb_attention_fwd)
 template <class T, int DH, bool BWD>
@@ -19,8 +21,8 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_q_kernel(const T* __restri
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
     const size_t n0 = (size_t)seq * Tn;
     const int ld = 3 * H;
-    ga_stage<T, DH>(Ks, qkv + n0 * ld + H + head * DH, ld, Tn, TP);
-    ga_stage<T, DH>(Vs, qkv + n0 * ld + 2 * H + head * DH, ld, Tn, TP);
+    at_stage<T, DH, DH, GB_THREADS>(Ks, qkv + n0 * ld + H + head * DH, ld, 0, TP, Tn);
+    at_stage<T, DH, DH, GB_THREADS>(Vs, qkv + n0 * ld + 2 * H + head * DH, ld, 0, TP, Tn);
     __syncthreads();
     const float scale = rsqrtf((float)DH);
     for (int qt = w; qt < NT; qt += GB_THREADS / 64) {
@@ -28,20 +30,11 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_q_kernel(const T* __restri
         const bool qv = q < Tn;
         const size_t nq = n0 + (qv ? q : 0);
         Frag<T> qf[KS], dof[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int d0 = 32 * ks + 8 * g4;
-            frag_zero(dof[ks]);
-            if (qv && d0 < DH) {
-                frag_load(qf[ks], qkv + nq * ld + head * DH + d0);
-                if (BWD) frag_load(dof[ks], dO + nq * H + head * DH + d0);
-            } else {
-                frag_zero(qf[ks]);
-            }
-        }
+        at_frag_rows<T, DH>(qf, qkv + nq * ld + head * DH, qv);
+        at_frag_rows<T, DH>(dof, BWD ? dO + nq * H + head * DH : nullptr, BWD && qv);
         // S^T and dP^T tiles: rows = keys 16 jt + 4 g4 + r, column = the lane's query
         f32x4 st[NTM], dp[NTM];
-        float mx = -3.0e38f;
+        float mx = AT_NEG;
 #pragma unroll
         for (int jt = 0; jt < NTM; ++jt) {
             st[jt] = F32X4_ZERO;
@@ -49,37 +42,19 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_q_kernel(const T* __restri
             if (jt < NT) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    const int d0 = 32 * ks + 8 * g4;
                     Frag<T> kf, vf;
-                    if (d0 < DH) {
-                        frag_load(kf, Ks + (size_t)(16 * jt + l15) * DH + d0);
-                        frag_load(vf, Vs + (size_t)(16 * jt + l15) * DH + d0);
-                    } else {
-                        frag_zero(kf);
-                        frag_zero(vf);
-                    }
+                    at_frag_row<T, DH>(kf, Ks + (size_t)(16 * jt + l15) * DH, ks);
                     st[jt] = mma(kf, qf[ks], st[jt]);
-                    if (BWD) dp[jt] = mma(vf, dof[ks], dp[jt]);
+                    if (BWD) {
+                        at_frag_row<T, DH>(vf, Vs + (size_t)(16 * jt + l15) * DH, ks);
+                        dp[jt] = mma(vf, dof[ks], dp[jt]);
+                    }
                 }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const bool kv = 16 * jt + 4 * g4 + r < Tn;
-                    st[jt][r] = kv ? st[jt][r] * scale : -3.0e38f;
-                    mx = fmaxf(mx, st[jt][r]);
-                }
+                mx = fmaxf(mx, at_mask_scale_max<1>(st + jt, 16 * jt, Tn, scale));
             }
         }
         mx = wave_max16(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int jt = 0; jt < NTM; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool kv = jt < NT && 16 * jt + 4 * g4 + r < Tn;
-                st[jt][r] = kv ? __expf(st[jt][r] - mx) : 0.f;
-                sum += st[jt][r];
-            }
-        sum = wave_sum16(sum);
+        const float sum = wave_sum16(at_exp_sum<NTM>(st, 0, Tn, mx));
         const float inv = 1.0f / sum;
         float dsum = 0.f;
 #pragma unroll
@@ -110,27 +85,13 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_q_kernel(const T* __restri
                 Frag<T> pf, dsf;
                 frag_from_c2(pf, st[2 * kk], st[2 * kk + 1]);
                 frag_from_c2(dsf, ds0, ds1);
-#pragma unroll
-                for (int mt = 0; mt < MTD; ++mt) {
-                    Frag<T> vt, kt;
-                    ga_frag_t<T, DH>(vt, Vs, 32 * kk, mt);
-                    oacc[mt] = mma(vt, pf, oacc[mt]);
-                    if (BWD) {
-                        ga_frag_t<T, DH>(kt, Ks, 32 * kk, mt);
-                        qacc[mt] = mma(kt, dsf, qacc[mt]);
-                    }
-                }
+                at_mma_t<T, DH, DH>(oacc, Vs, 32 * kk, pf);
+                if (BWD) at_mma_t<T, DH, DH>(qacc, Ks, 32 * kk, dsf);
             }
         }
         if (qv) {
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) {
-                const int d = 16 * mt + 4 * g4;
-                if (d < DH) {
-                    store4(O + nq * H + head * DH + d, oacc[mt][0], oacc[mt][1], oacc[mt][2], oacc[mt][3]);
-                    if (BWD) store4(dqkv + nq * ld + head * DH + d, qacc[mt][0], qacc[mt][1], qacc[mt][2], qacc[mt][3]);
-                }
-            }
+            at_store_row<T, DH>(O + nq * H + head * DH, oacc);
+            if (BWD) at_store_row<T, DH>(dqkv + nq * ld + head * DH, qacc);
         }
     }
 }
@@ -149,8 +110,8 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_k_kernel(const T* __restri
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id();
     const size_t n0 = (size_t)seq * Tn;
     const int ld = 3 * H;
-    ga_stage<T, DH>(Qs, qkv + n0 * ld + head * DH, ld, Tn, TP);
-    ga_stage<T, DH>(dOs, dO + n0 * H + head * DH, H, Tn, TP);
+    at_stage<T, DH, DH, GB_THREADS>(Qs, qkv + n0 * ld + head * DH, ld, 0, TP, Tn);
+    at_stage<T, DH, DH, GB_THREADS>(dOs, dO + n0 * H + head * DH, H, 0, TP, Tn);
     for (int t = threadIdx.x; t < TP; t += GB_THREADS) {
         ls[t] = t < Tn ? lse[(n0 + t) * heads + head] : 0.f;
         Ds[t] = t < Tn ? Dv[(n0 + t) * heads + head] : 0.f;
@@ -162,17 +123,8 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_k_kernel(const T* __restri
         const bool kv = key < Tn;
         const size_t nk = n0 + (kv ? key : 0);
         Frag<T> kf[KS], vf[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int d0 = 32 * ks + 8 * g4;
-            if (kv && d0 < DH) {
-                frag_load(kf[ks], qkv + nk * ld + H + head * DH + d0);
-                frag_load(vf[ks], qkv + nk * ld + 2 * H + head * DH + d0);
-            } else {
-                frag_zero(kf[ks]);
-                frag_zero(vf[ks]);
-            }
-        }
+        at_frag_rows<T, DH>(kf, qkv + nk * ld + H + head * DH, kv);
+        at_frag_rows<T, DH>(vf, qkv + nk * ld + 2 * H + head * DH, kv);
         f32x4 kacc[MTD], vacc[MTD];
 #pragma unroll
         for (int mt = 0; mt < MTD; ++mt) kacc[mt] = vacc[mt] = F32X4_ZERO;
@@ -185,15 +137,9 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_k_kernel(const T* __restri
                 f32x4 s = F32X4_ZERO, dpv = F32X4_ZERO;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    const int d0 = 32 * ks + 8 * g4;
                     Frag<T> qf, dof;
-                    if (d0 < DH) {
-                        frag_load(qf, Qs + (size_t)(16 * it + l15) * DH + d0);
-                        frag_load(dof, dOs + (size_t)(16 * it + l15) * DH + d0);
-                    } else {
-                        frag_zero(qf);
-                        frag_zero(dof);
-                    }
+                    at_frag_row<T, DH>(qf, Qs + (size_t)(16 * it + l15) * DH, ks);
+                    at_frag_row<T, DH>(dof, dOs + (size_t)(16 * it + l15) * DH, ks);
                     s = mma(qf, kf[ks], s);
                     dpv = mma(dof, vf[ks], dpv);
                 }
@@ -209,24 +155,12 @@ __global__ __launch_bounds__(GB_THREADS) void gb_attn_k_kernel(const T* __restri
             Frag<T> pf, dsf;
             frag_from_c2(pf, pt[0], pt[1]);
             frag_from_c2(dsf, dst[0], dst[1]);
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) {
-                Frag<T> dot, qt;
-                ga_frag_t<T, DH>(dot, dOs, 32 * kk, mt);
-                ga_frag_t<T, DH>(qt, Qs, 32 * kk, mt);
-                vacc[mt] = mma(dot, pf, vacc[mt]);
-                kacc[mt] = mma(qt, dsf, kacc[mt]);
-            }
+            at_mma_t<T, DH, DH>(vacc, dOs, 32 * kk, pf);
+            at_mma_t<T, DH, DH>(kacc, Qs, 32 * kk, dsf);
         }
         if (kv) {
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) {
-                const int d = 16 * mt + 4 * g4;
-                if (d < DH) {
-                    store4(dqkv + nk * ld + H + head * DH + d, kacc[mt][0], kacc[mt][1], kacc[mt][2], kacc[mt][3]);
-                    store4(dqkv + nk * ld + 2 * H + head * DH + d, vacc[mt][0], vacc[mt][1], vacc[mt][2], vacc[mt][3]);
-                }
-            }
+            at_store_row<T, DH>(dqkv + nk * ld + H + head * DH, kacc);
+            at_store_row<T, DH>(dqkv + nk * ld + 2 * H + head * DH, vacc);
         }
     }
 }

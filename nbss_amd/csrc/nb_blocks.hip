@@ -1,8 +1,9 @@
 // nb_blocks.hip — the narrow-band building blocks behind the C ABI (nbss_nb_*: include/nbss_hip.h; prototypes: nb.h).
 // The generic pieces of gb.h, one operation per call on caller-owned tensors: what a narrow-band network other than SpatialNet (NBC2: pre-norm
 // attention over time + convolutional feed-forward with GroupBatchNorm; NBC; NBC2-large) is sequenced from on the host side (nbss_amd/nbc2.py).
-// The relative-position attention of NBC is attn_relpos.hip, head width 96 attn_kb.hip.
+// The relative-position attention of NBC is attn_relpos.hip, head width 96 attn_kb.hip; the (dtype, head width) dispatch is attn_tiles.h's AT_DISPATCH.
 #include "gb.h"
+#include "attn_tiles.h"
 #include "nb.h"
 #include "wgrad.h"
 
@@ -41,9 +42,7 @@ int nb_attention_fwd_impl(int dtype, long nseq, int Tn, int H, int heads, const 
     if (heads <= 0 || H % heads) return NBSS_EINVAL;
     const int dh = H / heads;
     if (dh == 96) return nb_attention_kb_fwd_impl(dtype, nseq, Tn, H, heads, qkv, o, st);
-    if (dh == 48) return dtype == NBSS_BF16 ? nb_attn_fwd<bf16_t, 48>(nseq, Tn, H, heads, qkv, o, st) : nb_attn_fwd<float, 48>(nseq, Tn, H, heads, qkv, o, st);
-    if (dh == 24) return dtype == NBSS_BF16 ? nb_attn_fwd<bf16_t, 24>(nseq, Tn, H, heads, qkv, o, st) : nb_attn_fwd<float, 24>(nseq, Tn, H, heads, qkv, o, st);
-    return NBSS_EUNSUPPORTED;
+    return AT_DISPATCH_NARROW(dtype, dh, nb_attn_fwd, nseq, Tn, H, heads, qkv, o, st);
 }
 
 // GroupNorm forward that keeps its (mean, rstd) per (sequence, group) for nb_group_norm_bwd_impl (dx in place of dy; dgamma / dbeta accumulated)
@@ -147,7 +146,5 @@ int nb_attention_bwd_impl(int dtype, long nseq, int Tn, int H, int heads, const 
     float* Dv = (float*)((char*)lse + ws_align((size_t)N * heads * sizeof(float)));
     const int dh = H / heads;
     if (dh == 96) return nb_attention_kb_bwd_impl(dtype, nseq, Tn, H, heads, qkv, dO, O, dqkv, lse, Dv, st);
-    if (dh == 48) return dtype == NBSS_BF16 ? gb_attn_launch<bf16_t, 48>(c, qkv, dO, O, dqkv, lse, Dv, st) : gb_attn_launch<float, 48>(c, qkv, dO, O, dqkv, lse, Dv, st);
-    if (dh == 24) return dtype == NBSS_BF16 ? gb_attn_launch<bf16_t, 24>(c, qkv, dO, O, dqkv, lse, Dv, st) : gb_attn_launch<float, 24>(c, qkv, dO, O, dqkv, lse, Dv, st);
-    return NBSS_EUNSUPPORTED;
+    return AT_DISPATCH_NARROW(dtype, dh, gb_attn_launch, c, qkv, dO, O, dqkv, lse, Dv, st);
 }

@@ -14,6 +14,7 @@ from util import rel_l2
 
 DTYPES = [pytest.param(NBSS_F32, id="f32"), pytest.param(NBSS_BF16, id="bf16")]
 DH = 96
+NARROW = [24, 48]  # the whole-head kernels behind the same two entry points
 # the lengths the narrow heads are tested at, plus those that straddle the 64-row block: block - 1, block, block + 1, two blocks + 1
 LENGTHS = [1, 2, 15, 16, 17, 31, 33, 48, 100, 255, 256, 63, 64, 65, 129]
 GOLDEN = Path(__file__).resolve().parent / "golden" / "nbc2_head96.npz"
@@ -24,25 +25,26 @@ def _td(dtype):
 
 
 def _attn64(qkv64, nseq, T, heads):
-    H = heads * DH
-    q, k, v = [t.reshape(nseq, T, heads, DH).transpose(1, 2) for t in qkv64.split(H, dim=-1)]
-    return (torch.softmax(q @ k.transpose(-1, -2) / DH ** 0.5, -1) @ v).transpose(1, 2).reshape(nseq, T, H)
+    H = qkv64.shape[-1] // 3
+    dh = H // heads
+    q, k, v = [t.reshape(nseq, T, heads, dh).transpose(1, 2) for t in qkv64.split(H, dim=-1)]
+    return (torch.softmax(q @ k.transpose(-1, -2) / dh ** 0.5, -1) @ v).transpose(1, 2).reshape(nseq, T, H)
 
 
-def _fwd(backend, dtype, qkv):
+def _fwd(backend, dtype, qkv, heads):
     """qkv: stream-dtype host tensor -> o on the backend's device"""
     lib, dev = backend.lib, backend.device
     nseq, T, H3 = qkv.shape
     qd = qkv.to(dev).contiguous()
     o = torch.full((nseq, T, H3 // 3), float("nan"), dtype=qd.dtype, device=dev)
-    lib.call("nbss_nb_attention_fwd", dtype, nseq, T, H3 // 3, H3 // 3 // DH, ops._ptr(lib, qd), ops._ptr(lib, o), ops._stream(lib, qd))
+    lib.call("nbss_nb_attention_fwd", dtype, nseq, T, H3 // 3, heads, ops._ptr(lib, qd), ops._ptr(lib, o), ops._stream(lib, qd))
     return o
 
 
-def _bwd(backend, dtype, qkv, do):
+def _bwd(backend, dtype, qkv, do, heads):
     lib, dev = backend.lib, backend.device
     nseq, T, H3 = qkv.shape
-    H, heads = H3 // 3, H3 // 3 // DH
+    H = H3 // 3
     qd, dd = qkv.to(dev).contiguous(), do.to(dev).contiguous()
     dqkv = torch.full((nseq, T, H3), float("nan"), dtype=qd.dtype, device=dev)
     ws = torch.empty(lib._dll.nbss_nb_attention_bwd_ws_bytes(dtype, nseq, T, H, heads), dtype=torch.uint8, device=dev)
@@ -58,35 +60,50 @@ def _grad64(qkv, do, nseq, T, heads):
 
 def _torch_bf16_grad(qkv, do, nseq, T, heads):
     """torch's own bf16 computation (host, bf16 tensors throughout) of the same forward + autograd backward"""
-    H = heads * DH
+    H = qkv.shape[-1] // 3
+    dh = H // heads
     qb = qkv.to(torch.bfloat16).requires_grad_(True)
-    q, k, v = [t.reshape(nseq, T, heads, DH).transpose(1, 2) for t in qb.split(H, dim=-1)]
-    o = (torch.softmax(q @ k.transpose(-1, -2) / DH ** 0.5, -1) @ v).transpose(1, 2).reshape(nseq, T, H)
+    q, k, v = [t.reshape(nseq, T, heads, dh).transpose(1, 2) for t in qb.split(H, dim=-1)]
+    o = (torch.softmax(q @ k.transpose(-1, -2) / dh ** 0.5, -1) @ v).transpose(1, 2).reshape(nseq, T, H)
     o.backward(do.to(torch.bfloat16))
     return qb.grad
 
 
 def _check_fwd(backend, dtype, qkv, nseq, T, heads):
     qs = qkv.to(_td(dtype))
-    e = rel_l2(_fwd(backend, dtype, qs), _attn64(qs.double(), nseq, T, heads))
-    print(f"attention96 fwd {backend.name} dtype={dtype} heads={heads} T={T}: rel_l2 {e:.3e}")
+    e = rel_l2(_fwd(backend, dtype, qs, heads), _attn64(qs.double(), nseq, T, heads))
+    print(f"attention fwd {backend.name} dtype={dtype} dh={qkv.shape[-1] // 3 // heads} heads={heads} T={T}: rel_l2 {e:.3e}")
     assert e < (2e-5 if dtype == NBSS_F32 else 1.5e-2), (T, heads, e)
 
 
 def _check_bwd(backend, dtype, qkv, do, nseq, T, heads):
     qs, ds = qkv.to(_td(dtype)), do.to(_td(dtype))
     want = _grad64(qs, ds, nseq, T, heads)  # (the fp64 formula on the inputs as the stream holds them)
-    got = _bwd(backend, dtype, qs, ds)
-    again = _bwd(backend, dtype, qs, ds)
+    got = _bwd(backend, dtype, qs, ds, heads)
+    again = _bwd(backend, dtype, qs, ds, heads)
     assert torch.equal(got, again), "the backward is not repeatable"
     e = rel_l2(got, want)
     if dtype == NBSS_F32:
-        print(f"attention96 bwd {backend.name} f32 heads={heads} T={T}: rel_l2 {e:.3e}")
+        print(f"attention bwd {backend.name} f32 dh={qkv.shape[-1] // 3 // heads} heads={heads} T={T}: rel_l2 {e:.3e}")
         assert e < 5e-5, (T, heads, e)
     else:
         e_torch = rel_l2(_torch_bf16_grad(qs, ds, nseq, T, heads), want)
-        print(f"attention96 bwd {backend.name} bf16 heads={heads} T={T}: torch-bf16 {e_torch:.3e}  kernel {e:.3e}")
+        print(f"attention bwd {backend.name} bf16 dh={qkv.shape[-1] // 3 // heads} heads={heads} T={T}: torch-bf16 {e_torch:.3e}  kernel {e:.3e}")
         assert e <= 1.5 * e_torch, (T, heads, e, e_torch)
+
+
+def _forward_case(backend, dtype, dh, heads, T):
+    g = torch.Generator().manual_seed(100 * T + heads)
+    nseq = 2
+    _check_fwd(backend, dtype, torch.randn(nseq, T, 3 * heads * dh, generator=g), nseq, T, heads)
+
+
+def _backward_case(backend, dtype, dh, heads, T):
+    g = torch.Generator().manual_seed(100 * T + heads + 7)
+    nseq = 2
+    qkv = torch.randn(nseq, T, 3 * heads * dh, generator=g)
+    do = torch.randn(nseq, T, heads * dh, generator=g)
+    _check_bwd(backend, dtype, qkv, do, nseq, T, heads)
 
 
 @pytest.mark.parametrize("T", LENGTHS)
@@ -94,9 +111,7 @@ def _check_bwd(backend, dtype, qkv, do, nseq, T, heads):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_attention96_forward(backend, dtype, heads, T):
     """softmax(q k^T / sqrt(96)) v of nbss_nb_attention_fwd at head width 96 against fp64 torch: the bars the block meets at widths 24 / 48"""
-    g = torch.Generator().manual_seed(100 * T + heads)
-    nseq = 2
-    _check_fwd(backend, dtype, torch.randn(nseq, T, 3 * heads * DH, generator=g), nseq, T, heads)
+    _forward_case(backend, dtype, DH, heads, T)
 
 
 @pytest.mark.parametrize("T", LENGTHS)
@@ -108,11 +123,25 @@ def test_attention96_backward(backend, dtype, heads, T):
     backward (host) shows against it on the same inputs (the margin of tests/test_bf16_vs_reference.py: accumulation order differs, precision class
     does not).  Largest case (T = 256, 2 heads), measured: torch-bf16 error 5.69e-03, kernel error 2.35e-03 on the emulator and 2.35e-03 on the MI355X
     (T = 1 is the exact case: one key, softmax == 1, torch's error is 0 and so must the kernel's be: D = rowsum(P dP) equals dP bit for bit, dS == 0)."""
-    g = torch.Generator().manual_seed(100 * T + heads + 7)
-    nseq = 2
-    qkv = torch.randn(nseq, T, 3 * heads * DH, generator=g)
-    do = torch.randn(nseq, T, heads * DH, generator=g)
-    _check_bwd(backend, dtype, qkv, do, nseq, T, heads)
+    _backward_case(backend, dtype, DH, heads, T)
+
+
+@pytest.mark.parametrize("T", LENGTHS)
+@pytest.mark.parametrize("heads", [1, 2])
+@pytest.mark.parametrize("dh", NARROW)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_narrow_forward(backend, dtype, dh, heads, T):
+    """the same entry point, cases, fp64 reference and bars at head widths 24 / 48: the whole-head kernels of csrc/gb_attn.hip"""
+    _forward_case(backend, dtype, dh, heads, T)
+
+
+@pytest.mark.parametrize("T", LENGTHS)
+@pytest.mark.parametrize("heads", [1, 2])
+@pytest.mark.parametrize("dh", NARROW)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_narrow_backward(backend, dtype, dh, heads, T):
+    """nbss_nb_attention_bwd at head widths 24 / 48 (gb_attn_q_kernel / gb_attn_k_kernel): the references and bars of test_attention96_backward"""
+    _backward_case(backend, dtype, dh, heads, T)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

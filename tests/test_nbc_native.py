@@ -107,10 +107,78 @@ def _relpos_reference(qkv, pos, u, v, scale, keep, keep_scale, heads):
 def test_relpos_attention_backward(backend, dtype, case):
     """nbss_nb_attention_relpos_train / _bwd (three kernels: per query tile, per key tile, per offset block) against torch.autograd through the reference
     formula in fp64 with the SAME dropout keep-bits: output, dqkv, the position table's gradient (summed over the sequences) and the two bias gradients"""
-    lib, dev = backend.lib, backend.device
     nseq, T, heads, dh, drop = case
     if backend.name == "hip":
         nseq, T = (6, 251) if dh == 24 else (3, 100)  # (head width 48 in fp32: the key-tile kernel holds three [T][48] images beside P in LDS)
+    _check_relpos_backward(backend, dtype, nseq, T, heads, dh, drop)
+
+
+# Lengths at which the whole-head kernels change what they do: one tile with a single valid row (1), a full tile whose pair partner is missing (16), the
+# pair partner with one valid row (17), no zero row staged behind the image (64), a third tile pair with one valid row (65).  At T = 1 and 17 P rows outside
+# the staged table are addressed (and must meet masked keys only).  Both head widths: 24 has the guarded second channel tile, 48 the half-empty second K step.
+EDGE_LENGTHS = [1, 16, 17, 64, 65]
+EDGE_CASES = [pytest.param((2, T, heads, dh, drop), id=f"T{T}-h{heads}x{dh}-{'drop' if drop else 'nodrop'}")
+              for T in EDGE_LENGTHS for heads, dh in ((2, 24), (1, 48)) for drop in (False, True)]
+# one full-length sequence at width 48 (bf16: three fp32 [256][48] images beside P do not fit a CU's LDS)
+LONG48 = pytest.param((2, 251, 1, 48, True), id="T251-h1x48-drop")
+
+
+def _check_relpos_forward(backend, dtype, nseq, T, heads, dh, drop):
+    """nbss_nb_attention_relpos_fwd (no keep-bits) / nbss_nb_attention_relpos_train (keep-bits) against the reference formula in fp64"""
+    lib, dev = backend.lib, backend.device
+    td = torch.bfloat16 if dtype == NBSS_BF16 else torch.float32
+    tol = 2e-5 if dtype == NBSS_F32 else 1.5e-2
+    g = torch.Generator().manual_seed(1000 * T + dh)
+    H = heads * dh
+    qkv = torch.randn(nseq, T, 3 * H, generator=g).to(td)
+    pos = torch.randn(2 * T - 1, H, generator=g).to(td)
+    u, v = torch.randn(heads, dh, generator=g) * 0.5, torch.randn(heads, dh, generator=g) * 0.5
+    scale = 1.0 / math.sqrt(H)
+    keep = (torch.rand(nseq, heads, T, T, generator=g) > 0.25) if drop else None
+    ks = 1.0 / 0.75
+    want = _relpos_reference(qkv.double(), pos.double(), u.double(), v.double(), scale, keep, ks, heads)
+    qd, pd, ud, vd = qkv.to(dev), pos.to(dev), u.to(dev).contiguous(), v.to(dev).contiguous()
+    o = torch.full((nseq, T, H), float("nan"), dtype=td, device=dev)
+    P = lambda t: ops._ptr(lib, t)  # noqa: E731
+    if drop:
+        bits = _pack_keep_bits(keep).to(dev)
+        lib.call("nbss_nb_attention_relpos_train", dtype, nseq, T, H, heads, P(qd), P(pd), P(ud), P(vd), scale, P(bits), ks, P(o), ops._stream(lib, qd))
+    else:
+        lib.call("nbss_nb_attention_relpos_fwd", dtype, nseq, T, H, heads, P(qd), P(pd), P(ud), P(vd), scale, P(o), ops._stream(lib, qd))
+    e = rel_l2(o, want)
+    print(f"relpos fwd {backend.name} dtype={dtype} T={T} h{heads}x{dh} drop={drop}: rel_l2 {e:.3e}")
+    assert e < tol
+
+
+@pytest.mark.parametrize("dtype", [pytest.param(NBSS_F32, id="f32"), pytest.param(NBSS_BF16, id="bf16")])
+@pytest.mark.parametrize("case", EDGE_CASES)
+def test_relpos_attention_forward_edge_lengths(backend, dtype, case):
+    """the forward entry points at the lengths of EDGE_LENGTHS, with and without keep-bits: the bars of test_relpos_attention_and_group_norm_blocks"""
+    _check_relpos_forward(backend, dtype, *case)
+
+
+@pytest.mark.parametrize("dtype", [pytest.param(NBSS_F32, id="f32"), pytest.param(NBSS_BF16, id="bf16")])
+@pytest.mark.parametrize("case", EDGE_CASES)
+def test_relpos_attention_backward_edge_lengths(backend, dtype, case):
+    """forward + the three backward kernels at the lengths of EDGE_LENGTHS, with and without keep-bits: the bars of test_relpos_attention_backward"""
+    _check_relpos_backward(backend, dtype, *case)
+
+
+@pytest.mark.parametrize("case", [LONG48])
+def test_relpos_attention_forward_full_length_width_48(backend, case):
+    _check_relpos_forward(backend, NBSS_BF16, *case)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [LONG48])
+def test_relpos_attention_backward_full_length_width_48(hip_lib, case):
+    """(device only: the emulator takes minutes for the three backward kernels at this length)"""
+    from conftest import Backend
+    _check_relpos_backward(Backend("hip", hip_lib, torch.device("cuda:0")), NBSS_BF16, *case)
+
+
+def _check_relpos_backward(backend, dtype, nseq, T, heads, dh, drop):
+    lib, dev = backend.lib, backend.device
     td = torch.bfloat16 if dtype == NBSS_BF16 else torch.float32
     tol = 5e-5 if dtype == NBSS_F32 else 3e-2
     g = torch.Generator().manual_seed(1)
@@ -131,7 +199,9 @@ def test_relpos_attention_backward(backend, dtype, case):
     st = ops._stream(lib, qd)
     P = lambda t: ops._ptr(lib, t)  # noqa: E731
     lib.call("nbss_nb_attention_relpos_train", dtype, nseq, T, H, heads, P(qd), P(pd), P(ud), P(vd), scale, P(bits), ks, P(o), st)
-    assert rel_l2(o, want_o.detach()) < tol
+    e = rel_l2(o, want_o.detach())
+    print(f"relpos train {backend.name} dtype={dtype} T={T} h{heads}x{dh} drop={drop}: o {e:.3e}")
+    assert e < tol
     ws = torch.empty(lib._dll.nbss_nb_attention_relpos_bwd_ws_bytes(nseq, T, H, heads), dtype=torch.uint8, device=dev)
     dqkv = torch.empty_like(qd)
     dpos = torch.zeros(2 * T - 1, H, dtype=torch.float32, device=dev)
@@ -139,7 +209,9 @@ def test_relpos_attention_backward(backend, dtype, case):
     lib.call("nbss_nb_attention_relpos_bwd", dtype, nseq, T, H, heads, P(qd), P(pd), P(ud), P(vd), scale, P(bits), ks, P(dod), P(dqkv), P(dpos), P(du), P(dv), P(ws), st)
     for name, got, want in (("dq", dqkv[..., :H], q64.grad[..., :H]), ("dk", dqkv[..., H:2 * H], q64.grad[..., H:2 * H]), ("dv", dqkv[..., 2 * H:], q64.grad[..., 2 * H:]),
                             ("dpos", dpos, p64.grad), ("du", du.view(heads, dh), u64.grad), ("dvb", dv.view(heads, dh), v64.grad)):
-        assert rel_l2(got, want) < tol, (name, rel_l2(got, want))
+        e = rel_l2(got, want)
+        print(f"relpos bwd {backend.name} dtype={dtype} T={T} h{heads}x{dh} drop={drop}: {name} {e:.3e}")
+        assert e < tol, (name, e)
 
 
 @pytest.mark.parametrize("dtype", [pytest.param(NBSS_F32, id="f32"), pytest.param(NBSS_BF16, id="bf16")])
