@@ -396,6 +396,32 @@ int nbss_online_tconvffn_step(int B, int F, int C, const float* ln_w, const floa
                               const float* c1b, const float* c2w, const float* c2b, const float* gn_w, const float* gn_b, const float* c3w, const float* c3b,
                               const float* w2_t, const float* b2, float* s1, float* s2, float* s3, float* a3, float* gn_sums, float* x, void* stream);
 
+/* ---- OnlineSpatialNet: the causal T-ConvFFN for training (csrc/online_train.hip; nbss_amd/online_train.py) -----------------------------------
+ * The block of nbss_online_tconvffn_step on whole utterances, forward and backward: y = x + T-ConvFFN(x) on x, y [B][F][T][96] of `dtype`
+ * (NBSS_F32: fp32 MFMA; NBSS_BF16: bf16 MFMA, fp32 accumulation); parameters, gradients and every statistic fp32.  The parameters are the
+ * module's own tensors in state_dict layout (NOT transposed): ln_w ln_b [96], w1 [192][96], b1 [192], c1w c2w c3w [192][24][3] with
+ * c1b c2b c3b [192] (causal: output frame t reads input frames t-2 .. t, zero before frame 0), gn_w gn_b [192], w2 [96][192], b2 [96].
+ * Geometry 96 / 192 / 8 groups / k 3.  NBSS_EINVAL: dtype outside {NBSS_F32, NBSS_BF16}, B < 1, F < 1, a NULL pointer (`save` of the forward
+ * excepted), y == x, dx == dy or dx == x.  NBSS_EUNSUPPORTED: T outside 1 .. NBSS_T_MAX (4096), F > NBSS_F_MAX, more than 2^28 tokens.  The two
+ * *_bytes calls return the same codes (negative) instead of a size.  Nothing is launched after a refusal.
+ * save: nbss_online_tconvffn_train_save_bytes() bytes that the forward fills for the backward — the LayerNorm (mean, rstd) per token, the
+ *   GroupNorm (mean, rstd) per (b, t, group) and the stream tensors a1, a2, a3 (pre-activations), h4 = SiLU(GroupNorm(a3)) and a4; the
+ *   backward recomputes LayerNorm(x), the three other SiLUs and the GroupNorm's xhat.  save = NULL: forward only (inference).
+ * ws: nbss_online_tconvffn_train_ws_bytes() bytes of scratch, for either call.
+ * bwd: dx = dy + (block)'(dy) — the residual path included; every d_* buffer is ACCUMULATED into (+=), like nbss_nb_*_bwd.
+ * No atomics: the GroupNorm statistics and the backward's per-frame sums are folded over the frequencies in order, parameter-gradient partials of
+ * fixed token slabs in slab order — two calls give the same bits, and the y / dx rows of a batch item do not depend on the other items. */
+int64_t nbss_online_tconvffn_train_save_bytes(int dtype, int B, int F, int T);
+int64_t nbss_online_tconvffn_train_ws_bytes(int dtype, int B, int F, int T);
+int nbss_online_tconvffn_train_fwd(int dtype, int B, int F, int T, const float* ln_w, const float* ln_b, const float* w1, const float* b1, const float* c1w,
+                                   const float* c1b, const float* c2w, const float* c2b, const float* gn_w, const float* gn_b, const float* c3w, const float* c3b,
+                                   const float* w2, const float* b2, const void* x, void* y, void* save, void* ws, void* stream);
+int nbss_online_tconvffn_train_bwd(int dtype, int B, int F, int T, const float* ln_w, const float* ln_b, const float* w1, const float* b1, const float* c1w,
+                                   const float* c1b, const float* c2w, const float* c2b, const float* gn_w, const float* gn_b, const float* c3w, const float* c3b,
+                                   const float* w2, const float* b2, const void* x, const void* save, const void* dy, void* dx, float* d_ln_w, float* d_ln_b,
+                                   float* d_w1, float* d_b1, float* d_c1w, float* d_c1b, float* d_c2w, float* d_c2b, float* d_gn_w, float* d_gn_b, float* d_c3w,
+                                   float* d_c3b, float* d_w2, float* d_b2, void* ws, void* stream);
+
 /* ---- OnlineSpatialNet: the waveform ends of a streaming step (csrc/online_io.hip; nbss_amd/online_io.py: NativeWaveStreamer) ----------------
  * n_fft in {256, 512}, hop = n_fft/2, win_len = n_fft, `tables` of nbss_stft_tables; 2 <= C <= 32 frames per call (NBSS_EUNSUPPORTED outside).
  * Frame t of the stream is frame t of torch.stft(center=True): samples [(t-1) hop, (t+1) hop).  Neither call knows a first or a last chunk:

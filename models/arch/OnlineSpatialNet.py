@@ -11,6 +11,7 @@ Besides the reference's whole-utterance forward this module offers an explicit s
 chunk shapes a step is a static kernel sequence and can be captured in a HIP graph (`OnlineStreamer`).
 Plain PyTorch (BASELINE config 5)."""
 import math
+import os
 from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
@@ -20,6 +21,7 @@ from torch import Tensor
 from torch.nn import MultiheadAttention
 
 from models.arch.base.linear_group import LinearGroup
+from models.arch.base.native import torch_path_note
 from models.arch.base.norm import new_norm
 from models.arch.base.retention import MultiScaleRetention, RetNetRelPos
 
@@ -94,7 +96,7 @@ class SpatialNetLayer(nn.Module):
         x = x + self._fconv(self.fconv2, x)
         a, attn = self._tsa(x, att_mask, chunkwise_recurrent, rope, state=state, inference=inference)
         x = x + a
-        x = x + self._tconvffn(x, state=state)
+        x = self._tconvffn(x, state=state, residual=True)
         return x, attn
 
     # ---- narrow-band -----------------------------------------------------------------------------------------------------------
@@ -111,7 +113,17 @@ class SpatialNetLayer(nn.Module):
             u = torch.cat([self.mhsa(u[:, i:i + 1], rel_pos=attn_mask[i], incremental_state=st, rope=rope) for i in range(T)], dim=1)
         return self.dropout_mhsa(u.reshape(B, Fq, T, H)), attn
 
-    def _tconvffn(self, x: Tensor, state: Dict[int, Any] = None) -> Tensor:
+    def _tconvffn(self, x: Tensor, state: Dict[int, Any] = None, residual: bool = False) -> Tensor:
+        """the block's output, or x + it with `residual`.  The residual form of a whole-utterance call (state is None) runs through the HIP kernels of
+        nbss_amd/online_train.py, forward and backward, when NBSS_ONLINE_NATIVE_TRAIN=1 (off by default), the tensor is on a HIP device and the block has
+        the geometry they are built for (else, with the switch on, the torch.nn modules below and one warning that names the reason)"""
+        if residual and os.environ.get("NBSS_ONLINE_NATIVE_TRAIN", "0") == "1":
+            from nbss_amd import online_train
+            why = online_train.eligible(self, x, state)
+            if why is None:
+                return online_train.tconvffn_residual(self, x)
+            if why.startswith("!"):
+                torch_path_note(self, "OnlineSpatialNet T-ConvFFN", why[1:])
         B, Fq, T, H0 = x.shape
         h = x.transpose(-1, -2).reshape(B * Fq, H0, T)
         for m in self.tconvffn:
@@ -123,7 +135,8 @@ class SpatialNetLayer(nn.Module):
                 h = h.reshape(B, T, C, Fq).transpose(1, -1).reshape(B * Fq, C, T)
             else:
                 h = m(h)
-        return self.dropout_tconvffn(h.reshape(B, Fq, H0, T).transpose(-1, -2))
+        h = self.dropout_tconvffn(h.reshape(B, Fq, H0, T).transpose(-1, -2))
+        return x + h if residual else h
 
     # ---- cross-band ------------------------------------------------------------------------------------------------------------
     def _fconv(self, ml: nn.ModuleList, x: Tensor) -> Tensor:

@@ -104,6 +104,10 @@ SIGNATURES = {
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),
     "nbss_online_advance": (_I, [_P, _I, _P]),
     "nbss_online_tconvffn_step": (_I, [_I, _I, _I] + [_P] * 21),
+    "nbss_online_tconvffn_train_save_bytes": (C.c_int64, [_I] * 4),
+    "nbss_online_tconvffn_train_ws_bytes": (C.c_int64, [_I] * 4),
+    "nbss_online_tconvffn_train_fwd": (_I, [_I] * 4 + [_P] * 19),
+    "nbss_online_tconvffn_train_bwd": (_I, [_I] * 4 + [_P] * 34),
     "nbss_online_stft_step": (_I, [_I] * 6 + [_P] * 7),
     "nbss_online_istft_step": (_I, [_I] * 5 + [_P] * 6),
     "nbss_nb_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),

@@ -542,3 +542,52 @@ def graph_guard_check(ctx, what: str):
         if p._version != v:
             raise RuntimeError(f"{what}: a parameter needed for the gradient computation was modified in place between forward and backward "
                                f"(shape {tuple(p.shape)}, version {p._version}, expected {v})")
+
+
+# ---- OnlineSpatialNet: the causal T-ConvFFN for training (csrc/online_train.hip) ----------------------------------------------------------------
+def _online_train_dims(x: Tensor):
+    if x.dim() != 4 or x.shape[-1] != 96 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise NbssError(f"online T-ConvFFN: x must be [B,F,T,96] in fp32 or bf16, got {tuple(x.shape)} {x.dtype}")
+    return (NBSS_BF16 if x.dtype == torch.bfloat16 else NBSS_F32, *x.shape[:3])
+
+
+def _online_train_bytes(lib: Lib, name: str, dtype: int, B: int, F: int, T: int) -> int:
+    n = getattr(lib, name)(dtype, B, F, T)
+    if n < 0:
+        raise NbssError(f"{name} failed: {_ERR.get(n, n)}")
+    return n
+
+
+def online_tconvffn_train_save_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
+    return _online_train_bytes(lib, "nbss_online_tconvffn_train_save_bytes", dtype, B, F, T)
+
+
+def online_tconvffn_train_ws_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
+    return _online_train_bytes(lib, "nbss_online_tconvffn_train_ws_bytes", dtype, B, F, T)
+
+
+def online_tconvffn_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True):
+    """y = x + T-ConvFFN(x) on x [B,F,T,96] (fp32 or bf16); params: the 14 fp32 tensors in the order of include/nbss_hip.h (state_dict layout).
+    -> (y, save): `save` is what online_tconvffn_train_bwd needs (None with keep=False: inference)"""
+    dt, B, F, T = _online_train_dims(x)
+    y = torch.empty_like(x)
+    save = scratch(online_tconvffn_train_save_bytes(lib, dt, B, F, T), x.device) if keep else None
+    ws = scratch(online_tconvffn_train_ws_bytes(lib, dt, B, F, T), x.device)
+    lib.call("nbss_online_tconvffn_train_fwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save),
+             _ptr(lib, ws), _stream(lib, x))
+    return y, save
+
+
+def online_tconvffn_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None):
+    """-> (dx, grads): dx includes the residual path; the 14 fp32 parameter gradients are ACCUMULATED into `grads` (zeros of the parameters' shapes when
+    not given)"""
+    dt, B, F, T = _online_train_dims(x)
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise NbssError(f"online T-ConvFFN: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    if grads is None:
+        grads = [torch.zeros_like(p) for p in params]
+    dx = torch.empty_like(x)
+    ws = scratch(online_tconvffn_train_ws_bytes(lib, dt, B, F, T), x.device)
+    lib.call("nbss_online_tconvffn_train_bwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
+             _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, x))
+    return dx, grads

@@ -1,0 +1,101 @@
+"""One OnlineSpatialNet training step (forward + backward + AdamW) of the shipped 8-layer configs/onlineSpatialNet.yaml model with the native T-ConvFFN
+switched off and on (NBSS_ONLINE_NATIVE_TRAIN) in the same process, and the T-ConvFFN block alone, forward and backward, against the module's `_tconvffn`.
+
+    python tools/online_train_bench.py [--batches 2 4] [--seconds 4] [--steps 10] [--warmup 3] [--layers 8]
+
+HIP events around `steps` iterations after `warmup` discarded ones; the two variants alternate in blocks so that clock drift hits both; peak memory is
+torch's allocator peak over the timed iterations.  Prints one JSON line per setting."""
+import argparse
+import json
+import os
+import sys
+from pathlib import Path
+
+import torch
+import yaml
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def _timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps, torch.cuda.max_memory_allocated() / 2 ** 20
+
+
+def _switch(on):
+    os.environ["NBSS_ONLINE_NATIVE_TRAIN"] = "1" if on else "0"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[2, 4])
+    ap.add_argument("--seconds", type=float, default=4.0)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--layers", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=2, help="off / on blocks per setting (the minimum of the rounds is reported)")
+    a = ap.parse_args()
+    from models.arch.OnlineSpatialNet import OnlineSpatialNet
+    arch = yaml.safe_load((ROOT / "configs" / "onlineSpatialNet.yaml").read_text())["model"]["arch"]["init_args"]
+    arch.update(num_layers=a.layers, dim_input=12, dim_output=4, num_freqs=129)
+    dev = torch.device("cuda", 0)
+    T = int(a.seconds * 8000) // 128 + 1
+    torch.manual_seed(2)
+    net = OnlineSpatialNet(**arch).to(dev).train()
+    opt = torch.optim.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-3)
+    for B in a.batches:
+        x, r = torch.randn(B, 129, T, 12, device=dev), torch.randn(B, 129, T, 4, device=dev)
+        for prec in ("32", "bf16-mixed"):
+            def step():
+                opt.zero_grad(set_to_none=True)
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    y = net(x)
+                ((y.float() - r) ** 2).mean().backward()
+                opt.step()
+            res = {}
+            for _ in range(a.rounds):
+                for on in (False, True):
+                    _switch(on)
+                    ms, mb = _timed(step, a.steps, a.warmup)
+                    k = "on" if on else "off"
+                    res[k] = (min(ms, res[k][0]), max(mb, res[k][1])) if k in res else (ms, mb)
+            print(json.dumps({"what": "train step", "layers": a.layers, "B": B, "T": T, "precision": prec, "off_ms": round(res["off"][0], 2),
+                              "on_ms": round(res["on"][0], 2), "off_over_on": round(res["off"][0] / res["on"][0], 3), "off_peak_MiB": round(res["off"][1]),
+                              "on_peak_MiB": round(res["on"][1])}), flush=True)
+        # the block alone: x + _tconvffn(x), forward and forward + backward
+        layer = net.layers[0]
+        for prec in ("32", "bf16-mixed"):
+            h = torch.randn(B, 129, T, 96, device=dev, requires_grad=True)
+            g = torch.randn(B, 129, T, 96, device=dev)
+
+            def fwd():
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    layer._tconvffn(h, residual=True)
+
+            def fwd_bwd():
+                net.zero_grad(set_to_none=True)
+                h.grad = None
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    y = layer._tconvffn(h, residual=True)
+                y.backward(g)
+            out = {"what": "T-ConvFFN block", "B": B, "T": T, "precision": prec}
+            for name, fn in (("fwd", fwd), ("fwd_bwd", fwd_bwd)):
+                for on in (False, True):
+                    _switch(on)
+                    out[f"{name}_{'on' if on else 'off'}_ms"] = round(_timed(fn, a.steps, a.warmup)[0], 3)
+                out[f"{name}_off_over_on"] = round(out[f"{name}_off_ms"] / out[f"{name}_on_ms"], 3)
+            print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
