@@ -422,6 +422,31 @@ int nbss_online_tconvffn_train_bwd(int dtype, int B, int F, int T, const float* 
                                    float* d_w1, float* d_b1, float* d_c1w, float* d_c1b, float* d_c2w, float* d_c2b, float* d_gn_w, float* d_gn_b, float* d_c3w,
                                    float* d_c3b, float* d_w2, float* d_b2, void* ws, void* stream);
 
+/* ---- OnlineSpatialNet: the chunkwise retention core for training (csrc/online_ret_train.hip; nbss_amd/online_train.py) -------------------------
+ * What models/arch/base/retention.py computes between the q / k / v / g projections and out_proj for chunkwise_recurrent = True, rope = False,
+ * look_ahead = 0 and chunks of 64 frames — MultiScaleRetention.chunk_recurrent_forward, the per-head RMSNorm (eps 1e-6, no affine) and the SiLU gate —
+ * on BF sequences of T frames, forward and backward; 4 heads, key width 24, value width 48.  q, k, dq, dk [BF][T][96]; v, g, out, d_out, dv, dg
+ * [BF][T][192]; all contiguous and of `dtype` (NBSS_F32: fp32 MFMA; NBSS_BF16: bf16 MFMA operands, fp32 accumulation).  decay [4]: the per-head gamma
+ * (fp32, on the device, as nbss_online_ret_step takes it).  The decay powers, the two row scalings (the decay row sums and the clamped absolute score
+ * sums, which the gradient treats as constants like the module does), the RMS statistics and the [24][48] state are fp32 in either dtype.
+ * k: the keys, used as k_scale * k ('ret(2,not_share_qk)': k_scale = 24^-0.5); k = NULL shares them with q ('share_qk'; k_scale is ignored).
+ * bwd: dq, dk, dv, dg are WRITTEN (not accumulated); dk includes the k_scale factor; with k = NULL dk must be NULL and dq is the sum of both roles of q.
+ * NBSS_EINVAL: dtype outside {NBSS_F32, NBSS_BF16}, BF < 1, a NULL pointer other than k, dk or the forward's `save`, dk without k or k without dk,
+ * `out` equal to q, k, v or g.  NBSS_EUNSUPPORTED: T outside 1 .. NBSS_T_MAX (4096), more than 2^28 tokens.  The two *_bytes calls return the same
+ * codes (negative) instead of a size.  Nothing is launched after a refusal.
+ * save: nbss_online_ret_train_save_bytes() bytes that the forward fills for the backward — the fp32 state at the START of every chunk,
+ *   [BF][4][ceil(T / 64)][24][48]; the backward walks the chunks in reverse, carries the state's gradient, and recomputes each chunk's scores, row
+ *   scalings, output and RMS statistics from q, k, v and that state.  save = NULL: forward only (inference), nothing is kept.
+ * ws: nbss_online_ret_train_ws_bytes() bytes, for either call: reserved (one 256-byte piece; the kernels keep a chunk's intermediates in LDS).
+ * One workgroup per (sequence, head) walks the chunks; more than 4096 pairs are covered by a grid-stride loop.  No atomics, every sum in a fixed order:
+ * two calls give the same bits, and a sequence's rows do not depend on the other sequences of the launch. */
+int64_t nbss_online_ret_train_save_bytes(int dtype, int64_t BF, int T);
+int64_t nbss_online_ret_train_ws_bytes(int dtype, int64_t BF, int T);
+int nbss_online_ret_train_fwd(int dtype, int64_t BF, int T, const void* q, const void* k, const void* v, const void* g, float k_scale,
+                              const float* decay, void* out, void* save, void* ws, void* stream);
+int nbss_online_ret_train_bwd(int dtype, int64_t BF, int T, const void* q, const void* k, const void* v, const void* g, float k_scale,
+                              const float* decay, const void* save, const void* d_out, void* dq, void* dk, void* dv, void* dg, void* ws, void* stream);
+
 /* ---- OnlineSpatialNet: the waveform ends of a streaming step (csrc/online_io.hip; nbss_amd/online_io.py: NativeWaveStreamer) ----------------
  * n_fft in {256, 512}, hop = n_fft/2, win_len = n_fft, `tables` of nbss_stft_tables; 2 <= C <= 32 frames per call (NBSS_EUNSUPPORTED outside).
  * Frame t of the stream is frame t of torch.stft(center=True): samples [(t-1) hop, (t+1) hop).  Neither call knows a first or a last chunk:

@@ -107,7 +107,18 @@ class SpatialNetLayer(nn.Module):
         if isinstance(self.mhsa, MultiheadAttention):
             u, attn = self.mhsa(u, u, u, need_weights=bool(getattr(self, "need_weights", False)), average_attn_weights=False, attn_mask=attn_mask)
         elif not inference:
-            u = self.mhsa(u, rel_pos=attn_mask, incremental_state=state, chunkwise_recurrent=chunkwise_recurrent, rope=rope)
+            # the chunkwise retention core runs through the HIP kernels of nbss_amd/online_train.py, forward and backward, when NBSS_ONLINE_NATIVE_RET=1 (off
+            # by default) and `ret_eligible` accepts the call (else, with the switch on, the module below and one warning that names the reason)
+            why = "off"
+            if os.environ.get("NBSS_ONLINE_NATIVE_RET", "0") == "1":
+                from nbss_amd import online_train
+                why = online_train.ret_eligible(self, u, attn_mask, chunkwise_recurrent, rope, state, inference)
+                if why is not None and why.startswith("!"):
+                    torch_path_note(self, "OnlineSpatialNet retention", why[1:])
+            if why is None:
+                u = online_train.retention_forward(self.mhsa, u, attn_mask)
+            else:
+                u = self.mhsa(u, rel_pos=attn_mask, incremental_state=state, chunkwise_recurrent=chunkwise_recurrent, rope=rope)
         else:  # frame-by-frame recurrence (what a streaming deployment computes)
             st: Dict[str, Any] = {}
             u = torch.cat([self.mhsa(u[:, i:i + 1], rel_pos=attn_mask[i], incremental_state=st, rope=rope) for i in range(T)], dim=1)

@@ -4,7 +4,11 @@ SiLU -> causal grouped conv -> SiLU -> causal grouped conv -> GroupNorm of each 
 
 `models.arch.OnlineSpatialNet.SpatialNetLayer._tconvffn` takes it when NBSS_ONLINE_NATIVE_TRAIN=1 (off by default), the tensor is on a HIP device, the call
 is not a streaming one, `supported(layer)` is None and the stream is fp32 (or autocast to bf16); attention and the cross-band blocks keep their torch.nn
-modules in training."""
+modules in training.
+
+The chunkwise retention core (csrc/online_ret_train.hip: nbss_online_ret_train_fwd / _bwd) has a switch of its own, NBSS_ONLINE_NATIVE_RET=1 (off by default,
+independent of the one above): `SpatialNetLayer._tsa` then runs the module's four projections and out_proj as its own nn.Linear's around
+`OnlineRetentionFn`, which replaces MultiScaleRetention.chunk_recurrent_forward, the per-head RMSNorm and the SiLU gate (`ret_eligible` says when)."""
 from __future__ import annotations
 
 import contextlib
@@ -155,3 +159,99 @@ def tconvffn_residual(layer, x: Tensor) -> Tensor:
     else:
         y = ops.online_tconvffn_train_fwd(lib, _kernel_params(params), xs.contiguous(), keep=False)[0]
     return y.to(x.dtype)
+
+
+# ---- the retention core (NBSS_ONLINE_NATIVE_RET) ---------------------------------------------------------------------------------------------------------
+RET_CHUNK, RET_T_MAX = 64, 4096
+
+
+def ret_enabled() -> bool:
+    """the retention switch, read at call time; off unless it is exactly '1'"""
+    return os.environ.get("NBSS_ONLINE_NATIVE_RET", "0") == "1"
+
+
+def ret_supported(mhsa) -> Optional[str]:
+    """None when the module is the retention the kernels are built for, else the reason"""
+    if type(mhsa).__name__ != "MultiScaleRetention":
+        return f"the attention must be retention (got {type(mhsa).__name__})"
+    if mhsa.embed_dim != 96 or mhsa.value_dim != 192:
+        return f"embed_dim must be 96 and value_dim 192 (got {mhsa.embed_dim}, {mhsa.value_dim})"
+    if mhsa.num_heads != 4:
+        return f"num_heads must be 4 (got {mhsa.num_heads})"
+    if mhsa.look_ahead != 0:
+        return f"look_ahead must be 0 (got {mhsa.look_ahead})"
+    if mhsa.gate_fn is not torch.nn.functional.silu:
+        return "the gate must be swish"
+    if mhsa.group_norm.weight is not None or mhsa.group_norm.eps != 1e-6:
+        return "the head norm must be RMSNorm(eps=1e-6) without affine"
+    return None
+
+
+def ret_eligible(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope, state, inference: bool) -> Optional[str]:
+    """None when this call of `_tsa` takes the native retention core; else why not, with the conventions of `eligible` (a leading '!': worth a warning)"""
+    if not ret_enabled():
+        return "NBSS_ONLINE_NATIVE_RET is not 1"
+    if state is not None or inference:
+        return "streaming or recurrent call"
+    if _LIB_OVERRIDE is None and not u.is_cuda:
+        return "not on a HIP device"
+    if active_lib(u) is None:
+        return "no library for the tensor's device"
+    why = ret_supported(layer.mhsa)
+    if why is not None:
+        return "!" + why
+    inner = rel_pos[1] if isinstance(rel_pos, tuple) and len(rel_pos) == 2 else None
+    if not chunkwise_recurrent or not (isinstance(inner, tuple) and inner[0] == "chunk"):
+        return "!only the chunkwise form runs natively"
+    if inner[1] != RET_CHUNK:
+        return f"!the chunk size must be {RET_CHUNK} (got {inner[1]})"
+    if rope is not False:
+        return f"!rope must be False (got {rope!r})"
+    if u.dim() != 3 or u.shape[-1] != 96:
+        return f"!input must be [B F,T,96], got {tuple(u.shape)}"
+    if u.dtype != torch.float32 and _stream_dtype(u) is None:
+        return f"!the stream must be fp32, or bf16 under autocast (got {u.dtype})"
+    if not 1 <= u.shape[1] <= RET_T_MAX:
+        return f"!1 <= T <= {RET_T_MAX} (got T = {u.shape[1]})"
+    return None
+
+
+class OnlineRetentionFn(torch.autograd.Function):
+    """out = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)) through the HIP kernels; inputs (lib, q, k or None, v, g, k_scale, decay).  One
+    backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
+
+    @staticmethod
+    def forward(ctx, lib, q, k, v, g, k_scale, decay):
+        q, v, g = q.contiguous(), v.contiguous(), g.contiguous()
+        k = None if k is None else k.contiguous()
+        out, save = ops.online_ret_train_fwd(lib, q, k, v, g, k_scale, decay, keep=True)
+        ctx.lib, ctx.k_scale, ctx.saved, ctx.params, ctx.versions = lib, k_scale, (q, k, v, g, decay, save), (), []
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        ops.graph_guard_check(ctx, "OnlineSpatialNet native retention")
+        q, k, v, g, decay, save = ctx.saved
+        dq, dk, dv, dg = ops.online_ret_train_bwd(ctx.lib, q, k, v, g, ctx.k_scale, decay, save, d_out.contiguous())
+        ctx.saved = None
+        return None, dq, dk, dv, dg, None, None
+
+
+def retention_forward(mhsa, u: Tensor, rel_pos) -> Tensor:
+    """MultiScaleRetention.forward(u, rel_pos, chunkwise_recurrent=True, rope=False) for a call `ret_eligible` accepted: the projections and out_proj are the
+    module's own nn.Linear's (torch GEMMs, autocast like any other), the core between them is native.  Without autograd the forward runs alone and keeps nothing."""
+    lib = active_lib(u)
+    if lib is None:
+        raise ops.NbssError("OnlineSpatialNet native retention: no library for a tensor on " + str(u.device))
+    dt = _stream_dtype(u)
+    q = mhsa.q_proj(u).to(dt)
+    k = None if mhsa.share_qk else mhsa.k_proj(u).to(dt)
+    v, g = mhsa.v_proj(u).to(dt), mhsa.g_proj(u).to(dt)
+    decay = rel_pos[1][2].detach().to(device=u.device, dtype=torch.float32).contiguous()
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, g)):
+        out = OnlineRetentionFn.apply(lib, q, k, v, g, float(mhsa.scaling), decay)
+    else:
+        out = ops.online_ret_train_fwd(lib, q.contiguous(), None if k is None else k.contiguous(), v.contiguous(), g.contiguous(), float(mhsa.scaling), decay,
+                                       keep=False)[0]
+    return mhsa.out_proj(out)

@@ -591,3 +591,45 @@ def online_tconvffn_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: T
     lib.call("nbss_online_tconvffn_train_bwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
              _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, x))
     return dx, grads
+
+
+# ---- OnlineSpatialNet: the chunkwise retention core for training (csrc/online_ret_train.hip) ----------------------------------------------------
+def _online_ret_dims(q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor):
+    if q.dim() != 3 or q.shape[-1] != 96 or q.dtype not in (torch.float32, torch.bfloat16):
+        raise NbssError(f"online retention: q must be [BF,T,96] in fp32 or bf16, got {tuple(q.shape)} {q.dtype}")
+    BF, T = q.shape[:2]
+    for name, t, width in (("k", k, 96), ("v", v, 192), ("g", g, 192)):
+        if t is not None and (tuple(t.shape) != (BF, T, width) or t.dtype != q.dtype):
+            raise NbssError(f"online retention: {name} must be [{BF},{T},{width}] {q.dtype}, got {tuple(t.shape)} {t.dtype}")
+    return NBSS_BF16 if q.dtype == torch.bfloat16 else NBSS_F32, BF, T
+
+
+def _online_ret_bytes(lib: Lib, name: str, dtype: int, BF: int, T: int) -> int:
+    n = getattr(lib, name)(dtype, BF, T)
+    if n < 0:
+        raise NbssError(f"{name} failed: {_ERR.get(n, n)}")
+    return n
+
+
+def online_ret_train_fwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, keep: bool = True):
+    """out [BF,T,192] = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)); k = None shares the keys with q; decay [4] fp32: the per-head gamma.
+    -> (out, save): `save` is what online_ret_train_bwd needs (None with keep=False: inference)"""
+    dt, BF, T = _online_ret_dims(q, k, v, g)
+    out = torch.empty_like(v)
+    save = scratch(_online_ret_bytes(lib, "nbss_online_ret_train_save_bytes", dt, BF, T), q.device) if keep else None
+    ws = scratch(_online_ret_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
+    lib.call("nbss_online_ret_train_fwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
+             _ptr(lib, out), _ptr(lib, save), _ptr(lib, ws), _stream(lib, q))
+    return out, save
+
+
+def online_ret_train_bwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, save: Tensor, d_out: Tensor):
+    """-> (dq, dk, dv, dg), written (not accumulated); dk includes k_scale and is None when k is (dq then holds both roles of q)"""
+    dt, BF, T = _online_ret_dims(q, k, v, g)
+    if d_out.shape != v.shape or d_out.dtype != v.dtype:
+        raise NbssError(f"online retention: d_out {tuple(d_out.shape)} {d_out.dtype} does not match v {tuple(v.shape)} {v.dtype}")
+    dq, dk, dv, dg = torch.empty_like(q), None if k is None else torch.empty_like(q), torch.empty_like(v), torch.empty_like(v)
+    ws = scratch(_online_ret_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
+    lib.call("nbss_online_ret_train_bwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
+             _ptr(lib, save), _ptr(lib, d_out), _ptr(lib, dq), _ptr(lib, dk), _ptr(lib, dv), _ptr(lib, dg), _ptr(lib, ws), _stream(lib, q))
+    return dq, dk, dv, dg

@@ -1,9 +1,11 @@
-"""One OnlineSpatialNet training step (forward + backward + AdamW) of the shipped 8-layer configs/onlineSpatialNet.yaml model with the native T-ConvFFN
-switched off and on (NBSS_ONLINE_NATIVE_TRAIN) in the same process, and the T-ConvFFN block alone, forward and backward, against the module's `_tconvffn`.
+"""One OnlineSpatialNet training step (forward + backward + AdamW) of the shipped 8-layer configs/onlineSpatialNet.yaml model in three settings in the same
+process — every switch off, the native T-ConvFFN (NBSS_ONLINE_NATIVE_TRAIN), and the native T-ConvFFN + the native retention core (NBSS_ONLINE_NATIVE_RET) —
+then the T-ConvFFN block alone against the module's `_tconvffn` and the retention block alone (`layer._tsa`: LayerNorm, projections, retention, out_proj)
+against the module's MultiScaleRetention, each forward and forward + backward.
 
     python tools/online_train_bench.py [--batches 2 4] [--seconds 4] [--steps 10] [--warmup 3] [--layers 8]
 
-HIP events around `steps` iterations after `warmup` discarded ones; the two variants alternate in blocks so that clock drift hits both; peak memory is
+HIP events around `steps` iterations after `warmup` discarded ones; the variants alternate in blocks so that clock drift hits both; peak memory is
 torch's allocator peak over the timed iterations.  Prints one JSON line per setting."""
 import argparse
 import json
@@ -32,8 +34,9 @@ def _timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps, torch.cuda.max_memory_allocated() / 2 ** 20
 
 
-def _switch(on):
+def _switch(on, ret=False):
     os.environ["NBSS_ONLINE_NATIVE_TRAIN"] = "1" if on else "0"
+    os.environ["NBSS_ONLINE_NATIVE_RET"] = "1" if ret else "0"
 
 
 def main():
@@ -43,7 +46,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--layers", type=int, default=8)
-    ap.add_argument("--rounds", type=int, default=2, help="off / on blocks per setting (the minimum of the rounds is reported)")
+    ap.add_argument("--rounds", type=int, default=2, help="blocks of the settings per case (the minimum of the rounds is reported)")
     a = ap.parse_args()
     from models.arch.OnlineSpatialNet import OnlineSpatialNet
     arch = yaml.safe_load((ROOT / "configs" / "onlineSpatialNet.yaml").read_text())["model"]["arch"]["init_args"]
@@ -64,14 +67,14 @@ def main():
                 opt.step()
             res = {}
             for _ in range(a.rounds):
-                for on in (False, True):
-                    _switch(on)
+                for k, on, ret in (("off", False, False), ("on", True, False), ("on_ret", True, True)):
+                    _switch(on, ret)
                     ms, mb = _timed(step, a.steps, a.warmup)
-                    k = "on" if on else "off"
                     res[k] = (min(ms, res[k][0]), max(mb, res[k][1])) if k in res else (ms, mb)
-            print(json.dumps({"what": "train step", "layers": a.layers, "B": B, "T": T, "precision": prec, "off_ms": round(res["off"][0], 2),
-                              "on_ms": round(res["on"][0], 2), "off_over_on": round(res["off"][0] / res["on"][0], 3), "off_peak_MiB": round(res["off"][1]),
-                              "on_peak_MiB": round(res["on"][1])}), flush=True)
+            print(json.dumps({"what": "train step", "layers": a.layers, "B": B, "T": T, "precision": prec, "rounds": a.rounds, "off_ms": round(res["off"][0], 2),
+                              "on_ms": round(res["on"][0], 2), "on_ret_ms": round(res["on_ret"][0], 2), "off_over_on": round(res["off"][0] / res["on"][0], 3),
+                              "on_over_on_ret": round(res["on"][0] / res["on_ret"][0], 3), "off_peak_MiB": round(res["off"][1]),
+                              "on_peak_MiB": round(res["on"][1]), "on_ret_peak_MiB": round(res["on_ret"][1])}), flush=True)
         # the block alone: x + _tconvffn(x), forward and forward + backward
         layer = net.layers[0]
         for prec in ("32", "bf16-mixed"):
@@ -93,6 +96,29 @@ def main():
                 for on in (False, True):
                     _switch(on)
                     out[f"{name}_{'on' if on else 'off'}_ms"] = round(_timed(fn, a.steps, a.warmup)[0], 3)
+                out[f"{name}_off_over_on"] = round(out[f"{name}_off_ms"] / out[f"{name}_on_ms"], 3)
+            print(json.dumps(out), flush=True)
+        # the retention block alone: layer._tsa (LayerNorm, the projections, retention, out_proj), forward and forward + backward
+        pos = net.get_causal_mask(slen=T, device=dev, chunkwise_recurrent=True, batch_size=B * 129)
+        for prec in ("32", "bf16-mixed"):
+            h = torch.randn(B, 129, T, 96, device=dev, requires_grad=True)
+            g = torch.randn(B, 129, T, 96, device=dev)
+
+            def fwd():
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    layer._tsa(h, pos, True, net.rope)
+
+            def fwd_bwd():
+                net.zero_grad(set_to_none=True)
+                h.grad = None
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    y = layer._tsa(h, pos, True, net.rope)[0]
+                y.backward(g.to(y.dtype))
+            out = {"what": "retention block", "B": B, "T": T, "precision": prec}
+            for name, fn in (("fwd", fwd), ("fwd_bwd", fwd_bwd)):
+                for ret in (False, True):
+                    _switch(False, ret)
+                    out[f"{name}_{'on' if ret else 'off'}_ms"] = round(_timed(fn, a.steps, a.warmup)[0], 3)
                 out[f"{name}_off_over_on"] = round(out[f"{name}_off_ms"] / out[f"{name}_on_ms"], 3)
             print(json.dumps(out), flush=True)
 
