@@ -38,30 +38,7 @@ NBSS_DEV void vec_copy(float* d, const float* s) { *reinterpret_cast<f32x4*>(d) 
 NBSS_DEV void vec_zero(bf16_t* d) { *reinterpret_cast<u32x4*>(d) = (u32x4){0, 0, 0, 0}; }
 NBSS_DEV void vec_zero(float* d) { *reinterpret_cast<f32x4*>(d) = (f32x4){0, 0, 0, 0}; }
 
-// LayerNorm over H=96 of one LDS-resident row, in place (fp32 statistics, eps 1e-5).
-template <class T, int HL>
-NBSS_DEV void ln_row_inplace(T* row, const float* __restrict__ gamma, const float* __restrict__ beta) {
-    float s = 0.f;
-    float v[HL];
-#pragma unroll
-    for (int i = 0; i < HL; i += 8) load8(row + i, v + i);
-#pragma unroll
-    for (int i = 0; i < HL; ++i) s += v[i];
-    const float mean = s * (1.0f / HL);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < HL; ++i) {
-        const float d = v[i] - mean;
-        q += d * d;
-    }
-    const float rstd = rsqrtf(q * (1.0f / HL) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < HL; i += 4)
-        store4(row + i, (v[i] - mean) * rstd * gamma[i] + beta[i], (v[i + 1] - mean) * rstd * gamma[i + 1] + beta[i + 1],
-               (v[i + 2] - mean) * rstd * gamma[i + 2] + beta[i + 2], (v[i + 3] - mean) * rstd * gamma[i + 3] + beta[i + 3]);
-}
-
-// The same LayerNorm with TWO adjacent lanes per row (each HL / 2 channels; the partial sums are exchanged with a DPP quad swap): all 512
+// LayerNorm over HL channels of one LDS-resident row, in place (fp32 statistics, eps 1e-5), with TWO adjacent lanes per row (each HL / 2 channels; the partial sums are exchanged with a DPP quad swap): all 512
 // threads of a two-frame slab are busy (258 rows) and a lane's serial chain is half as long.  `row` points at the lane's own half.
 template <class T, int HL>
 NBSS_DEV void ln_halfrow_inplace(T* row, const float* __restrict__ gamma, const float* __restrict__ beta, bool active) {
@@ -379,21 +356,12 @@ void fconv_bwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __
         }
     };
     auto row_stats = [&](const Frag<T> (&xq)[BK_KS], float& mean, float& rstd) {
-        float sum = 0.f;
+        float v[BK_KS][8];
 #pragma unroll
         for (int ks = 0; ks < BK_KS; ++ks)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) sum += frag_get(xq[ks], j);
-        mean = wave_sum16(sum) * (1.0f / FC_H);
-        float q = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < BK_KS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d = frag_get(xq[ks], j) - mean;
-                q += d * d;
-            }
-        rstd = rsqrtf(wave_sum16(q) * (1.0f / FC_H) + 1e-5f);
+            for (int j = 0; j < 8; ++j) v[ks][j] = frag_get(xq[ks], j);
+        ln_stats(v, mean, rstd);
     };
     auto row_fwd = [&](int ti, const Frag<T> (&xq)[BK_KS], const Frag<T> (&dq)[BK_KS], float mean, float rstd) {
         const int ft = ti / TT, tt = ti % TT, f = ft * 16 + l15, t = t0 + tt;

@@ -109,24 +109,10 @@ __global__ __launch_bounds__(FG_THREADS, 1) void fconv_bwd_g_kernel(FconvG p) {
         const int f = ft * 16 + l15;
         const bool valid = f < F;
         T* ur = U + (size_t)(f + 2) * LD + 8 * g4;
-        float xv[KSR][8];
-        float sum = 0.f;
+        float xv[KSR][8], mean, rstd;
 #pragma unroll
-        for (int ks = 0; ks < KSR; ++ks) {
-            load8(ur + ks * 32, xv[ks]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum += xv[ks][j];
-        }
-        const float mean = wave_sum16(sum) * (1.0f / HH);
-        float q = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KSR; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d = xv[ks][j] - mean;
-                q += d * d;
-            }
-        const float rstd = rsqrtf(wave_sum16(q) * (1.0f / HH) + 1e-5f);
+        for (int ks = 0; ks < KSR; ++ks) load8(ur + ks * 32, xv[ks]);
+        ln_stats(xv, mean, rstd);
         if (g4 == 0) {
             rst[2 * f] = mean;
             rst[2 * f + 1] = rstd;

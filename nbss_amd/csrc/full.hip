@@ -94,13 +94,7 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
 #pragma unroll
         for (int ks = 0; ks < (HH / 32); ++ks) wfrag_load(a[ks], Wsq, 0, (HH / 32), ks);
         float gam[(HH / 32)][8], bet[(HH / 32)][8];
-#pragma unroll
-        for (int ks = 0; ks < (HH / 32); ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                gam[ks][j] = lnw[ks * 32 + 8 * g4 + j];
-                bet[ks][j] = lnb[ks * 32 + 8 * g4 + j];
-            }
+        load_ln_affine(lnw, lnb, gam, bet);
         // software pipeline (the same as full_bwd's row loops): the x pieces of the wave's NEXT tile are requested before this tile's math —
         // one workgroup of 8 waves per CU, and each wave walks 8 tiles load -> LayerNorm -> MFMA (SQ_WAIT_ANY was 77 % of the wave cycles)
         const int tclf = t0 + (l15 % TT) < T_ ? t0 + (l15 % TT) : T_ - 1;
@@ -124,26 +118,12 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
 #pragma unroll
                 for (int ks = 0; ks < (HH / 32); ++ks) frag_load(xnext[ks], nx + ks * 32 + 8 * g4);
             }
-            float v[(HH / 32)][8];
-            float sum = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < (HH / 32); ++ks) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    v[ks][j] = keep_if(valid, frag_get(xcur[ks], j));
-                    sum += v[ks][j];
-                }
-            }
-            const float mean = wave_sum16(sum) * (1.0f / HH);
-            float q = 0.f;
+            float v[(HH / 32)][8], mean, rstd;
 #pragma unroll
             for (int ks = 0; ks < (HH / 32); ++ks)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float d = v[ks][j] - mean;
-                    q += d * d;
-                }
-            const float rstd = rsqrtf(wave_sum16(q) * (1.0f / HH) + 1e-5f);
+                for (int j = 0; j < 8; ++j) v[ks][j] = keep_if(valid, frag_get(xcur[ks], j));
+            ln_stats(v, mean, rstd);
             f32x4 acc = F32X4_ZERO;
 #pragma unroll
             for (int ks = 0; ks < (HH / 32); ++ks) {
@@ -310,7 +290,7 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
             const int f = (16 / TT) * nt + (l15 / TT), tt = l15 % TT;
             const bool valid = f < F && t0 + tt < T_;
             Frag<T> u[BK_KS];
-            ln_strip96<T>(x + (((size_t)b * F + f) * T_ + t0 + tt) * FL_H, valid, gam, bet, u);
+            ln_strip(x + (((size_t)b * F + f) * T_ + t0 + tt) * FL_H, valid, gam, bet, u);
             f32x4 acc = F32X4_ZERO;
 #pragma unroll
             for (int ks = 0; ks < FL_KS; ++ks) acc = mma(a[ks], u[ks], acc);
@@ -495,7 +475,7 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
                 frag_load(am, wa + mt * 512);
                 du[mt] = mma(am, bq, F32X4_ZERO);
             }
-            ln_bwd_row96_raw_nas<T>(du, xcur, dcur, dx + n * FL_H, stats + n * 2, valid, lnw);
+            ln_bwd_row_raw<true>(du, xcur, dcur, dx + n * FL_H, stats + n * 2, valid, lnw);
         }
     }
     PHASE(9);

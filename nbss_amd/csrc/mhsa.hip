@@ -15,6 +15,7 @@
 //   * two stacked C tiles are re-used as the next B operand in the permuted K order
 //     (common.h), which is how Q^T feeds S^T and O^T feeds the output projection.
 // T = 251 is padded to 16 tiles of 16 keys; padded keys are masked to -inf.
+#include "blocks.h"
 #include "launch.h"
 #include "layout.h"
 #include "prof.h"
@@ -27,48 +28,12 @@
 #define MH_TP 256
 #define MH_NT 16       // key/query tiles of 16 frames
 // strips per wave: template parameter NSW (2 = 8 waves x 2 strips; 1 = 16 waves x 1 strip)
-#define MH_KS (MH_H / 32)
 #ifndef MH_BF16_NSW
 #define MH_BF16_NSW 2
 #endif
 #ifndef MH_BF16_HPP
 #define MH_BF16_HPP 4  // heads per pass of the bf16 kernel (A/B: 2 = two passes of a head pair, K / V images of 49 KB)
 #endif
-
-// LN of a 16-frame strip held as natural-order B fragments (lane: frame l&15, channels 32ks+8g+j)
-template <class T>
-NBSS_DEV void ln_strip(const T* __restrict__ xr, bool valid, const float (&gam)[MH_KS][8], const float (&bet)[MH_KS][8], Frag<T> (&u)[MH_KS], float* __restrict__ stat = nullptr) {
-    const int g4 = lane_id() >> 4;
-    float v[MH_KS][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < MH_KS; ++ks) {
-        if (valid) load8(xr + ks * 32 + 8 * g4, v[ks]);
-        else
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[ks][j] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum += v[ks][j];
-    }
-    const float mean = wave_sum16(sum) * (1.0f / MH_H);
-    float q = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < MH_KS; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float d = v[ks][j] - mean;
-            q += d * d;
-        }
-    const float rstd = rsqrtf(wave_sum16(q) * (1.0f / MH_H) + 1e-5f);
-    if (stat && valid && g4 == 0) {  // training-mode forward: the row statistics go to the save buffer (layout.h: mhsa_stat_offset)
-        stat[0] = mean;
-        stat[1] = rstd;
-    }
-#pragma unroll
-    for (int ks = 0; ks < MH_KS; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) frag_set(u[ks], j, (v[ks][j] - mean) * rstd * gam[ks][j] + bet[ks][j]);
-}
 
 // A operand of O^T = V^T P^T from the row-major bf16 V image [TP][24]: rows d = half*16 + l15, K = the 32 frames of k-step ks
 NBSS_DEV void v_frag_tr(Frag<bf16_t>& f, const bf16_t* __restrict__ vr, int half, int ks) {
@@ -99,9 +64,9 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 4 ? 2 : 1) void mhsa_fwd_kern
     const float qscale = 1.4426950408889634f * rsqrtf((float)MH_DH);
     float* lnstat = osave ? reinterpret_cast<float*>(reinterpret_cast<char*>(osave) + mhsa_stat_offset(c)) : nullptr;
 
-    float gam[MH_KS][8], bet[MH_KS][8];
+    float gam[BK_KS][8], bet[BK_KS][8];
 #pragma unroll
-    for (int ks = 0; ks < MH_KS; ++ks) {
+    for (int ks = 0; ks < BK_KS; ++ks) {
         load8(lnw + ks * 32 + 8 * g4, gam[ks]);
         load8(lnb + ks * 32 + 8 * g4, bet[ks]);
     }
@@ -131,11 +96,11 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 4 ? 2 : 1) void mhsa_fwd_kern
         // ---- stage A: LN, then Q (registers), K and V^T (LDS) for this pass's heads --------
         Frag<T> qf[NSW][HPP];
         {
-            Frag<T> u[NSW][MH_KS];
+            Frag<T> u[NSW][BK_KS];
 #pragma unroll
             for (int si = 0; si < NSW; ++si) {
                 const int t = (w * NSW + si) * 16 + l15;
-                ln_strip<T>(xb + (size_t)t * MH_H, t < T_, gam, bet, u[si], lnstat ? lnstat + ((size_t)bf * T_ + t) * 2 : nullptr);
+                ln_strip(xb + (size_t)t * MH_H, t < T_, gam, bet, u[si], lnstat ? lnstat + ((size_t)bf * T_ + t) * 2 : nullptr);
             }
             if (WLDS) {
                 wwin_store();
@@ -155,17 +120,17 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 4 ? 2 : 1) void mhsa_fwd_kern
                     f32x4 ct[NSW][2];
 #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        Frag<T> a[MH_KS];
+                        Frag<T> a[BK_KS];
 #pragma unroll
-                        for (int ks = 0; ks < MH_KS; ++ks) {
-                            if (WLDS) frag_load(a[ks], wl + ((size_t)(((which & 1) * MH_HEADS + head) * 2 + half) * MH_KS + ks) * 512 + lane * 8);
-                            else wfrag_load(a[ks], Win, (which * MH_HEADS + head) * 2 + half, MH_KS, ks);
+                        for (int ks = 0; ks < BK_KS; ++ks) {
+                            if (WLDS) frag_load(a[ks], wl + ((size_t)(((which & 1) * MH_HEADS + head) * 2 + half) * BK_KS + ks) * 512 + lane * 8);
+                            else wfrag_load(a[ks], Win, (which * MH_HEADS + head) * 2 + half, BK_KS, ks);
                         }
 #pragma unroll
                         for (int si = 0; si < NSW; ++si) {
                             f32x4 acc = F32X4_ZERO;
 #pragma unroll
-                            for (int ks = 0; ks < MH_KS; ++ks) acc = mma(a[ks], u[si][ks], acc);
+                            for (int ks = 0; ks < BK_KS; ++ks) acc = mma(a[ks], u[si][ks], acc);
                             ct[si][half] = acc;
                         }
                     }
@@ -425,40 +390,6 @@ static int mhsa_fwd_t(const nbss_cfg& c, const float* P, const void* packed, int
 // G = geometry (geom.h): small dh = 24 (two 16-row tiles per head, the second half empty; one k-step for q k^T), large dh = 48 (three
 // tiles, two k-steps).  in_proj fragments: K_INP tiles (which, head, i) with rows padded to multiples of 32 per head (layout.h).
 template <class T, class G>
-NBSS_DEV void ln_strip_g(const T* __restrict__ xr, bool valid, const float* __restrict__ lnw, const float* __restrict__ lnb, Frag<T> (&u)[G::KS]) {
-    const int g4 = lane_id() >> 4;
-    float v[G::KS][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-        if (valid) load8(xr + ks * 32 + 8 * g4, v[ks]);
-        else
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[ks][j] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum += v[ks][j];
-    }
-    const float mean = wave_sum16(sum) * (1.0f / G::H);
-    float q = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float d = v[ks][j] - mean;
-            q += d * d;
-        }
-    const float rstd = rsqrtf(wave_sum16(q) * (1.0f / G::H) + 1e-5f);
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-        float gam[8], bet[8];
-        load8(lnw + ks * 32 + 8 * g4, gam);
-        load8(lnb + ks * 32 + 8 * g4, bet);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) frag_set(u[ks], j, (v[ks][j] - mean) * rstd * gam[j] + bet[j]);
-    }
-}
-
-template <class T, class G>
 __global__ __launch_bounds__(512) void mhsa_kv_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __restrict__ lnb, const float* __restrict__ bin,
                                                       const T* __restrict__ Win, const T* __restrict__ x, T* __restrict__ Kg, T* __restrict__ Vg) {
     constexpr int H = G::H, DH = G::DH, HEADS = G::HEADS, KS = G::KS;
@@ -469,7 +400,7 @@ __global__ __launch_bounds__(512) void mhsa_kv_kernel(nbss_cfg c, const float* _
     const bool tv = t < T_;
     const size_t n = (size_t)bf * T_ + (tv ? t : 0);
     Frag<T> u[KS];
-    ln_strip_g<T, G>(x + n * H, tv, lnw, lnb, u);
+    ln_strip(x + n * H, tv, lnw, lnb, u);
 #pragma unroll
     for (int which = 1; which < 3; ++which) {
         T* dst = (which == 1 ? Kg : Vg) + n * H;
@@ -526,7 +457,7 @@ __global__ __launch_bounds__(512) void mhsa_flash_kernel(nbss_cfg c, const float
     Frag<T> qf[HEADS][KSD];
     {
         Frag<T> u[KS];
-        ln_strip_g<T, G>(x + n * H, tv, lnw, lnb, u);
+        ln_strip(x + n * H, tv, lnw, lnb, u);
 #pragma unroll
         for (int head = 0; head < HEADS; ++head) {
             f32x4 ct[2 * KSD];

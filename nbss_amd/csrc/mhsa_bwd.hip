@@ -29,7 +29,6 @@
 #define MB_NSW 2   // strips per wave: 2 (8 waves per sequence) or 1 (16 waves, <= 128 VGPRs: four waves per SIMD)
 #endif
 #define MB_NTHR (64 * 16 / MB_NSW)
-#define MB_KS 3
 
 template <class T>
 NBSS_DEV void row_pieces(Frag<T>& f, const T* __restrict__ row) {  // [.. 24] row -> permuted-K fragment (d = 4g+j | 16+4g+j)
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
     }
     // dqkv operand of the in_proj weight gradient: token-major [N][3H]
     auto dqkv_row = [&](int grp, size_t n) -> T* { return dqkv + n * (3 * MB_H) + grp * MB_DH; };
-    Frag<T> uf[MB_NSW][MB_KS], dr[MB_NSW][MB_KS];
+    Frag<T> uf[MB_NSW][BK_KS], dr[MB_NSW][BK_KS];
     float smean[MB_NSW], srstd[MB_NSW];
     // saved attention output / log-sum-exp rows of the current head (raw: converted on use)
     RawRow4<T> onx0[MB_NSW], onx1[MB_NSW];
@@ -182,23 +181,15 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
     for (int i = threadIdx.x; i < 2 * MB_H; i += blockDim.x) lnp[i] = i < MB_H ? lp.p[P_MH_LN_W][i] : lp.p[P_MH_LN_B][i - MB_H];
 #pragma unroll
     for (int si = 0; si < MB_NSW; ++si) {
-        float v[MB_KS][8], sum = 0.f;
+        float v[BK_KS][8];
 #pragma unroll
-        for (int ks = 0; ks < MB_KS; ++ks) {
+        for (int ks = 0; ks < BK_KS; ++ks) {
             if (tv[si]) load8(xb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4, v[ks]);
             else
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[ks][j] = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum += v[ks][j];
         }
-        smean[si] = wave_sum16(sum) * (1.0f / MB_H);
-        float q = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < MB_KS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) q += (v[ks][j] - smean[si]) * (v[ks][j] - smean[si]);
-        srstd[si] = rsqrtf(wave_sum16(q) * (1.0f / MB_H) + 1e-5f);
+        ln_stats(v, smean[si], srstd[si]);
     }
     lds_barrier();  // lnp is read below
     PHASE(0);
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
 #pragma unroll
         for (int si = 0; si < MB_NSW; ++si) {
 #pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
+            for (int ks = 0; ks < BK_KS; ++ks) {
                 if (tv[si]) {
                     frag_load(uf[si][ks], xb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4);
                     frag_load(dr[si][ks], dyb + (size_t)tt[si] * MB_H + ks * 32 + 8 * g4);
@@ -234,7 +225,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
 #pragma unroll
         for (int si = 0; si < MB_NSW; ++si)
 #pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {  // LN(x) in place of x (rebuilt per head from the row statistics)
+            for (int ks = 0; ks < BK_KS; ++ks) {  // LN(x) in place of x (rebuilt per head from the row statistics)
                 float gm[8], bt[8];
                 load8(lnp + ks * 32 + 8 * g4, gm);
                 load8(lnp + MB_H + ks * 32 + 8 * g4, bt);
@@ -248,12 +239,12 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
 #pragma unroll
             for (int si = 0; si < MB_NSW; ++si) ct[si][0] = ct[si][1] = F32X4_ZERO;
 #pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
+            for (int ks = 0; ks < BK_KS; ++ks) {
                 Frag<T> a[2];
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    if (which < 3) wfrag_load(a[half], Win, (which * MB_HEADS + head) * 2 + half, MB_KS, ks);
-                    else wfrag_load(a[half], WoutT, head * 2 + half, MB_KS, ks);
+                    if (which < 3) wfrag_load(a[half], Win, (which * MB_HEADS + head) * 2 + half, BK_KS, ks);
+                    else wfrag_load(a[half], WoutT, head * 2 + half, BK_KS, ks);
                 }
 #pragma unroll
                 for (int si = 0; si < MB_NSW; ++si) {
@@ -486,7 +477,7 @@ __global__ __launch_bounds__(MB_NTHR) void mhsa_bwd_kernel(nbss_cfg c, LayerPtrs
 #pragma unroll
     for (int si = 0; si < MB_NSW; ++si) {
         const size_t n = n0 + tt[si];
-        ln_bwd_row96<T>(du[si], x + n * MB_H, dy + n * MB_H, dx + n * MB_H, stats + n * 2, tv[si], lp.p[P_MH_LN_W], dlw, dlb);
+        ln_bwd_row<T>(du[si], x + n * MB_H, dy + n * MB_H, dx + n * MB_H, stats + n * 2, tv[si], lp.p[P_MH_LN_W], dlw, dlb);
     }
     ln_affine_flush(dlw, dlb, aff, aff + MB_H);
     lds_barrier();
@@ -576,7 +567,7 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
     // gamma / beta after the statistics, for dy / O after the first barrier and for the bias rows inside the projections: 65 % of its wave
     // time, profiles/r04b_phase_mhsa_bwd.txt)
     {
-        Frag<T> uf[2][MB_KS], dr[2][MB_KS];
+        Frag<T> uf[2][BK_KS], dr[2][BK_KS];
         RawRow4<T> orw0[2], orw1[2];
         float lsev[2];
         f32x2 ms[2];
@@ -605,7 +596,7 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
 #pragma unroll
         for (int si = 0; si < 2; ++si) {
 #pragma unroll
-            for (int i = 0; i < MB_KS; ++i) {
+            for (int i = 0; i < BK_KS; ++i) {
                 const int tc = tv[si] ? tt[si] : tlast;
                 frag_load(uf[si][i], xb + (tc * MB_H + i * 32 + 8 * g4));
                 frag_load(dr[si][i], dyb + (tc * MB_H + i * 32 + 8 * g4));
@@ -655,7 +646,7 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
         for (int si = 0; si < 2; ++si) {
             const short dmask = tv[si] ? (short)-1 : (short)0;
 #pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
+            for (int ks = 0; ks < BK_KS; ++ks) {
                 float gm[8], bt[8];
                 load8(lnp + ks * 32 + 8 * g4, gm);
                 load8(lnp + MB_H + ks * 32 + 8 * g4, bt);
@@ -671,10 +662,10 @@ __global__ __launch_bounds__(512, 4) void mhsa_bwd_h_kernel(nbss_cfg c, LayerPtr
 #pragma unroll
             for (int si = 0; si < 2; ++si) ct[si][0] = ct[si][1] = F32X4_ZERO;
 #pragma unroll
-            for (int ks = 0; ks < MB_KS; ++ks) {
+            for (int ks = 0; ks < BK_KS; ++ks) {
                 Frag<T> a[2];
 #pragma unroll
-                for (int half = 0; half < 2; ++half) frag_load(a[half], wl + (((which * 6 + half * MB_KS + ks) * 64 + lane) * 8));
+                for (int half = 0; half < 2; ++half) frag_load(a[half], wl + (((which * 6 + half * BK_KS + ks) * 64 + lane) * 8));
 #pragma unroll
                 for (int si = 0; si < 2; ++si) {
                     if (!sact[si]) continue;

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(TW_THREADS, 2) void tailw_kernel(TailArgs a) {
                     du[mt] = mma(af, df, du[mt]);
                 }
             }
-            ln_bwd_row96_raw_na<bf16_t>(du, xr, dr, a.dx + nrow * TW_H, tv, lnp);
+            ln_bwd_row_raw<false>(du, xr, dr, a.dx + nrow * TW_H, nullptr, tv, lnp);
         };
         RawC4<bf16_t> xn[TPW][BK_MT], dn[TPW][BK_MT];
         if (ch < nchunks) {

@@ -26,7 +26,6 @@
 #define TF_CG 24
 #define TF_TP 256
 #define TF_NSW 2     // strips per wave of the backward kernel (8 waves); the forward kernel takes it as a template parameter
-#define TF_KS (TF_H / 32)
 #ifndef TF_FWD_WPS
 #define TF_FWD_WPS 2
 #endif
@@ -34,12 +33,12 @@
 #define TF_AFF (2 * TF_FFN + 2 * TF_H)  // GN weight, GN bias, LN weight, LN bias partial sums per workgroup
 
 template <class T>
-NBSS_DEV void ln_strip_tf(const T* __restrict__ xr, bool valid, const float (&gam)[TF_KS][8], const float (&bet)[TF_KS][8], Frag<T> (&u)[TF_KS]) {
+NBSS_DEV void ln_strip_tf(const T* __restrict__ xr, bool valid, const float (&gam)[BK_KS][8], const float (&bet)[BK_KS][8], Frag<T> (&u)[BK_KS]) {
     const int g4 = lane_id() >> 4;
-    float v[TF_KS][8];
+    float v[BK_KS][8];
     float sum = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < TF_KS; ++ks) {
+    for (int ks = 0; ks < BK_KS; ++ks) {
         if (valid) load8(xr + ks * 32 + 8 * g4, v[ks]);
         else
 #pragma unroll
@@ -50,7 +49,7 @@ NBSS_DEV void ln_strip_tf(const T* __restrict__ xr, bool valid, const float (&ga
     const float mean = wave_sum16(sum) * (1.0f / TF_H);
     float q = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < TF_KS; ++ks)
+    for (int ks = 0; ks < BK_KS; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float d = v[ks][j] - mean;
@@ -58,7 +57,7 @@ NBSS_DEV void ln_strip_tf(const T* __restrict__ xr, bool valid, const float (&ga
         }
     const float rstd = rsqrtf(wave_sum16(q) * (1.0f / TF_H) + 1e-5f);
 #pragma unroll
-    for (int ks = 0; ks < TF_KS; ++ks)
+    for (int ks = 0; ks < BK_KS; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) frag_set(u[ks], j, (v[ks][j] - mean) * rstd * gam[ks][j] + bet[ks][j]);
 }
@@ -247,11 +246,11 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 1 ? 4 : TF_FWD_WPS) void tcon
         tv[si] = tg >= 0 && tg < T_;
         tin[si] = tv[si] && (!LONG || (tt[si] >= HALO && tt[si] < HALO + CH));
     }
-    Frag<T> u[NSW][TF_KS];
+    Frag<T> u[NSW][BK_KS];
     {
-        float gam[TF_KS][8], bet[TF_KS][8];
+        float gam[BK_KS][8], bet[BK_KS][8];
 #pragma unroll
-        for (int ks = 0; ks < TF_KS; ++ks)
+        for (int ks = 0; ks < BK_KS; ++ks)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 gam[ks][j] = lnw[ks * 32 + 8 * g4 + j];
@@ -306,14 +305,14 @@ __global__ __launch_bounds__(64 * 16 / NSW, NSW == 1 ? 4 : TF_FWD_WPS) void tcon
         // (a) h1 = SiLU(W1_g LN(x) + b1_g) -> ha
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            Frag<T> a[TF_KS];
+            Frag<T> a[BK_KS];
 #pragma unroll
-            for (int ks = 0; ks < TF_KS; ++ks) lfrag<T>(a[ks], wl, half * 3 + ks);
+            for (int ks = 0; ks < BK_KS; ++ks) lfrag<T>(a[ks], wl, half * 3 + ks);
 #pragma unroll
             for (int si = 0; si < NSW; ++si) {
                 f32x4 acc = F32X4_ZERO;
 #pragma unroll
-                for (int ks = 0; ks < TF_KS; ++ks) acc = mma(a[ks], u[si][ks], acc);
+                for (int ks = 0; ks < BK_KS; ++ks) acc = mma(a[ks], u[si][ks], acc);
                 ct[si][half] = acc;
             }
         }
@@ -455,9 +454,6 @@ NBSS_DEV void store_op(float* __restrict__ op, size_t n, bool valid, int gr, con
     if (g4 < 2) store4_nt(r + 16 + 4 * g4, hi[0], hi[1], hi[2], hi[3]);
 }
 
-// sum over the 16 lanes that share (lane>>4): per-channel reduction over the frames of a strip
-NBSS_DEV float sum_l15(float v) { return row_sum16(v); }
-
 __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs lp, const float* __restrict__ P, float* __restrict__ part, int layer,
                                                            const float* __restrict__ W1, const float* __restrict__ Wc1, const float* __restrict__ Wc2,
                                                            const float* __restrict__ Wc3, const float* __restrict__ W1tn, const float* __restrict__ Wc1t,
@@ -529,9 +525,9 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
     float smean[TF_NSW], srstd[TF_NSW];
 #pragma unroll
     for (int si = 0; si < TF_NSW; ++si) {
-        float v[TF_KS][8], sum = 0.f;
+        float v[BK_KS][8], sum = 0.f;
 #pragma unroll
-        for (int ks = 0; ks < TF_KS; ++ks) {
+        for (int ks = 0; ks < BK_KS; ++ks) {
             load8(xb + (size_t)tc[si] * TF_H + ks * 32 + 8 * g4, v[ks]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) sum += v[ks][j];
@@ -539,7 +535,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
         smean[si] = wave_sum16(sum) * (1.0f / TF_H);
         float q = 0.f;
 #pragma unroll
-        for (int ks = 0; ks < TF_KS; ++ks)
+        for (int ks = 0; ks < BK_KS; ++ks)
 #pragma unroll
             for (int j = 0; j < 8; ++j) q += (v[ks][j] - smean[si]) * (v[ks][j] - smean[si]);
         srstd[si] = rsqrtf(wave_sum16(q) * (1.0f / TF_H) + 1e-5f);
@@ -567,11 +563,11 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
         // x, dy and the weights behind stores were 43 % of the wave time).
         // (Issuing them one phase earlier still, before the last conv phase of the previous group, spilled 20 registers and
         // was slower: 6.7 vs 6.3 ms/step.)
-        Frag<float> xr[TF_NSW][TF_KS], dr[TF_NSW][TF_KS];
+        Frag<float> xr[TF_NSW][BK_KS], dr[TF_NSW][BK_KS];
 #pragma unroll
         for (int si = 0; si < TF_NSW; ++si)
 #pragma unroll
-            for (int ks = 0; ks < TF_KS; ++ks) {
+            for (int ks = 0; ks < BK_KS; ++ks) {
                 // unconditional (clamped) loads: frames beyond T re-read the last frame; LN(x) of such frames is replaced by beta below
                 // and every product of their dy is masked where it is used
                 frag_load(xr[si][ks], xb + (size_t)tc[si] * TF_H + ks * 32 + 8 * g4);
@@ -592,7 +588,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
             dh5[si][0] = F32X4_ZERO;
             dh5[si][1] = F32X4_ZERO;
 #pragma unroll
-            for (int ks = 0; ks < TF_KS; ++ks) {
+            for (int ks = 0; ks < BK_KS; ++ks) {
                 Frag<float> uf;
                 float gm[8], bt[8];
                 load8(lnp + ks * 32 + 8 * g4, gm);
@@ -742,7 +738,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
             }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float w0 = sum_l15(dgw[0][r]), w1 = sum_l15(dgw[1][r]), q0 = sum_l15(dgb[0][r]), q1 = sum_l15(dgb[1][r]);
+            const float w0 = row_sum16(dgw[0][r]), w1 = row_sum16(dgw[1][r]), q0 = row_sum16(dgb[0][r]), q1 = row_sum16(dgb[1][r]);
             if (l15 == 0 && wact) {
                 atomicAdd(aff + cbase + d0 + r, w0);
                 atomicAdd(aff + TF_FFN + cbase + d0 + r, q0);
@@ -903,7 +899,7 @@ __global__ __launch_bounds__(512) void tconvffn_bwd_kernel(nbss_cfg c, LayerPtrs
     for (int mt = 0; mt < TF_H / 16; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float a = sum_l15(dlw[mt][r]), b = sum_l15(dlb[mt][r]);
+            const float a = row_sum16(dlw[mt][r]), b = row_sum16(dlb[mt][r]);
             if (l15 == 0 && wact) {
                 atomicAdd(aff + 2 * TF_FFN + 16 * mt + 4 * g4 + r, a);
                 atomicAdd(aff + 2 * TF_FFN + TF_H + 16 * mt + 4 * g4 + r, b);

@@ -272,3 +272,81 @@ def test_block_forward_backward_random_small_grids(emu_lib):
             for (B, F, T) in [(1, 1, 1), (1, 1, 2), (2, 1, 1), (1, 2, 1)]:
                 run(B, F, T, block, dtype)
     check()
+
+
+# ---- the LayerNorm row helpers' edges (csrc/blocks.h), on both backends ---------------------------------------------------------------------------
+# The narrow-band kernels (mhsa, tconvffn) cut T into strips of 16 frames, the cross-band kernels (fconv, full) cut F into tiles of 16 rows; a
+# lane outside the grid holds zeros or a clamped row.  Grids (F, T): a single row | a last tile with ONE valid row along F and one strip of 15 along T |
+# exactly one tile along F, a last strip with one valid row along T | 5 rows, two strips and one frame.  "large": the smallest SpatialNet-large
+# grid of tests/test_large.py (the H = 192 instances).  "offset": x + 300, far above its spread — the variance has to come from the deviations.
+LN_EDGE_GRIDS = {"F1_T1": (2, 1, 1, "small", 0.0), "F17_T15": (2, 17, 15, "small", 0.0), "F16_T17": (2, 16, 17, "small", 0.0), "F5_T33": (2, 5, 33, "small", 0.0),
+                 "large_F5_T19": (1, 5, 19, "large", 0.0), "offset_F17_T15": (2, 17, 15, "small", 300.0)}
+_FC_NAMES = [[f"layers.0.fconv{w + 1}.{k}" for k in ("0.weight", "0.bias", "1.weight", "1.bias", "2.weight")] for w in (0, 1)]
+LN_EDGE_BLOCKS = {
+    "mhsa": (lambda x, p: ref.mhsa(x, p, "layers.0"), MH_NAMES, 3e-2),
+    "tconvffn": (lambda x, p: ref.tconvffn(x, p, "layers.0"), TF_NAMES, 3e-2),
+    "fconv0": (lambda x, p: ref.fconv(x, p, "layers.0.fconv1"), _FC_NAMES[0], 5e-2),
+    "fconv1": (lambda x, p: ref.fconv(x, p, "layers.0.fconv2"), _FC_NAMES[1], 5e-2),
+    "full": (lambda x, p: ref.full(x, p, "layers.0"), FULL_NAMES, 3e-2)}
+_ln_edge_oracle = {}  # (block, grid, dtype) -> the fp64 oracle's y, dx and parameter gradients: computed once, shared by both backends, never written
+
+
+def _ln_edge_case(backend, block, grid, dtype):
+    B, F, T, geo, offset = LN_EDGE_GRIDS[grid]
+    cs = Case(backend, B, F, T, dtype, geo=geo)
+    x, x64 = cs.stream(seed=11)
+    if offset:
+        x = x + offset
+        x64 = x.double().cpu()
+    dy, dy64 = cs.stream(seed=111, scale=0.5)
+    fwd_ref, names, _ = LN_EDGE_BLOCKS[block]
+    key = (block, grid, dtype)
+    if key not in _ln_edge_oracle:
+        want_dx, want_g = oracle_grads(fwd_ref, x64, cs.p64, dy64, names)
+        _ln_edge_oracle[key] = (fwd_ref(x64, cs.p64), want_dx, want_g)
+    return cs, x, x64, dy, dy64, _ln_edge_oracle[key]
+
+
+LN_EDGE_CASES = [pytest.param(g, d, id=f"{g}-{n}") for g in sorted(LN_EDGE_GRIDS) for d, n in ((NBSS_F32, "f32"), (NBSS_BF16, "bf16"))
+                 if d == NBSS_F32 or not LN_EDGE_GRIDS[g][4]]  # (the offset case is an fp32 case)
+
+
+@pytest.mark.parametrize("grid,dtype", LN_EDGE_CASES)
+@pytest.mark.parametrize("block", sorted(LN_EDGE_BLOCKS))
+def test_layernorm_row_edges(backend, block, grid, dtype):
+    """forward and backward of every fused block at the edges of the LayerNorm row helpers, emulator and device, against the fp64 oracle at the bars of
+    the fixed-shape tests: forward y <= 2e-5 | 1.5e-2 and the branch y - x <= 3 x that (tests/test_kernels_fwd.py); dx <= 1e-4 | 3e-2 (F-conv bf16: 5e-2), the
+    branch gradient dx - dy <= 3 x that, every parameter gradient at the dx bar (bf16 on fewer than 128 tokens: 4 x, as in
+    test_block_forward_backward_random_small_grids).  The offset case is fp32 only."""
+    cs, x, x64, dy, dy64, (want_y, want_dx, want_g) = _ln_edge_case(backend, block, grid, dtype)
+    lib, cfg, dev = cs.lib, cs.cfg, backend.device
+    G = torch.zeros_like(cs.flat)
+    ws = ops.workspace(lib, cfg, dev)
+    if block == "mhsa":
+        save = ops.mhsa_save(lib, cfg, dev)
+        y = ops.mhsa_fwd(lib, cfg, cs.flat, cs.packed, 0, x, o_save=save)
+        dx = ops.mhsa_bwd(lib, cfg, cs.flat, G, cs.packed, 0, x, dy, save, ws)
+    elif block == "tconvffn":
+        y = ops.tconvffn_fwd(lib, cfg, cs.flat, cs.packed, 0, x)
+        dx = ops.tconvffn_bwd(lib, cfg, cs.flat, G, cs.packed, 0, x, dy, ws)
+    elif block == "full":
+        y = ops.full_fwd(lib, cfg, cs.flat, cs.packed, 0, x)
+        dx = ops.full_bwd(lib, cfg, cs.flat, G, cs.packed, 0, x, dy, ws)
+    else:
+        which = int(block[-1])
+        y = ops.fconv_fwd(lib, cfg, cs.flat, cs.packed, 0, which, x)
+        dx = ops.fconv_bwd(lib, cfg, cs.flat, G, cs.packed, 0, which, x, dy, ws)
+    ftol = cs.tol
+    btol = 1e-4 if dtype == NBSS_F32 else LN_EDGE_BLOCKS[block][2]
+    gtol = btol if cfg.B * cfg.F * cfg.T >= 128 or dtype == NBSS_F32 else 4 * btol
+    figures = [("y", rel_l2(y, want_y), ftol), ("y - x", rel_l2(y.double().cpu() - x64, want_y - x64), 3 * ftol),
+               ("dx", rel_l2(dx, want_dx), btol), ("dx - dy", rel_l2(dx.double().cpu() - dy64, want_dx - dy64), 3 * btol)]
+    table = param_table(lib, cfg)
+    for n, g in want_g.items():
+        off, shape = table[n]
+        got = G[off:off + g.numel()].reshape(shape)
+        figures.append((n, rel_l2(got, g) if float(g.abs().max()) > 0 else float(got.abs().max()), gtol))
+    for name, err, bar in figures:
+        print(f"ln_edge {backend.name} {block} {grid} {'f32' if dtype == NBSS_F32 else 'bf16'} {name}: {err:.3e} (bar {bar:.1e})")
+    bad = [(name, err, bar) for name, err, bar in figures if not err < bar]
+    assert not bad, bad
