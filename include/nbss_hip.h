@@ -447,6 +447,38 @@ int nbss_online_ret_train_fwd(int dtype, int64_t BF, int T, const void* q, const
 int nbss_online_ret_train_bwd(int dtype, int64_t BF, int T, const void* q, const void* k, const void* v, const void* g, float k_scale,
                               const float* decay, const void* save, const void* d_out, void* dq, void* dk, void* dv, void* dg, void* ws, void* stream);
 
+/* ---- OnlineSpatialNet: the cross-band trio for training (csrc/online_xband_train.hip; nbss_amd/online_train.py) -------------------------------
+ * x1 = x + fconv1(x), x2 = x1 + full(x1), y = x2 + fconv2(x2) of models/arch/OnlineSpatialNet.py `SpatialNetLayer.forward` on x, y [B][F][T][96] of
+ * `dtype`, forward and backward, through the SpatialNet-small kernels behind nbss_fconv_fwd / nbss_full_fwd and their _bwd (the same launches: the results
+ * have the bits of chaining those entry points on a one-layer SpatialNet with the same parameters).  No nbss_cfg, flat buffer or packed buffer on the
+ * caller's side: the 18 parameters are the module's own fp32 tensors in state_dict order and layout — fconv1.0.{weight,bias} [96], fconv1.1.weight
+ * [96][12][5], fconv1.1.bias [96], fconv1.2.weight [96] (per-channel PReLU), norm_full.{weight,bias} [96], squeeze.0.weight [8][96], squeeze.0.bias [8],
+ * full.weight [8][F][F], full.bias [8][F], unsqueeze.0.weight [96][8], unsqueeze.0.bias [96], fconv2.* like fconv1.* — gathered and packed inside `ws` by
+ * every call.  Geometry 96 / 8, F-conv groups 8, kernel 5, zero padding, LayerNorm eps 1e-5.
+ * save: nbss_online_xband_save_bytes() bytes that the forward fills for the backward: x1 and x2, two stream tensors; the backward recomputes every
+ *   other intermediate from x, x1 and x2.  save = NULL: forward only, nothing kept.
+ * ws: nbss_online_xband_ws_bytes() bytes of scratch, for either call (it holds the reused backward kernels' workspace, nbss_workspace_bytes of the
+ *   one-layer configuration: allocate it once per shape, not per call).
+ * bwd: dx includes the three residual paths; the 18 d_* buffers are WRITTEN (not accumulated; they may be uninitialised).
+ * NBSS_EINVAL: dtype outside {NBSS_F32, NBSS_BF16}, B, F or T < 1, a NULL pointer (`save` of the forward excepted), y == x, dx == dy.
+ * NBSS_EUNSUPPORTED: F > 272, T > 4096, more than 2^31 / 288 tokens; for the backward, a forward with `save`, and nbss_online_xband_save_bytes: T > 256,
+ * or NBSS_F32 with F > 160.  The two *_bytes calls return the same codes (negative) instead of a size.  Nothing is launched after a refusal. */
+int64_t nbss_online_xband_save_bytes(int dtype, int B, int F, int T);
+int64_t nbss_online_xband_ws_bytes(int dtype, int B, int F, int T);
+int nbss_online_xband_train_fwd(int dtype, int B, int F, int T, const float* fc1_ln_w, const float* fc1_ln_b, const float* fc1_w, const float* fc1_b,
+                                const float* fc1_prelu, const float* full_ln_w, const float* full_ln_b, const float* sq_w, const float* sq_b,
+                                const float* full_w, const float* full_b, const float* usq_w, const float* usq_b, const float* fc2_ln_w,
+                                const float* fc2_ln_b, const float* fc2_w, const float* fc2_b, const float* fc2_prelu, const void* x, void* y, void* save,
+                                void* ws, void* stream);
+int nbss_online_xband_train_bwd(int dtype, int B, int F, int T, const float* fc1_ln_w, const float* fc1_ln_b, const float* fc1_w, const float* fc1_b,
+                                const float* fc1_prelu, const float* full_ln_w, const float* full_ln_b, const float* sq_w, const float* sq_b,
+                                const float* full_w, const float* full_b, const float* usq_w, const float* usq_b, const float* fc2_ln_w,
+                                const float* fc2_ln_b, const float* fc2_w, const float* fc2_b, const float* fc2_prelu, const void* x, const void* save,
+                                const void* dy, void* dx, float* d_fc1_ln_w, float* d_fc1_ln_b, float* d_fc1_w, float* d_fc1_b, float* d_fc1_prelu,
+                                float* d_full_ln_w, float* d_full_ln_b, float* d_sq_w, float* d_sq_b, float* d_full_w, float* d_full_b, float* d_usq_w,
+                                float* d_usq_b, float* d_fc2_ln_w, float* d_fc2_ln_b, float* d_fc2_w, float* d_fc2_b, float* d_fc2_prelu, void* ws,
+                                void* stream);
+
 /* ---- OnlineSpatialNet: the waveform ends of a streaming step (csrc/online_io.hip; nbss_amd/online_io.py: NativeWaveStreamer) ----------------
  * n_fft in {256, 512}, hop = n_fft/2, win_len = n_fft, `tables` of nbss_stft_tables; 2 <= C <= 32 frames per call (NBSS_EUNSUPPORTED outside).
  * Frame t of the stream is frame t of torch.stft(center=True): samples [(t-1) hop, (t+1) hop).  Neither call knows a first or a last chunk:

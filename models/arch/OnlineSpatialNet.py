@@ -91,9 +91,7 @@ class SpatialNetLayer(nn.Module):
 
     def forward(self, x: Tensor, att_mask=None, chunkwise_recurrent: bool = True, rope=True, state: Dict[int, Any] = None, inference: bool = False):
         """x [B,F,T,H] -> (x, attention weights or None)"""
-        x = x + self._fconv(self.fconv1, x)
-        x = x + self._full(x)
-        x = x + self._fconv(self.fconv2, x)
+        x = self._xband(x, state)
         a, attn = self._tsa(x, att_mask, chunkwise_recurrent, rope, state=state, inference=inference)
         x = x + a
         x = self._tconvffn(x, state=state, residual=True)
@@ -150,6 +148,21 @@ class SpatialNetLayer(nn.Module):
         return x + h if residual else h
 
     # ---- cross-band ------------------------------------------------------------------------------------------------------------
+    def _xband(self, x: Tensor, state: Dict[int, Any] = None) -> Tensor:
+        """x + fconv1, + full-band, + fconv2.  A whole-utterance call (state is None) runs the three blocks as ONE autograd node through the HIP kernels of
+        nbss_amd/online_train.py, forward and backward, when NBSS_ONLINE_NATIVE_XBAND=1 (off by default) and `xband_eligible` accepts the call (else, with
+        the switch on, the torch.nn modules below and one warning that names the reason)"""
+        if os.environ.get("NBSS_ONLINE_NATIVE_XBAND", "0") == "1":
+            from nbss_amd import online_train
+            why = online_train.xband_eligible(self, x, state)
+            if why is None:
+                return online_train.xband_residual(self, x)
+            if why.startswith("!"):
+                torch_path_note(self, "OnlineSpatialNet cross-band blocks", why[1:])
+        x = x + self._fconv(self.fconv1, x)
+        x = x + self._full(x)
+        return x + self._fconv(self.fconv2, x)
+
     def _fconv(self, ml: nn.ModuleList, x: Tensor) -> Tensor:
         B, Fq, T, H = x.shape
         h = x.permute(0, 2, 3, 1).reshape(B * T, H, Fq)

@@ -108,6 +108,10 @@ SIGNATURES = {
     "nbss_online_tconvffn_train_ws_bytes": (C.c_int64, [_I] * 4),
     "nbss_online_tconvffn_train_fwd": (_I, [_I] * 4 + [_P] * 19),
     "nbss_online_tconvffn_train_bwd": (_I, [_I] * 4 + [_P] * 34),
+    "nbss_online_xband_save_bytes": (C.c_int64, [_I] * 4),
+    "nbss_online_xband_ws_bytes": (C.c_int64, [_I] * 4),
+    "nbss_online_xband_train_fwd": (_I, [_I] * 4 + [_P] * 23),
+    "nbss_online_xband_train_bwd": (_I, [_I] * 4 + [_P] * 42),
     "nbss_online_ret_train_save_bytes": (C.c_int64, [_I, C.c_int64, _I]),
     "nbss_online_ret_train_ws_bytes": (C.c_int64, [_I, C.c_int64, _I]),
     "nbss_online_ret_train_fwd": (_I, [_I, C.c_int64, _I, _P, _P, _P, _P, C.c_float] + [_P] * 5),

@@ -3,12 +3,16 @@ SiLU -> causal grouped conv -> SiLU -> causal grouped conv -> GroupNorm of each 
 -> SiLU -> 1x1 -> + x, on the whole [B,F,T,96] stream in fp32 or bf16, with every parameter gradient from the HIP backward.
 
 `models.arch.OnlineSpatialNet.SpatialNetLayer._tconvffn` takes it when NBSS_ONLINE_NATIVE_TRAIN=1 (off by default), the tensor is on a HIP device, the call
-is not a streaming one, `supported(layer)` is None and the stream is fp32 (or autocast to bf16); attention and the cross-band blocks keep their torch.nn
-modules in training.
+is not a streaming one, `supported(layer)` is None and the stream is fp32 (or autocast to bf16); attention and the cross-band blocks have switches of
+their own (below).
 
 The chunkwise retention core (csrc/online_ret_train.hip: nbss_online_ret_train_fwd / _bwd) has a switch of its own, NBSS_ONLINE_NATIVE_RET=1 (off by default,
 independent of the one above): `SpatialNetLayer._tsa` then runs the module's four projections and out_proj as its own nn.Linear's around
-`OnlineRetentionFn`, which replaces MultiScaleRetention.chunk_recurrent_forward, the per-head RMSNorm and the SiLU gate (`ret_eligible` says when)."""
+`OnlineRetentionFn`, which replaces MultiScaleRetention.chunk_recurrent_forward, the per-head RMSNorm and the SiLU gate (`ret_eligible` says when).
+
+The cross-band trio (csrc/online_xband_train.hip: nbss_online_xband_train_fwd / _bwd) has the third switch, NBSS_ONLINE_NATIVE_XBAND=1 (off by default, independent
+of the other two): `SpatialNetLayer._xband` then evaluates x + fconv1, + full-band, + fconv2 as one `OnlineXBandFn` node on SpatialNet-small's F-conv and full-band
+kernels (`xband_eligible` says when).  With all three on, what stays torch.nn in a training layer is the LayerNorm and the linear projections around retention."""
 from __future__ import annotations
 
 import contextlib
@@ -255,3 +259,146 @@ def retention_forward(mhsa, u: Tensor, rel_pos) -> Tensor:
         out = ops.online_ret_train_fwd(lib, q.contiguous(), None if k is None else k.contiguous(), v.contiguous(), g.contiguous(), float(mhsa.scaling), decay,
                                        keep=False)[0]
     return mhsa.out_proj(out)
+
+
+# ---- the cross-band trio (NBSS_ONLINE_NATIVE_XBAND) --------------------------------------------------------------------------------------------------------
+XBAND_F_MAX, XBAND_T_MAX, XBAND_T_TRAIN_MAX, XBAND_F_TRAIN_MAX_FP32 = 272, 4096, 256, 160
+# (attribute path, tensor) in the order of the C ABI's parameter list = state_dict order
+XBAND_SLOTS = (("fconv1", 0, "weight"), ("fconv1", 0, "bias"), ("fconv1", 1, "weight"), ("fconv1", 1, "bias"), ("fconv1", 2, "weight"),
+               ("norm_full", None, "weight"), ("norm_full", None, "bias"), ("squeeze", 0, "weight"), ("squeeze", 0, "bias"), ("full", None, "weight"),
+               ("full", None, "bias"), ("unsqueeze", 0, "weight"), ("unsqueeze", 0, "bias"),
+               ("fconv2", 0, "weight"), ("fconv2", 0, "bias"), ("fconv2", 1, "weight"), ("fconv2", 1, "bias"), ("fconv2", 2, "weight"))
+
+
+def xband_enabled() -> bool:
+    """the cross-band switch, read at call time; off unless it is exactly '1'"""
+    return os.environ.get("NBSS_ONLINE_NATIVE_XBAND", "0") == "1"
+
+
+def xband_params(layer) -> List[Tensor]:
+    """the trio's 18 parameters (the module's live tensors; a LinearGroup shared across layers is the same tensor in each) in the order of the C ABI"""
+    out = []
+    for name, i, a in XBAND_SLOTS:
+        m = getattr(layer, name)
+        out.append(getattr(m if i is None else m[i], a, None))
+    return out
+
+
+def xband_supported(layer) -> Optional[str]:
+    """None when the layer's fconv1 / full-band block / fconv2 are the geometry the kernels are built for (SpatialNet-small's cross-band blocks), else the reason"""
+    for name, norm in (("norms[3]", layer.fconv1[0]), ("norms[4]", layer.fconv2[0]), ("norms[5]", layer.norm_full)):
+        if type(norm).__name__ != "LayerNorm":
+            return f"{name} must be LN (got {type(norm).__name__})"
+        if tuple(norm.normalized_shape) != (96,):
+            return f"dim_hidden must be 96 (got {norm.normalized_shape[0]})"
+        if norm.eps != 1e-5 or norm.weight is None or norm.bias is None:
+            return f"{name} must be LayerNorm(eps=1e-5) with weight and bias"
+    if layer.dropout_full is not None:
+        return "dropout[2] (dropout_full) must be 0"
+    sq, usq = layer.squeeze[0], layer.unsqueeze[0]
+    if sq.in_channels != 96 or usq.out_channels != 96:
+        return f"dim_hidden must be 96 (got {sq.in_channels})"
+    if sq.out_channels != 8 or usq.in_channels != 8 or layer.full.num_groups != 8:
+        return f"dim_squeeze must be 8 (got {sq.out_channels})"
+    if sq.kernel_size[0] != 1 or usq.kernel_size[0] != 1 or sq.bias is None or usq.bias is None:
+        return "squeeze and unsqueeze must be 1x1 convolutions with bias"
+    if type(layer.squeeze[1]).__name__ != "SiLU" or type(layer.unsqueeze[1]).__name__ != "SiLU":
+        return "squeeze and unsqueeze must end in SiLU"
+    if layer.full.bias is None:
+        return "the LinearGroup must have a bias"
+    if layer.full.in_features != layer.full.out_features:
+        return "the LinearGroup must be square"
+    for ml in (layer.fconv1, layer.fconv2):
+        conv, act = ml[1], ml[2]
+        if conv.in_channels != 96 or conv.out_channels != 96:
+            return f"dim_hidden must be 96 (got {conv.in_channels})"
+        if conv.groups != 8:
+            return f"the F-convs must have 8 groups (got {conv.groups})"
+        if conv.kernel_size[0] != 5 or conv.dilation[0] != 1 or conv.stride[0] != 1:
+            return f"the F-conv kernel size must be 5 (got {conv.kernel_size[0]}), without dilation or stride"
+        if conv.padding_mode != "zeros" or conv.padding != "same":
+            return f"padding must be 'zeros' (got {conv.padding_mode!r})"
+        if conv.bias is None:
+            return "the F-convs must have a bias"
+        if type(act).__name__ != "PReLU" or act.weight.numel() != 96:
+            return "the F-conv activation must be a per-channel PReLU"
+    return None
+
+
+def xband_eligible(layer, x: Tensor, state) -> Optional[str]:
+    """None when this call of `SpatialNetLayer.forward` takes the native cross-band trio; else why not, with the conventions of `eligible` (a leading '!':
+    worth a warning)"""
+    if not xband_enabled():
+        return "NBSS_ONLINE_NATIVE_XBAND is not 1"
+    if state is not None:
+        return "streaming call"
+    if _LIB_OVERRIDE is None and not x.is_cuda:
+        return "not on a HIP device"
+    if active_lib(x) is None:
+        return "no library for the tensor's device"
+    why = xband_supported(layer)
+    if why is not None:
+        return "!" + why
+    if x.dim() != 4 or x.shape[-1] != 96:
+        return f"!input must be [B,F,T,96], got {tuple(x.shape)}"
+    dt = _stream_dtype(x)
+    if dt is None:
+        return f"!the stream must be fp32, or bf16 under autocast (got {x.dtype})"
+    B, Fq, T = x.shape[:3]
+    if Fq != layer.full.in_features:
+        return f"!the input has {Fq} frequencies, the LinearGroup {layer.full.in_features}"
+    if B < 1 or not 1 <= T <= XBAND_T_MAX or not 1 <= Fq <= XBAND_F_MAX or B * Fq * T * 288 >= 2 ** 31:
+        return f"!1 <= T <= {XBAND_T_MAX}, F <= {XBAND_F_MAX} and B F T < 2^31 / 288 (got B = {B}, F = {Fq}, T = {T})"
+    if _xband_needs_grad(layer, x) and (T > XBAND_T_TRAIN_MAX or (dt == torch.float32 and Fq > XBAND_F_TRAIN_MAX_FP32)):
+        return f"!with gradients T <= {XBAND_T_TRAIN_MAX}, and F <= {XBAND_F_TRAIN_MAX_FP32} in fp32 (got T = {T}, F = {Fq})"
+    return None
+
+
+def _xband_needs_grad(layer, x: Tensor) -> bool:
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in xband_params(layer)))
+
+
+def _xband_kernel_params(params) -> List[Tensor]:
+    """fp32 and contiguous (views where the module's tensors already are: the 1x1 weights [O][I][1] are their matrices as they lie)"""
+    return [p.detach().float().contiguous() for p in params]
+
+
+class OnlineXBandFn(torch.autograd.Function):
+    """y = the cross-band trio through the HIP kernels; inputs (lib, x, *the 18 parameters): the parameters are inputs of the node, so p.grad is populated
+    the usual way (a LinearGroup shared by several layers is an input of several nodes: autograd sums).  Saved: x and the two block inputs the forward keeps.
+    One backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
+
+    @staticmethod
+    def forward(ctx, lib, x, *params):
+        xk = x.contiguous()
+        p32 = _xband_kernel_params(params)
+        y, save = ops.online_xband_train_fwd(lib, p32, xk, keep=True)
+        ctx.lib, ctx.saved, ctx.params = lib, (xk, save, p32), params
+        ctx.versions = [p._version for p in params]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        ops.graph_guard_check(ctx, "OnlineSpatialNet native cross-band blocks")
+        xk, save, p32 = ctx.saved
+        dx, grads = ops.online_xband_train_bwd(ctx.lib, p32, xk, save, dy.contiguous())
+        ctx.saved = None
+        out = [g.reshape(p.shape).to(p.dtype) if ctx.needs_input_grad[2 + i] else None for i, (g, p) in enumerate(zip(grads, ctx.params))]
+        return (None, dx if ctx.needs_input_grad[1] else None, *out)
+
+
+def xband_residual(layer, x: Tensor) -> Tensor:
+    """x + fconv1, + full, + fconv2 for a call `xband_eligible` accepted; in the dtype of x.  Without autograd (no_grad, or nothing requires a gradient) the
+    forward runs alone and keeps nothing."""
+    lib = active_lib(x)
+    if lib is None:
+        raise ops.NbssError("OnlineSpatialNet native cross-band blocks: no library for a tensor on " + str(x.device))
+    params = xband_params(layer)
+    xs = x.to(_stream_dtype(x))
+    if _xband_needs_grad(layer, x):
+        y = OnlineXBandFn.apply(lib, xs, *params)
+    else:
+        with torch.no_grad():
+            y = ops.online_xband_train_fwd(lib, _xband_kernel_params(params), xs.contiguous(), keep=False)[0]
+    return y.to(x.dtype)

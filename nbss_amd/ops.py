@@ -633,3 +633,67 @@ def online_ret_train_bwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g:
     lib.call("nbss_online_ret_train_bwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
              _ptr(lib, save), _ptr(lib, d_out), _ptr(lib, dq), _ptr(lib, dk), _ptr(lib, dv), _ptr(lib, dg), _ptr(lib, ws), _stream(lib, q))
     return dq, dk, dv, dg
+
+
+# ---- OnlineSpatialNet: the cross-band trio for training (csrc/online_xband_train.hip) -----------------------------------------------------------
+def online_xband_save_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
+    return _online_train_bytes(lib, "nbss_online_xband_save_bytes", dtype, B, F, T)
+
+
+def online_xband_ws_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
+    return _online_train_bytes(lib, "nbss_online_xband_ws_bytes", dtype, B, F, T)
+
+
+def _online_xband_check(what: str, tensors: List[Tensor], F: int):
+    """the entry points take bare pointers: the 18 tensors must have the sizes the kernels will read / write"""
+    want = [96, 96, 96 * 12 * 5, 96, 96, 96, 96, 8 * 96, 8, 8 * F * F, 8 * F, 96 * 8, 96, 96, 96, 96 * 12 * 5, 96, 96]
+    if len(tensors) != 18 or any(t is None or t.numel() != n for t, n in zip(tensors, want)):
+        raise NbssError(f"online cross-band: {what} must be the 18 tensors of fconv1, norm_full, squeeze, full, unsqueeze, fconv2 for {F} frequencies "
+                        f"(got sizes {[None if t is None else t.numel() for t in tensors]})")
+
+
+_XBAND_WS: Dict[tuple, Tensor] = {}
+
+
+def online_xband_ws(lib: Lib, x: Tensor) -> Tensor:
+    """the workspace of the cross-band entry points for the shape of x: ONE buffer per (library, device, dtype, shape), shared by every layer and by both
+    directions (its largest part is the reused backward kernels' workspace, ~0.9 GB at batch 4 in fp32; the calls are in order on one stream and each
+    writes what it reads).  A new shape on the same device and dtype replaces the old buffer."""
+    dt, B, F, T = _online_train_dims(x)
+    slot, shape = (id(lib), x.device, dt), (B, F, T)
+    have = _XBAND_WS.get(slot)
+    if have is None or have[0] != shape:
+        _XBAND_WS.pop(slot, None)  # (free the old shape's buffer before the new one is allocated)
+        have = _XBAND_WS[slot] = (shape, scratch(online_xband_ws_bytes(lib, dt, B, F, T), x.device))
+    return have[1]
+
+
+def online_xband_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True, ws: Optional[Tensor] = None):
+    """y = the cross-band trio (x + fconv1, + full, + fconv2) on x [B,F,T,96] (fp32 or bf16); params: the 18 fp32 tensors in state_dict order.
+    -> (y, save): `save` (the inputs of the second and third block) is what online_xband_train_bwd needs (None with keep=False: inference)"""
+    dt, B, F, T = _online_train_dims(x)
+    _online_xband_check("params", params, F)
+    y = torch.empty_like(x)
+    save = scratch(online_xband_save_bytes(lib, dt, B, F, T), x.device) if keep else None
+    ws = online_xband_ws(lib, x) if ws is None else ws
+    lib.call("nbss_online_xband_train_fwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save),
+             _ptr(lib, ws), _stream(lib, x))
+    return y, save
+
+
+def online_xband_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None,
+                           ws: Optional[Tensor] = None):
+    """-> (dx, grads): dx includes the residual paths; the 18 fp32 parameter gradients are WRITTEN into `grads` (uninitialised buffers of the parameters'
+    shapes when not given)"""
+    dt, B, F, T = _online_train_dims(x)
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise NbssError(f"online cross-band: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    _online_xband_check("params", params, F)
+    if grads is None:
+        grads = [torch.empty_like(p) for p in params]
+    _online_xband_check("grads", grads, F)
+    dx = torch.empty_like(x)
+    ws = online_xband_ws(lib, x) if ws is None else ws
+    lib.call("nbss_online_xband_train_bwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
+             _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, x))
+    return dx, grads

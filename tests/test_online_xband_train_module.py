@@ -1,0 +1,280 @@
+"""The native cross-band trio inside models.arch.OnlineSpatialNet (nbss_amd/online_train.py: xband_*, OnlineXBandFn): the switch NBSS_ONLINE_NATIVE_XBAND,
+the autograd Function in the graph, every p.grad of a 2-layer model — the LinearGroup shared by both layers included — against the switch-off run in fp64 on
+the CPU (the project's fp32 bars: output <= 2e-5, gradients <= 1e-4 rel-L2), the refusals, and one `TrainCLI fit` on the device.  F 17 puts one bin in the
+second frequency tile; T 7 leaves the last workgroup of every frames-per-workgroup grid part empty."""
+import copy
+import re
+import warnings
+from pathlib import Path
+
+import pytest
+import torch
+
+from nbss_amd import online_train, ops
+from util import rel_l2
+
+ROOT = Path(__file__).resolve().parent.parent
+FWD_TOL, GRAD_TOL = 2e-5, 1e-4
+BF16_FWD_TOL, BF16_FCONV_TOL, BF16_TOL = 1.5e-2, 5e-2, 3e-2  # tests/test_online_xband_train.py
+F, T = 17, 7
+NODE = "OnlineXBandFnBackward"
+SWITCHES = ("NBSS_ONLINE_NATIVE_XBAND", "NBSS_ONLINE_NATIVE_TRAIN", "NBSS_ONLINE_NATIVE_RET")
+
+
+def _net(**kw):
+    from models.arch.OnlineSpatialNet import OnlineSpatialNet
+    torch.manual_seed(23)
+    args = dict(dim_input=4, dim_output=4, num_layers=2, dim_squeeze=8, num_freqs=F, dim_hidden=96, dim_ffn=192, num_heads=4, attention="ret(2)", full_share=0)
+    args.update(kw)
+    net = OnlineSpatialNet(**args).train()
+    with torch.no_grad():
+        for p in net.parameters():
+            if p.dim() == 1:
+                p.add_(0.2 * torch.randn_like(p))
+    return net
+
+
+def _grad_fns(t):
+    """names of every node of the autograd graph behind t"""
+    seen, todo, names = set(), [t.grad_fn], set()
+    while todo:
+        f = todo.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        names.add(type(f).__name__)
+        todo += [g for g, _ in f.next_functions]
+    return names
+
+
+def _all_off(monkeypatch):
+    for s in SWITCHES:
+        monkeypatch.delenv(s, raising=False)
+
+
+@pytest.fixture(scope="module", params=["ret(2)", "mhsa(5)"])
+def reference(request):
+    """the switch-off run in fp64 on the CPU: computed once per attention"""
+    net = _net(attention=request.param)
+    assert net.layers[1].full is net.layers[0].full  # full_share = 0: one LinearGroup for both layers
+    x, r = torch.randn(2, F, T, 4), torch.randn(2, F, T, 4)
+    n64 = copy.deepcopy(net).double()
+    y = n64(x.double())
+    (y * r.double()).sum().backward()
+    return net, x, r, y.detach(), {k: p.grad for k, p in n64.named_parameters()}
+
+
+def _check_against(net, y, wy, wg):
+    ey = rel_l2(y.detach().cpu(), wy)
+    errs = {k: rel_l2(p.grad.cpu(), wg[k]) for k, p in net.named_parameters()}
+    print(f"y {ey:.1e}; worst grad {max(errs, key=errs.get)} {max(errs.values()):.1e}; layers.0.full.weight {errs['layers.0.full.weight']:.1e}")
+    assert set(errs) == set(wg) and ey <= FWD_TOL, ey
+    assert max(errs.values()) <= GRAD_TOL, {k: v for k, v in errs.items() if v > GRAD_TOL}
+
+
+def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch):
+    net, x, r, wy, wg = reference
+    net = copy.deepcopy(net).to(backend.device)
+    xd, rd = x.to(backend.device), r.to(backend.device)
+    _all_off(monkeypatch)
+    with online_train.use_lib(backend.lib):
+        assert NODE not in _grad_fns(net(xd))  # off by default
+        monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+        y = net(xd)
+        names = _grad_fns(y)
+        assert NODE in names and "OnlineTConvFFNFnBackward" not in names and "OnlineRetentionFnBackward" not in names  # independent of the other two
+        (y * rd).sum().backward()
+        with pytest.raises(RuntimeError, match="second time|retain_graph"):
+            (y * rd).sum().backward()
+        with torch.no_grad():  # inference obeys the same switch: the forward entry alone, nothing kept
+            y_inf = net(xd)
+    assert torch.equal(y_inf, y.detach())
+    _check_against(net, y, wy, wg)
+
+
+def test_all_three_switches_together(backend, reference, monkeypatch):
+    net, x, r, wy, wg = reference
+    if net.pos is None:  # (the retention switch has nothing to take in the mhsa model: the other two still run)
+        want = {NODE, "OnlineTConvFFNFnBackward"}
+    else:
+        want = {NODE, "OnlineTConvFFNFnBackward", "OnlineRetentionFnBackward"}
+    net = copy.deepcopy(net).to(backend.device)
+    xd, rd = x.to(backend.device), r.to(backend.device)
+    for s in SWITCHES:
+        monkeypatch.setenv(s, "1")
+    with online_train.use_lib(backend.lib), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)  # (mhsa model: the retention switch names its reason)
+        y = net(xd)
+        assert want <= _grad_fns(y)
+        (y * rd).sum().backward()
+    _check_against(net, y, wy, wg)
+
+
+def test_in_place_parameter_update_between_forward_and_backward_is_refused(backend, monkeypatch):
+    net = _net(num_layers=1).to(backend.device)
+    x = torch.randn(1, F, 3, 4, device=backend.device)
+    monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+    with online_train.use_lib(backend.lib):
+        y = net(x)
+        with torch.no_grad():
+            net.layers[0].squeeze[0].bias.add_(1.0)
+        with pytest.raises(RuntimeError, match="modified in place"):
+            y.sum().backward()
+
+
+@pytest.mark.parametrize("kw,reason", [(dict(dropout=(0, 0, 0.1)), "dropout"), (dict(norms=("LN", "LN", "GN", "GN", "LN", "LN")), r"norms\[3\] must be LN"),
+                                       (dict(dim_hidden=192), "dim_hidden must be 96"), (dict(dim_squeeze=16), "dim_squeeze must be 8")],
+                         ids=["dropout_full", "GN", "dim_hidden", "dim_squeeze"])
+def test_unsupported_layer_warns_once_and_runs_torch(backend, monkeypatch, kw, reason):
+    net = _net(attention="mhsa(5)", **kw).eval().to(backend.device)  # (eval: the dropout draws nothing, the two runs can be compared)
+    assert re.search(reason, online_train.xband_supported(net.layers[0]))
+    x = torch.randn(1, F, 4, 4, device=backend.device)
+    _all_off(monkeypatch)
+    with online_train.use_lib(backend.lib):
+        y_off = net(x)
+        monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+        with pytest.warns(RuntimeWarning, match=reason):
+            y = net(x)
+        with warnings.catch_warnings():
+            warnings.simplefilter("error", RuntimeWarning)  # once per module and reason
+            y2 = net(x)
+    assert NODE not in _grad_fns(y) and torch.equal(y, y_off) and torch.equal(y, y2)
+
+
+def test_supported_says_why():
+    from models.arch.OnlineSpatialNet import SpatialNetLayer
+    from models.arch.base.linear_group import LinearGroup
+
+    def layer(**kw):
+        args = dict(dim_hidden=96, dim_ffn=192, dim_squeeze=8, num_freqs=5, num_heads=4, attention="mhsa(5)")
+        args.update(kw)
+        return SpatialNetLayer(**args)
+
+    assert online_train.xband_supported(layer()) is None
+    assert len(online_train.xband_params(layer())) == 18
+    assert "padding" in online_train.xband_supported(layer(padding="reflect"))
+    assert "groups" in online_train.xband_supported(layer(conv_groups=(4, 8)))
+    assert "kernel size" in online_train.xband_supported(layer(kernel_size=(3, 3)))
+    assert "norms[5]" in online_train.xband_supported(layer(norms=("LN", "LN", "GN", "LN", "LN", "GN")))
+    assert "norms[4]" in online_train.xband_supported(layer(norms=("LN", "LN", "GN", "LN", "GN", "LN")))
+    lay = layer()
+    lay.fconv2[0].eps = 1e-6
+    assert "eps" in online_train.xband_supported(lay)
+    lay = layer()
+    lay.fconv1[2] = torch.nn.PReLU(1)
+    assert "PReLU" in online_train.xband_supported(lay)
+    assert "bias" in online_train.xband_supported(layer(full=LinearGroup(5, 5, 8, bias=False)))
+
+
+def test_streaming_call_never_takes_the_native_blocks(backend, monkeypatch):
+    net = _net(attention="mhsa(5)").to(backend.device)
+    x = torch.randn(1, F, 8, 4, device=backend.device)
+    monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+    with online_train.use_lib(backend.lib):
+        assert online_train.xband_eligible(net.layers[0], torch.zeros(1, F, 8, 96, device=backend.device), {}) == "streaming call"
+        assert online_train.xband_eligible(net.layers[0], torch.zeros(1, F, 8, 96, device=backend.device), None) is None
+        st = net.init_stream(1, device=backend.device)
+        y = torch.cat([net.forward_stream(x[:, :, :4], st), net.forward_stream(x[:, :, 4:], st)], 2)
+        assert NODE not in _grad_fns(y)
+        whole = net(x)
+    assert NODE in _grad_fns(whole)
+    assert rel_l2(y.detach(), whole.detach()) < 1e-4  # (the streamed frames are the whole-utterance ones)
+
+
+def test_wrong_dtype_or_device_goes_to_torch(backend, monkeypatch):
+    net = _net(num_layers=1)
+    monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+    lay = net.layers[0]
+    assert online_train.xband_eligible(lay, torch.zeros(1, F, 4, 96), None) == "not on a HIP device"  # (no override: a CPU tensor)
+    with online_train.use_lib(backend.lib):
+        other = torch.zeros(1, F, 4, 96, device="cpu" if backend.device.type != "cpu" else "meta")
+        assert online_train.xband_eligible(lay, other, None) == "no library for the tensor's device"
+        x64 = torch.zeros(1, F, 4, 96, dtype=torch.float64, device=backend.device)
+        assert online_train.xband_eligible(lay, x64, None).startswith("!the stream must be fp32")
+        assert online_train.xband_eligible(lay, torch.zeros(1, F + 1, 4, 96, device=backend.device), None).startswith("!the input has")
+
+
+def test_257_frames_fall_back_with_gradients_and_run_natively_without(backend, monkeypatch):
+    net = _net(num_layers=1, attention="mhsa(5)").to(backend.device)
+    x = torch.randn(1, F, 257, 4, device=backend.device)
+    _all_off(monkeypatch)
+    calls = []
+    orig = ops.online_xband_train_fwd
+    monkeypatch.setattr(ops, "online_xband_train_fwd", lambda *a, **k: (calls.append(k.get("keep")), orig(*a, **k))[1])
+    with online_train.use_lib(backend.lib):
+        with torch.no_grad():
+            y_off = net(x)
+        monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+        with pytest.warns(RuntimeWarning, match="with gradients T <= 256"):
+            y = net(x)
+        assert NODE not in _grad_fns(y) and not calls
+        # (torch's own modules both times, but not the same kernels with and without autograd on the device: fp32 against fp32, the forward bar)
+        assert rel_l2(y.detach(), y_off) <= FWD_TOL
+        with torch.no_grad(), warnings.catch_warnings():
+            warnings.simplefilter("error", RuntimeWarning)
+            y_inf = net(x)
+    assert calls == [False]  # the forward entry alone, nothing kept
+    assert rel_l2(y_inf, y_off) <= FWD_TOL
+
+
+def test_bf16_autocast(backend, monkeypatch):
+    """under bf16 autocast the stream is bf16 and the result has the caller's dtype; bars of tests/test_online_xband_train.py"""
+    _all_off(monkeypatch)
+    net = _net(num_layers=1)
+    lay = net.layers[0]
+    g = torch.Generator().manual_seed(5)
+    x, r = torch.randn(2, F, T, 96, generator=g).bfloat16().float(), (0.5 * torch.randn(2, F, T, 96, generator=g)).bfloat16().float()
+    l64 = copy.deepcopy(lay).double()
+    x64 = x.double().requires_grad_(True)
+    (l64._xband(x64) * r.double()).sum().backward()
+    wy = l64._xband(x64).detach()
+    lay = copy.deepcopy(lay).to(backend.device)
+    xd = x.to(backend.device).requires_grad_(True)
+    monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+    with online_train.use_lib(backend.lib), torch.autocast(backend.device.type, dtype=torch.bfloat16):
+        y = lay._xband(xd)
+        assert y.dtype == torch.float32 and NODE in _grad_fns(y)
+        with torch.no_grad():
+            assert lay._xband(xd).dtype == torch.float32
+    (y * r.to(backend.device)).sum().backward()
+    assert xd.grad.dtype == torch.float32
+    errs = {"y": rel_l2(y.detach().cpu(), wy), "dx": rel_l2(xd.grad.cpu(), x64.grad)}
+    want = dict(zip(online_train.XBAND_SLOTS, online_train.xband_params(l64)))
+    for slot, p in zip(online_train.XBAND_SLOTS, online_train.xband_params(lay)):
+        assert p.grad.dtype == torch.float32
+        errs[".".join(str(s) for s in slot if s is not None)] = rel_l2(p.grad.cpu(), want[slot].grad)
+    print(" ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    bars = {k: BF16_FWD_TOL if k == "y" else BF16_FCONV_TOL if k.startswith("fconv") else BF16_TOL for k in errs}
+    assert not {k: v for k, v in errs.items() if not v <= bars[k]}, errs
+
+
+@pytest.mark.gpu
+def test_fit_on_the_device_with_the_switch(monkeypatch):
+    """TrainCLI fit, configs/onlineSpatialNet.yaml, synthetic data, 2 layers, 1-s segments, two epochs of two steps: the first step's loss is the switch-off
+    run's to 1e-4 relative, and the loss decreases"""
+    import SharedTrainer
+    from SharedTrainer import TrainCLI
+    argv = ["fit", "--config", str(ROOT / "configs" / "onlineSpatialNet.yaml"), "--config", str(ROOT / "configs" / "datasets" / "synthetic.yaml"),
+            "--model.arch.dim_input=12", "--model.arch.dim_output=4", "--model.arch.num_freqs=129", "--model.arch.num_layers=2", "--data.num_samples=[4,2,2]",
+            "--data.audio_time_len=[1.0,1.0,1.0]", "--data.batch_size=[2,1]", "--trainer.max_epochs=2"]
+    steps = []
+    orig = SharedTrainer.TrainModule.training_step
+
+    def recording(self, *a, **k):
+        loss = orig(self, *a, **k)
+        steps.append((float(loss.detach()), NODE in _grad_fns(loss)))
+        return loss
+
+    monkeypatch.setattr(SharedTrainer.TrainModule, "training_step", recording)
+    _all_off(monkeypatch)
+    TrainCLI(argv=argv)
+    off, steps[:] = list(steps), []
+    monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
+    log = TrainCLI(argv=argv).result["log"]
+    on = list(steps)
+    print("switch off:", off, "\nswitch on: ", on)
+    assert len(log) == 2 and len(on) == len(off) == 4 and log[0]["device"].startswith("cuda")
+    assert not any(n for _, n in off) and all(n for _, n in on)
+    assert abs(on[0][0] - off[0][0]) <= 1e-4 * abs(off[0][0]), (on[0], off[0])
+    key = next(k for k in log[0] if k.startswith("train/"))
+    assert log[1][key] < log[0][key], log

@@ -1,7 +1,8 @@
-"""One OnlineSpatialNet training step (forward + backward + AdamW) of the shipped 8-layer configs/onlineSpatialNet.yaml model in three settings in the same
-process — every switch off, the native T-ConvFFN (NBSS_ONLINE_NATIVE_TRAIN), and the native T-ConvFFN + the native retention core (NBSS_ONLINE_NATIVE_RET) —
-then the T-ConvFFN block alone against the module's `_tconvffn` and the retention block alone (`layer._tsa`: LayerNorm, projections, retention, out_proj)
-against the module's MultiScaleRetention, each forward and forward + backward.
+"""One OnlineSpatialNet training step (forward + backward + AdamW) of the shipped 8-layer configs/onlineSpatialNet.yaml model in four settings in the same
+process — every switch off, the native T-ConvFFN (NBSS_ONLINE_NATIVE_TRAIN), the native T-ConvFFN + the native retention core (NBSS_ONLINE_NATIVE_RET), and
+those two + the native cross-band trio (NBSS_ONLINE_NATIVE_XBAND) — then the T-ConvFFN block alone against the module's `_tconvffn`, the retention block
+alone (`layer._tsa`: LayerNorm, projections, retention, out_proj) against the module's MultiScaleRetention, and the cross-band trio alone (`layer._xband`:
+fconv1, full-band, fconv2 with their residuals) against the module's `_fconv` / `_full` chain, each forward and forward + backward.
 
     python tools/online_train_bench.py [--batches 2 4] [--seconds 4] [--steps 10] [--warmup 3] [--layers 8]
 
@@ -34,9 +35,10 @@ def _timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps, torch.cuda.max_memory_allocated() / 2 ** 20
 
 
-def _switch(on, ret=False):
+def _switch(on, ret=False, xband=False):
     os.environ["NBSS_ONLINE_NATIVE_TRAIN"] = "1" if on else "0"
     os.environ["NBSS_ONLINE_NATIVE_RET"] = "1" if ret else "0"
+    os.environ["NBSS_ONLINE_NATIVE_XBAND"] = "1" if xband else "0"
 
 
 def main():
@@ -67,14 +69,16 @@ def main():
                 opt.step()
             res = {}
             for _ in range(a.rounds):
-                for k, on, ret in (("off", False, False), ("on", True, False), ("on_ret", True, True)):
-                    _switch(on, ret)
+                for k, on, ret, xb in (("off", False, False, False), ("on", True, False, False), ("on_ret", True, True, False), ("on_ret_xband", True, True, True)):
+                    _switch(on, ret, xb)
                     ms, mb = _timed(step, a.steps, a.warmup)
                     res[k] = (min(ms, res[k][0]), max(mb, res[k][1])) if k in res else (ms, mb)
             print(json.dumps({"what": "train step", "layers": a.layers, "B": B, "T": T, "precision": prec, "rounds": a.rounds, "off_ms": round(res["off"][0], 2),
-                              "on_ms": round(res["on"][0], 2), "on_ret_ms": round(res["on_ret"][0], 2), "off_over_on": round(res["off"][0] / res["on"][0], 3),
-                              "on_over_on_ret": round(res["on"][0] / res["on_ret"][0], 3), "off_peak_MiB": round(res["off"][1]),
-                              "on_peak_MiB": round(res["on"][1]), "on_ret_peak_MiB": round(res["on_ret"][1])}), flush=True)
+                              "on_ms": round(res["on"][0], 2), "on_ret_ms": round(res["on_ret"][0], 2), "on_ret_xband_ms": round(res["on_ret_xband"][0], 2),
+                              "off_over_on": round(res["off"][0] / res["on"][0], 3), "on_over_on_ret": round(res["on"][0] / res["on_ret"][0], 3),
+                              "on_ret_over_on_ret_xband": round(res["on_ret"][0] / res["on_ret_xband"][0], 3), "off_peak_MiB": round(res["off"][1]),
+                              "on_peak_MiB": round(res["on"][1]), "on_ret_peak_MiB": round(res["on_ret"][1]),
+                              "on_ret_xband_peak_MiB": round(res["on_ret_xband"][1])}), flush=True)
         # the block alone: x + _tconvffn(x), forward and forward + backward
         layer = net.layers[0]
         for prec in ("32", "bf16-mixed"):
@@ -119,6 +123,28 @@ def main():
                 for ret in (False, True):
                     _switch(False, ret)
                     out[f"{name}_{'on' if ret else 'off'}_ms"] = round(_timed(fn, a.steps, a.warmup)[0], 3)
+                out[f"{name}_off_over_on"] = round(out[f"{name}_off_ms"] / out[f"{name}_on_ms"], 3)
+            print(json.dumps(out), flush=True)
+        # the cross-band trio alone: layer._xband (x + fconv1, + full-band, + fconv2), forward and forward + backward
+        for prec in ("32", "bf16-mixed"):
+            h = torch.randn(B, 129, T, 96, device=dev, requires_grad=True)
+            g = torch.randn(B, 129, T, 96, device=dev)
+
+            def fwd():
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    layer._xband(h)
+
+            def fwd_bwd():
+                net.zero_grad(set_to_none=True)
+                h.grad = None
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec != "32"):
+                    y = layer._xband(h)
+                y.backward(g.to(y.dtype))
+            out = {"what": "cross-band trio", "B": B, "T": T, "precision": prec}
+            for name, fn in (("fwd", fwd), ("fwd_bwd", fwd_bwd)):
+                for xb in (False, True):
+                    _switch(False, False, xb)
+                    out[f"{name}_{'on' if xb else 'off'}_ms"] = round(_timed(fn, a.steps, a.warmup)[0], 3)
                 out[f"{name}_off_over_on"] = round(out[f"{name}_off_ms"] / out[f"{name}_on_ms"], 3)
             print(json.dumps(out), flush=True)
 
