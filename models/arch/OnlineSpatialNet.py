@@ -11,7 +11,6 @@ Besides the reference's whole-utterance forward this module offers an explicit s
 chunk shapes a step is a static kernel sequence and can be captured in a HIP graph (`OnlineStreamer`).
 Plain PyTorch (BASELINE config 5)."""
 import math
-import os
 from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
@@ -21,7 +20,6 @@ from torch import Tensor
 from torch.nn import MultiheadAttention
 
 from models.arch.base.linear_group import LinearGroup
-from models.arch.base.native import torch_path_note
 from models.arch.base.norm import new_norm
 from models.arch.base.retention import MultiScaleRetention, RetNetRelPos
 
@@ -105,15 +103,10 @@ class SpatialNetLayer(nn.Module):
         if isinstance(self.mhsa, MultiheadAttention):
             u, attn = self.mhsa(u, u, u, need_weights=bool(getattr(self, "need_weights", False)), average_attn_weights=False, attn_mask=attn_mask)
         elif not inference:
-            # the chunkwise retention core runs through the HIP kernels of nbss_amd/online_train.py, forward and backward, when NBSS_ONLINE_NATIVE_RET=1 (off
-            # by default) and `ret_eligible` accepts the call (else, with the switch on, the module below and one warning that names the reason)
-            why = "off"
-            if os.environ.get("NBSS_ONLINE_NATIVE_RET", "0") == "1":
-                from nbss_amd import online_train
-                why = online_train.ret_eligible(self, u, attn_mask, chunkwise_recurrent, rope, state, inference)
-                if why is not None and why.startswith("!"):
-                    torch_path_note(self, "OnlineSpatialNet retention", why[1:])
-            if why is None:
+            # the chunkwise retention core runs through the HIP kernels of nbss_amd/online_train.py, forward and backward, when the switch of its RETENTION
+            # block is on (off by default) and `take` accepts the call (else, with the switch on, the module below and one warning that names the reason)
+            from nbss_amd import online_train
+            if online_train.take(online_train.RETENTION, self, u, state is not None or inference, attn_mask, chunkwise_recurrent, rope):
                 u = online_train.retention_forward(self.mhsa, u, attn_mask)
             else:
                 u = self.mhsa(u, rel_pos=attn_mask, incremental_state=state, chunkwise_recurrent=chunkwise_recurrent, rope=rope)
@@ -124,15 +117,11 @@ class SpatialNetLayer(nn.Module):
 
     def _tconvffn(self, x: Tensor, state: Dict[int, Any] = None, residual: bool = False) -> Tensor:
         """the block's output, or x + it with `residual`.  The residual form of a whole-utterance call (state is None) runs through the HIP kernels of
-        nbss_amd/online_train.py, forward and backward, when NBSS_ONLINE_NATIVE_TRAIN=1 (off by default), the tensor is on a HIP device and the block has
-        the geometry they are built for (else, with the switch on, the torch.nn modules below and one warning that names the reason)"""
-        if residual and os.environ.get("NBSS_ONLINE_NATIVE_TRAIN", "0") == "1":
-            from nbss_amd import online_train
-            why = online_train.eligible(self, x, state)
-            if why is None:
-                return online_train.tconvffn_residual(self, x)
-            if why.startswith("!"):
-                torch_path_note(self, "OnlineSpatialNet T-ConvFFN", why[1:])
+        nbss_amd/online_train.py, forward and backward, when the switch of its TCONVFFN block is on (off by default), the tensor is on a HIP device and the
+        block has the geometry they are built for (else, with the switch on, the torch.nn modules below and one warning that names the reason)"""
+        from nbss_amd import online_train
+        if residual and online_train.take(online_train.TCONVFFN, self, x, state is not None):
+            return online_train.tconvffn_residual(self, x)
         B, Fq, T, H0 = x.shape
         h = x.transpose(-1, -2).reshape(B * Fq, H0, T)
         for m in self.tconvffn:
@@ -150,15 +139,11 @@ class SpatialNetLayer(nn.Module):
     # ---- cross-band ------------------------------------------------------------------------------------------------------------
     def _xband(self, x: Tensor, state: Dict[int, Any] = None) -> Tensor:
         """x + fconv1, + full-band, + fconv2.  A whole-utterance call (state is None) runs the three blocks as ONE autograd node through the HIP kernels of
-        nbss_amd/online_train.py, forward and backward, when NBSS_ONLINE_NATIVE_XBAND=1 (off by default) and `xband_eligible` accepts the call (else, with
+        nbss_amd/online_train.py, forward and backward, when the switch of its XBAND block is on (off by default) and `take` accepts the call (else, with
         the switch on, the torch.nn modules below and one warning that names the reason)"""
-        if os.environ.get("NBSS_ONLINE_NATIVE_XBAND", "0") == "1":
-            from nbss_amd import online_train
-            why = online_train.xband_eligible(self, x, state)
-            if why is None:
-                return online_train.xband_residual(self, x)
-            if why.startswith("!"):
-                torch_path_note(self, "OnlineSpatialNet cross-band blocks", why[1:])
+        from nbss_amd import online_train
+        if online_train.take(online_train.XBAND, self, x, state is not None):
+            return online_train.xband_residual(self, x)
         x = x + self._fconv(self.fconv1, x)
         x = x + self._full(x)
         return x + self._fconv(self.fconv2, x)

@@ -28,10 +28,10 @@ def native_runner(module, where: str, cls: str):
     return NATIVE[module]
 
 
-def torch_path_note(module, label: str, why: str) -> None:
+def torch_path_note(module, label: str, why: str, stacklevel: int = 3) -> None:
     """one warning per module and reason: a user on a HIP device can tell which path ran.  To be called from the module's forward(): the warning points
-    at the frame that called forward()."""
+    at the frame that called forward() (a helper between forward() and this call adds one to `stacklevel`)."""
     seen = _NOTED.setdefault(module, set())
     if why not in seen:
         seen.add(why)
-        warnings.warn(f"{label}: torch.nn path instead of the native HIP kernels ({why})", RuntimeWarning, stacklevel=3)
+        warnings.warn(f"{label}: torch.nn path instead of the native HIP kernels ({why})", RuntimeWarning, stacklevel=stacklevel)

@@ -1,23 +1,24 @@
-"""Native training path of the OnlineSpatialNet's causal T-ConvFFN (csrc/online_train.hip: nbss_online_tconvffn_train_fwd / _bwd): LayerNorm -> 1x1 ->
-SiLU -> causal grouped conv -> SiLU -> causal grouped conv -> GroupNorm of each frame over (24 channels x all frequencies) -> SiLU -> causal grouped conv
--> SiLU -> 1x1 -> + x, on the whole [B,F,T,96] stream in fp32 or bf16, with every parameter gradient from the HIP backward.
+"""Native training paths of the OnlineSpatialNet's three blocks, each behind an opt-in switch of its own (off unless exactly '1', read at call time,
+independent of the others):
 
-`models.arch.OnlineSpatialNet.SpatialNetLayer._tconvffn` takes it when NBSS_ONLINE_NATIVE_TRAIN=1 (off by default), the tensor is on a HIP device, the call
-is not a streaming one, `supported(layer)` is None and the stream is fp32 (or autocast to bf16); attention and the cross-band blocks have switches of
-their own (below).
+    TCONVFFN   NBSS_ONLINE_NATIVE_TRAIN   csrc/online_train.hip        x + causal T-ConvFFN(x) on the [B,F,T,96] stream        OnlineTConvFFNFn
+    RETENTION  NBSS_ONLINE_NATIVE_RET     csrc/online_ret_train.hip    the chunkwise retention core between the projections    OnlineRetentionFn
+    XBAND      NBSS_ONLINE_NATIVE_XBAND   csrc/online_xband_train.hip  x + fconv1, + full-band, + fconv2 as one node           OnlineXBandFn
 
-The chunkwise retention core (csrc/online_ret_train.hip: nbss_online_ret_train_fwd / _bwd) has a switch of its own, NBSS_ONLINE_NATIVE_RET=1 (off by default,
-independent of the one above): `SpatialNetLayer._tsa` then runs the module's four projections and out_proj as its own nn.Linear's around
-`OnlineRetentionFn`, which replaces MultiScaleRetention.chunk_recurrent_forward, the per-head RMSNorm and the SiLU gate (`ret_eligible` says when).
-
-The cross-band trio (csrc/online_xband_train.hip: nbss_online_xband_train_fwd / _bwd) has the third switch, NBSS_ONLINE_NATIVE_XBAND=1 (off by default, independent
-of the other two): `SpatialNetLayer._xband` then evaluates x + fconv1, + full-band, + fconv2 as one `OnlineXBandFn` node on SpatialNet-small's F-conv and full-band
-kernels (`xband_eligible` says when).  With all three on, what stays torch.nn in a training layer is the LayerNorm and the linear projections around retention."""
+A block is one `Block` record: its switch, its label, its `supported` and the checks of the call.  Everything else is written once.  `take` is what
+`models.arch.OnlineSpatialNet.SpatialNetLayer` asks per call: the common gate (`_gate`: switch, streaming call, device, library, geometry, stream dtype — fp32,
+or bf16 under autocast), then the block's checks, then one warning when the switch is on and the layer or call does not fit (a reason that starts with '!');
+every other refusal is an ordinary torch.nn case.  The two blocks of the form y = x + block(x) with N parameter inputs share one autograd Function body
+(`_residual_fn`) and one driver (`_residual`); retention has inputs of its own (q, k, v, g) and keeps its Function, with the module's nn.Linear projections
+around it.  Without autograd (no_grad, or nothing requires a gradient) the forward entry runs alone under no_grad and keeps nothing.  With all three switches
+on, what stays torch.nn in a training layer is the LayerNorm and the linear projections around retention."""
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import Callable, List, Optional
 
 import torch
 from torch import Tensor
@@ -25,21 +26,24 @@ from torch import Tensor
 from . import ops
 from ._lib import Lib, hip
 
+TCONVFFN_T_MAX, TCONVFFN_F_MAX = 4096, 272
+RET_CHUNK, RET_T_MAX = 64, 4096
+XBAND_F_MAX, XBAND_T_MAX, XBAND_T_TRAIN_MAX, XBAND_F_TRAIN_MAX_FP32 = 272, 4096, 256, 160
 # (module index in layer.tconvffn, attribute) in the order of the C ABI's parameter list
 PARAM_SLOTS = ((0, "weight"), (0, "bias"), (1, "weight"), (1, "bias"), (3, "weight"), (3, "bias"), (5, "weight"), (5, "bias"), (6, "weight"), (6, "bias"),
                (8, "weight"), (8, "bias"), (10, "weight"), (10, "bias"))
+# (attribute path, tensor) in the order of the C ABI's parameter list = state_dict order
+XBAND_SLOTS = (("fconv1", 0, "weight"), ("fconv1", 0, "bias"), ("fconv1", 1, "weight"), ("fconv1", 1, "bias"), ("fconv1", 2, "weight"),
+               ("norm_full", None, "weight"), ("norm_full", None, "bias"), ("squeeze", 0, "weight"), ("squeeze", 0, "bias"), ("full", None, "weight"),
+               ("full", None, "bias"), ("unsqueeze", 0, "weight"), ("unsqueeze", 0, "bias"),
+               ("fconv2", 0, "weight"), ("fconv2", 0, "bias"), ("fconv2", 1, "weight"), ("fconv2", 1, "bias"), ("fconv2", 2, "weight"))
 
 _LIB_OVERRIDE: Optional[Lib] = None
 
 
-def enabled() -> bool:
-    """the switch, read at call time (like NBSS_NBC2_NATIVE); off unless it is exactly '1'"""
-    return os.environ.get("NBSS_ONLINE_NATIVE_TRAIN", "0") == "1"
-
-
 @contextlib.contextmanager
 def use_lib(lib: Lib):
-    """tests only: run the block through `lib` — the host-emulator build takes CPU tensors, so the module path can be exercised without a device"""
+    """tests only: run the blocks through `lib` — the host-emulator build takes CPU tensors, so the module path can be exercised without a device"""
     global _LIB_OVERRIDE
     prev, _LIB_OVERRIDE = _LIB_OVERRIDE, lib
     try:
@@ -55,11 +59,7 @@ def active_lib(x: Tensor) -> Optional[Lib]:
     return hip() if x.is_cuda else None
 
 
-def tconvffn_params(layer) -> List[Tensor]:
-    """the block's 14 parameters (the module's live tensors) in the order of the C ABI"""
-    return [getattr(layer.tconvffn[i], a) for i, a in PARAM_SLOTS]
-
-
+# ---- what the kernels are built for ------------------------------------------------------------------------------------------------------------------------
 def supported(layer) -> Optional[str]:
     """None when the layer's T-ConvFFN is the geometry the kernels are built for (the checks of nbss_amd/online.py::supported that concern this block),
     else the reason"""
@@ -93,87 +93,6 @@ def supported(layer) -> Optional[str]:
     return None
 
 
-def _kernel_params(params) -> List[Tensor]:
-    """fp32, contiguous, the 1x1 weights as matrices (views where the module's tensors already are all that)"""
-    return [(p.detach()[:, :, 0] if (i in (2, 12)) else p.detach()).float().contiguous() for i, p in enumerate(params)]
-
-
-class OnlineTConvFFNFn(torch.autograd.Function):
-    """y = x + T-ConvFFN(x) through the HIP kernels; inputs (lib, x, *the 14 parameters): the parameters are inputs of the node, so p.grad is populated the
-    usual way.  One backward per forward: the saved activations are freed by it (retain_graph and double backward are refused)."""
-
-    @staticmethod
-    def forward(ctx, lib, x, *params):
-        xk = x.contiguous()
-        p32 = _kernel_params(params)
-        y, save = ops.online_tconvffn_train_fwd(lib, p32, xk, keep=True)
-        ctx.lib, ctx.saved, ctx.params = lib, (xk, save, p32), params
-        ctx.versions = [p._version for p in params]
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        ops.graph_guard_check(ctx, "OnlineSpatialNet native T-ConvFFN")
-        xk, save, p32 = ctx.saved
-        dx, grads = ops.online_tconvffn_train_bwd(ctx.lib, p32, xk, save, dy.contiguous())
-        ctx.saved = None
-        out = [g.reshape(p.shape).to(p.dtype) if ctx.needs_input_grad[2 + i] else None for i, (g, p) in enumerate(zip(grads, ctx.params))]
-        return (None, dx if ctx.needs_input_grad[1] else None, *out)
-
-
-def eligible(layer, x: Tensor, state) -> Optional[str]:
-    """None when this call takes the native block; else why not.  A reason that starts with '!' is worth a warning (the switch is on, the tensor is on the
-    library's device, and the layer or dtype does not fit); the others are the ordinary torch.nn cases."""
-    if not enabled():
-        return "NBSS_ONLINE_NATIVE_TRAIN is not 1"
-    if state is not None:
-        return "streaming call"
-    if _LIB_OVERRIDE is None and not x.is_cuda:
-        return "not on a HIP device"
-    why = supported(layer)
-    if why is not None:
-        return "!" + why
-    if x.dim() != 4 or x.shape[-1] != 96:
-        return f"!input must be [B,F,T,96], got {tuple(x.shape)}"
-    if x.dtype != torch.float32 and _stream_dtype(x) is None:
-        return f"!the stream must be fp32, or bf16 under autocast (got {x.dtype})"
-    if not 1 <= x.shape[2] <= 4096 or x.shape[1] > 272:
-        return f"!1 <= T <= 4096 and F <= 272 (got T = {x.shape[2]}, F = {x.shape[1]})"
-    return None
-
-
-def _stream_dtype(x: Tensor) -> Optional[torch.dtype]:
-    dev = "cuda" if x.is_cuda else "cpu"
-    if torch.is_autocast_enabled(dev):
-        return torch.bfloat16 if torch.get_autocast_dtype(dev) == torch.bfloat16 else None
-    return torch.float32 if x.dtype == torch.float32 else None
-
-
-def tconvffn_residual(layer, x: Tensor) -> Tensor:
-    """x + T-ConvFFN(x) for a call `eligible` accepted; in the dtype of x.  Without autograd (no_grad, or nothing requires a gradient) the forward runs alone
-    and keeps nothing."""
-    lib = active_lib(x)
-    if lib is None:
-        raise ops.NbssError("OnlineSpatialNet native T-ConvFFN: no library for a tensor on " + str(x.device))
-    params = tconvffn_params(layer)
-    xs = x.to(_stream_dtype(x))
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        y = OnlineTConvFFNFn.apply(lib, xs, *params)
-    else:
-        y = ops.online_tconvffn_train_fwd(lib, _kernel_params(params), xs.contiguous(), keep=False)[0]
-    return y.to(x.dtype)
-
-
-# ---- the retention core (NBSS_ONLINE_NATIVE_RET) ---------------------------------------------------------------------------------------------------------
-RET_CHUNK, RET_T_MAX = 64, 4096
-
-
-def ret_enabled() -> bool:
-    """the retention switch, read at call time; off unless it is exactly '1'"""
-    return os.environ.get("NBSS_ONLINE_NATIVE_RET", "0") == "1"
-
-
 def ret_supported(mhsa) -> Optional[str]:
     """None when the module is the retention the kernels are built for, else the reason"""
     if type(mhsa).__name__ != "MultiScaleRetention":
@@ -189,99 +108,6 @@ def ret_supported(mhsa) -> Optional[str]:
     if mhsa.group_norm.weight is not None or mhsa.group_norm.eps != 1e-6:
         return "the head norm must be RMSNorm(eps=1e-6) without affine"
     return None
-
-
-def ret_eligible(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope, state, inference: bool) -> Optional[str]:
-    """None when this call of `_tsa` takes the native retention core; else why not, with the conventions of `eligible` (a leading '!': worth a warning)"""
-    if not ret_enabled():
-        return "NBSS_ONLINE_NATIVE_RET is not 1"
-    if state is not None or inference:
-        return "streaming or recurrent call"
-    if _LIB_OVERRIDE is None and not u.is_cuda:
-        return "not on a HIP device"
-    if active_lib(u) is None:
-        return "no library for the tensor's device"
-    why = ret_supported(layer.mhsa)
-    if why is not None:
-        return "!" + why
-    inner = rel_pos[1] if isinstance(rel_pos, tuple) and len(rel_pos) == 2 else None
-    if not chunkwise_recurrent or not (isinstance(inner, tuple) and inner[0] == "chunk"):
-        return "!only the chunkwise form runs natively"
-    if inner[1] != RET_CHUNK:
-        return f"!the chunk size must be {RET_CHUNK} (got {inner[1]})"
-    if rope is not False:
-        return f"!rope must be False (got {rope!r})"
-    if u.dim() != 3 or u.shape[-1] != 96:
-        return f"!input must be [B F,T,96], got {tuple(u.shape)}"
-    if u.dtype != torch.float32 and _stream_dtype(u) is None:
-        return f"!the stream must be fp32, or bf16 under autocast (got {u.dtype})"
-    if not 1 <= u.shape[1] <= RET_T_MAX:
-        return f"!1 <= T <= {RET_T_MAX} (got T = {u.shape[1]})"
-    return None
-
-
-class OnlineRetentionFn(torch.autograd.Function):
-    """out = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)) through the HIP kernels; inputs (lib, q, k or None, v, g, k_scale, decay).  One
-    backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
-
-    @staticmethod
-    def forward(ctx, lib, q, k, v, g, k_scale, decay):
-        q, v, g = q.contiguous(), v.contiguous(), g.contiguous()
-        k = None if k is None else k.contiguous()
-        out, save = ops.online_ret_train_fwd(lib, q, k, v, g, k_scale, decay, keep=True)
-        ctx.lib, ctx.k_scale, ctx.saved, ctx.params, ctx.versions = lib, k_scale, (q, k, v, g, decay, save), (), []
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_out):
-        ops.graph_guard_check(ctx, "OnlineSpatialNet native retention")
-        q, k, v, g, decay, save = ctx.saved
-        dq, dk, dv, dg = ops.online_ret_train_bwd(ctx.lib, q, k, v, g, ctx.k_scale, decay, save, d_out.contiguous())
-        ctx.saved = None
-        return None, dq, dk, dv, dg, None, None
-
-
-def retention_forward(mhsa, u: Tensor, rel_pos) -> Tensor:
-    """MultiScaleRetention.forward(u, rel_pos, chunkwise_recurrent=True, rope=False) for a call `ret_eligible` accepted: the projections and out_proj are the
-    module's own nn.Linear's (torch GEMMs, autocast like any other), the core between them is native.  Without autograd the forward runs alone and keeps nothing."""
-    lib = active_lib(u)
-    if lib is None:
-        raise ops.NbssError("OnlineSpatialNet native retention: no library for a tensor on " + str(u.device))
-    dt = _stream_dtype(u)
-    q = mhsa.q_proj(u).to(dt)
-    k = None if mhsa.share_qk else mhsa.k_proj(u).to(dt)
-    v, g = mhsa.v_proj(u).to(dt), mhsa.g_proj(u).to(dt)
-    decay = rel_pos[1][2].detach().to(device=u.device, dtype=torch.float32).contiguous()
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, g)):
-        out = OnlineRetentionFn.apply(lib, q, k, v, g, float(mhsa.scaling), decay)
-    else:
-        out = ops.online_ret_train_fwd(lib, q.contiguous(), None if k is None else k.contiguous(), v.contiguous(), g.contiguous(), float(mhsa.scaling), decay,
-                                       keep=False)[0]
-    return mhsa.out_proj(out)
-
-
-# ---- the cross-band trio (NBSS_ONLINE_NATIVE_XBAND) --------------------------------------------------------------------------------------------------------
-XBAND_F_MAX, XBAND_T_MAX, XBAND_T_TRAIN_MAX, XBAND_F_TRAIN_MAX_FP32 = 272, 4096, 256, 160
-# (attribute path, tensor) in the order of the C ABI's parameter list = state_dict order
-XBAND_SLOTS = (("fconv1", 0, "weight"), ("fconv1", 0, "bias"), ("fconv1", 1, "weight"), ("fconv1", 1, "bias"), ("fconv1", 2, "weight"),
-               ("norm_full", None, "weight"), ("norm_full", None, "bias"), ("squeeze", 0, "weight"), ("squeeze", 0, "bias"), ("full", None, "weight"),
-               ("full", None, "bias"), ("unsqueeze", 0, "weight"), ("unsqueeze", 0, "bias"),
-               ("fconv2", 0, "weight"), ("fconv2", 0, "bias"), ("fconv2", 1, "weight"), ("fconv2", 1, "bias"), ("fconv2", 2, "weight"))
-
-
-def xband_enabled() -> bool:
-    """the cross-band switch, read at call time; off unless it is exactly '1'"""
-    return os.environ.get("NBSS_ONLINE_NATIVE_XBAND", "0") == "1"
-
-
-def xband_params(layer) -> List[Tensor]:
-    """the trio's 18 parameters (the module's live tensors; a LinearGroup shared across layers is the same tensor in each) in the order of the C ABI"""
-    out = []
-    for name, i, a in XBAND_SLOTS:
-        m = getattr(layer, name)
-        out.append(getattr(m if i is None else m[i], a, None))
-    return out
 
 
 def xband_supported(layer) -> Optional[str]:
@@ -325,80 +151,242 @@ def xband_supported(layer) -> Optional[str]:
     return None
 
 
-def xband_eligible(layer, x: Tensor, state) -> Optional[str]:
-    """None when this call of `SpatialNetLayer.forward` takes the native cross-band trio; else why not, with the conventions of `eligible` (a leading '!':
-    worth a warning)"""
-    if not xband_enabled():
-        return "NBSS_ONLINE_NATIVE_XBAND is not 1"
-    if state is not None:
-        return "streaming call"
-    if _LIB_OVERRIDE is None and not x.is_cuda:
-        return "not on a HIP device"
-    if active_lib(x) is None:
-        return "no library for the tensor's device"
-    why = xband_supported(layer)
-    if why is not None:
-        return "!" + why
+def tconvffn_params(layer) -> List[Tensor]:
+    """the block's 14 parameters (the module's live tensors) in the order of the C ABI"""
+    return [getattr(layer.tconvffn[i], a) for i, a in PARAM_SLOTS]
+
+
+def xband_params(layer) -> List[Tensor]:
+    """the trio's 18 parameters (the module's live tensors; a LinearGroup shared across layers is the same tensor in each) in the order of the C ABI"""
+    out = []
+    for name, i, a in XBAND_SLOTS:
+        m = getattr(layer, name)
+        out.append(getattr(m if i is None else m[i], a, None))
+    return out
+
+
+# ---- the checks of one call, after the common gate (a reason starts with '!': the switch is on and the call does not fit) ---------------------------------
+def _tconvffn_call(layer, x: Tensor) -> Optional[str]:
     if x.dim() != 4 or x.shape[-1] != 96:
         return f"!input must be [B,F,T,96], got {tuple(x.shape)}"
-    dt = _stream_dtype(x)
-    if dt is None:
-        return f"!the stream must be fp32, or bf16 under autocast (got {x.dtype})"
+    if not 1 <= x.shape[2] <= TCONVFFN_T_MAX or x.shape[1] > TCONVFFN_F_MAX:
+        return f"!1 <= T <= {TCONVFFN_T_MAX} and F <= {TCONVFFN_F_MAX} (got T = {x.shape[2]}, F = {x.shape[1]})"
+    return None
+
+
+def _ret_call(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope) -> Optional[str]:
+    inner = rel_pos[1] if isinstance(rel_pos, tuple) and len(rel_pos) == 2 else None
+    if not chunkwise_recurrent or not (isinstance(inner, tuple) and inner[0] == "chunk"):
+        return "!only the chunkwise form runs natively"
+    if inner[1] != RET_CHUNK:
+        return f"!the chunk size must be {RET_CHUNK} (got {inner[1]})"
+    if rope is not False:
+        return f"!rope must be False (got {rope!r})"
+    if u.dim() != 3 or u.shape[-1] != 96:
+        return f"!input must be [B F,T,96], got {tuple(u.shape)}"
+    if not 1 <= u.shape[1] <= RET_T_MAX:
+        return f"!1 <= T <= {RET_T_MAX} (got T = {u.shape[1]})"
+    return None
+
+
+def _xband_call(layer, x: Tensor) -> Optional[str]:
+    if x.dim() != 4 or x.shape[-1] != 96:
+        return f"!input must be [B,F,T,96], got {tuple(x.shape)}"
     B, Fq, T = x.shape[:3]
     if Fq != layer.full.in_features:
         return f"!the input has {Fq} frequencies, the LinearGroup {layer.full.in_features}"
     if B < 1 or not 1 <= T <= XBAND_T_MAX or not 1 <= Fq <= XBAND_F_MAX or B * Fq * T * 288 >= 2 ** 31:
         return f"!1 <= T <= {XBAND_T_MAX}, F <= {XBAND_F_MAX} and B F T < 2^31 / 288 (got B = {B}, F = {Fq}, T = {T})"
-    if _xband_needs_grad(layer, x) and (T > XBAND_T_TRAIN_MAX or (dt == torch.float32 and Fq > XBAND_F_TRAIN_MAX_FP32)):
+    if _needs_grad(x, xband_params(layer)) and (T > XBAND_T_TRAIN_MAX or (_stream_dtype(x) == torch.float32 and Fq > XBAND_F_TRAIN_MAX_FP32)):
         return f"!with gradients T <= {XBAND_T_TRAIN_MAX}, and F <= {XBAND_F_TRAIN_MAX_FP32} in fp32 (got T = {T}, F = {Fq})"
     return None
 
 
-def _xband_needs_grad(layer, x: Tensor) -> bool:
-    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in xband_params(layer)))
+@dataclass(frozen=True)
+class Block:
+    """one natively trainable block of a SpatialNetLayer"""
+    switch: str  # the environment variable that turns it on
+    what: str  # in warnings "OnlineSpatialNet <what>", in errors "OnlineSpatialNet native <what>"
+    supported: Callable  # (layer) -> None, or why the layer is not what the kernels are built for
+    call: Callable  # (layer, x, *what the call adds) -> None, or '!' and why this call does not fit
+    streaming: str = "streaming call"  # the reason given to a call that carries a state
+    # the y = x + block(x) form only:
+    params: Optional[Callable] = None  # (layer) -> the parameter inputs in the order of the C ABI
+    entry: Optional[str] = None  # ops.<entry>_fwd / ops.<entry>_bwd (looked up at call time)
+
+    @property
+    def native(self) -> str:
+        return "OnlineSpatialNet native " + self.what
 
 
-def _xband_kernel_params(params) -> List[Tensor]:
+TCONVFFN = Block("NBSS_ONLINE_NATIVE_TRAIN", "T-ConvFFN", supported, _tconvffn_call, params=tconvffn_params, entry="online_tconvffn_train")
+RETENTION = Block("NBSS_ONLINE_NATIVE_RET", "retention", lambda layer: ret_supported(layer.mhsa), _ret_call, streaming="streaming or recurrent call")
+XBAND = Block("NBSS_ONLINE_NATIVE_XBAND", "cross-band blocks", xband_supported, _xband_call, params=xband_params, entry="online_xband_train")
+
+
+# ---- the scaffold: written once for the three blocks ------------------------------------------------------------------------------------------------------
+def _on(block: Block) -> bool:
+    return os.environ.get(block.switch, "0") == "1"
+
+
+# the switches, read at call time (like NBSS_NBC2_NATIVE); each off unless it is exactly '1'
+enabled, ret_enabled, xband_enabled = (functools.partial(_on, b) for b in (TCONVFFN, RETENTION, XBAND))
+
+
+def _stream_dtype(x: Tensor) -> Optional[torch.dtype]:
+    dev = "cuda" if x.is_cuda else "cpu"
+    if torch.is_autocast_enabled(dev):
+        return torch.bfloat16 if torch.get_autocast_dtype(dev) == torch.bfloat16 else None
+    return torch.float32 if x.dtype == torch.float32 else None
+
+
+def _needs_grad(x, params=()) -> bool:
+    """whether autograd will ask for a gradient of the tensor (or tensors, None allowed) `x` or of a parameter"""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ((x,) if isinstance(x, Tensor) else tuple(x)) + tuple(params))
+
+
+def _gate(block: Block, layer, x: Tensor, streaming: bool, *call) -> Optional[str]:
+    """None when this call takes the native block; else why not.  A reason that starts with '!' is worth a warning (the switch is on, the tensor is on the
+    library's device, and the layer, dtype or call does not fit); the others are the ordinary torch.nn cases."""
+    if not _on(block):
+        return f"{block.switch} is not 1"
+    if streaming:
+        return block.streaming
+    if _LIB_OVERRIDE is None and not x.is_cuda:
+        return "not on a HIP device"
+    if active_lib(x) is None:
+        return "no library for the tensor's device"
+    why = block.supported(layer)
+    if why is not None:
+        return "!" + why
+    if _stream_dtype(x) is None:
+        return f"!the stream must be fp32, or bf16 under autocast (got {x.dtype})"
+    return block.call(layer, x, *call)
+
+
+def eligible(layer, x: Tensor, state) -> Optional[str]:
+    """`_gate` for the T-ConvFFN of a call of `SpatialNetLayer._tconvffn`"""
+    return _gate(TCONVFFN, layer, x, state is not None)
+
+
+def ret_eligible(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope, state, inference: bool) -> Optional[str]:
+    """`_gate` for the retention core of a call of `SpatialNetLayer._tsa`"""
+    return _gate(RETENTION, layer, u, state is not None or inference, rel_pos, chunkwise_recurrent, rope)
+
+
+def xband_eligible(layer, x: Tensor, state) -> Optional[str]:
+    """`_gate` for the cross-band trio of a call of `SpatialNetLayer._xband`"""
+    return _gate(XBAND, layer, x, state is not None)
+
+
+def take(block: Block, layer, x: Tensor, streaming: bool, *call) -> bool:
+    """whether this call of a SpatialNetLayer method takes the native block; with the switch on and a layer or call that does not fit, one warning per layer
+    and reason, which points at the caller of that method"""
+    why = _gate(block, layer, x, streaming, *call)
+    if why is not None and why.startswith("!"):
+        from models.arch.base.native import torch_path_note
+        torch_path_note(layer, "OnlineSpatialNet " + block.what, why[1:], stacklevel=4)
+    return why is None
+
+
+def _lib_for(block: Block, x: Tensor) -> Lib:
+    lib = active_lib(x)
+    if lib is None:
+        raise ops.NbssError(f"{block.native}: no library for a tensor on {x.device}")
+    return lib
+
+
+def _kernel_params(params) -> List[Tensor]:
     """fp32 and contiguous (views where the module's tensors already are: the 1x1 weights [O][I][1] are their matrices as they lie)"""
     return [p.detach().float().contiguous() for p in params]
 
 
-class OnlineXBandFn(torch.autograd.Function):
-    """y = the cross-band trio through the HIP kernels; inputs (lib, x, *the 18 parameters): the parameters are inputs of the node, so p.grad is populated
-    the usual way (a LinearGroup shared by several layers is an input of several nodes: autograd sums).  Saved: x and the two block inputs the forward keeps.
-    One backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
+_xband_kernel_params = _kernel_params  # (the name tests/test_online_xband_train.py calls it by)
 
-    @staticmethod
+def _residual_fn(name: str, block: Block, doc: str):
+    """the autograd Function `name` of y = x + block(x) through the HIP kernels; inputs (lib, x, *the block's parameters): the parameters are inputs of the
+    node, so p.grad is populated the usual way.  One backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
+
     def forward(ctx, lib, x, *params):
         xk = x.contiguous()
-        p32 = _xband_kernel_params(params)
-        y, save = ops.online_xband_train_fwd(lib, p32, xk, keep=True)
+        p32 = _kernel_params(params)
+        y, save = getattr(ops, block.entry + "_fwd")(lib, p32, xk, keep=True)
         ctx.lib, ctx.saved, ctx.params = lib, (xk, save, p32), params
         ctx.versions = [p._version for p in params]
         return y
 
-    @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        ops.graph_guard_check(ctx, "OnlineSpatialNet native cross-band blocks")
+        ops.graph_guard_check(ctx, block.native)
         xk, save, p32 = ctx.saved
-        dx, grads = ops.online_xband_train_bwd(ctx.lib, p32, xk, save, dy.contiguous())
+        dx, grads = getattr(ops, block.entry + "_bwd")(ctx.lib, p32, xk, save, dy.contiguous())
         ctx.saved = None
         out = [g.reshape(p.shape).to(p.dtype) if ctx.needs_input_grad[2 + i] else None for i, (g, p) in enumerate(zip(grads, ctx.params))]
         return (None, dx if ctx.needs_input_grad[1] else None, *out)
 
+    return type(name, (torch.autograd.Function,), {"forward": staticmethod(forward), "backward": staticmethod(backward), "__doc__": doc,
+                                                   "__module__": __name__})
 
-def xband_residual(layer, x: Tensor) -> Tensor:
-    """x + fconv1, + full, + fconv2 for a call `xband_eligible` accepted; in the dtype of x.  Without autograd (no_grad, or nothing requires a gradient) the
-    forward runs alone and keeps nothing."""
-    lib = active_lib(x)
-    if lib is None:
-        raise ops.NbssError("OnlineSpatialNet native cross-band blocks: no library for a tensor on " + str(x.device))
-    params = xband_params(layer)
+
+OnlineTConvFFNFn = _residual_fn("OnlineTConvFFNFn", TCONVFFN, "y = x + T-ConvFFN(x); inputs (lib, x, *the 14 parameters).  Saved: x and the kernels' activations.")
+OnlineXBandFn = _residual_fn("OnlineXBandFn", XBAND, "y = the cross-band trio; inputs (lib, x, *the 18 parameters) (a LinearGroup shared by several layers is an "
+                             "input of several nodes: autograd sums).  Saved: x and the two block inputs the forward keeps.")
+
+
+def _residual(block: Block, fn, layer, x: Tensor) -> Tensor:
+    """x + block(x) for a call the gate accepted; in the dtype of x.  Without autograd (no_grad, or nothing requires a gradient) the forward runs alone and
+    keeps nothing."""
+    lib = _lib_for(block, x)
+    params = block.params(layer)
     xs = x.to(_stream_dtype(x))
-    if _xband_needs_grad(layer, x):
-        y = OnlineXBandFn.apply(lib, xs, *params)
+    if _needs_grad(x, params):
+        y = fn.apply(lib, xs, *params)
     else:
         with torch.no_grad():
-            y = ops.online_xband_train_fwd(lib, _xband_kernel_params(params), xs.contiguous(), keep=False)[0]
+            y = getattr(ops, block.entry + "_fwd")(lib, _kernel_params(params), xs.contiguous(), keep=False)[0]
     return y.to(x.dtype)
+
+
+# x + T-ConvFFN(x) for a call `eligible` accepted, and x + fconv1, + full, + fconv2 for a call `xband_eligible` accepted: (layer, x) -> y
+tconvffn_residual = functools.partial(_residual, TCONVFFN, OnlineTConvFFNFn)
+xband_residual = functools.partial(_residual, XBAND, OnlineXBandFn)
+
+
+class OnlineRetentionFn(torch.autograd.Function):
+    """out = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)) through the HIP kernels; inputs (lib, q, k or None, v, g, k_scale, decay).  One
+    backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
+
+    @staticmethod
+    def forward(ctx, lib, q, k, v, g, k_scale, decay):
+        q, v, g = q.contiguous(), v.contiguous(), g.contiguous()
+        k = None if k is None else k.contiguous()
+        out, save = ops.online_ret_train_fwd(lib, q, k, v, g, k_scale, decay, keep=True)
+        ctx.lib, ctx.k_scale, ctx.saved = lib, k_scale, (q, k, v, g, decay, save)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        ops.graph_guard_check(ctx, RETENTION.native)
+        q, k, v, g, decay, save = ctx.saved
+        dq, dk, dv, dg = ops.online_ret_train_bwd(ctx.lib, q, k, v, g, ctx.k_scale, decay, save, d_out.contiguous())
+        ctx.saved = None
+        return None, dq, dk, dv, dg, None, None
+
+
+def retention_forward(mhsa, u: Tensor, rel_pos) -> Tensor:
+    """MultiScaleRetention.forward(u, rel_pos, chunkwise_recurrent=True, rope=False) for a call `ret_eligible` accepted: the projections and out_proj are the
+    module's own nn.Linear's (torch GEMMs, autocast like any other), the core between them is native.  Without autograd the forward runs alone and keeps nothing."""
+    lib = _lib_for(RETENTION, u)
+    dt = _stream_dtype(u)
+    q = mhsa.q_proj(u).to(dt)
+    k = None if mhsa.share_qk else mhsa.k_proj(u).to(dt)
+    v, g = mhsa.v_proj(u).to(dt), mhsa.g_proj(u).to(dt)
+    decay = rel_pos[1][2].detach().to(device=u.device, dtype=torch.float32).contiguous()
+    if _needs_grad((q, k, v, g)):
+        out = OnlineRetentionFn.apply(lib, q, k, v, g, float(mhsa.scaling), decay)
+    else:
+        with torch.no_grad():
+            out = ops.online_ret_train_fwd(lib, q.contiguous(), None if k is None else k.contiguous(), v.contiguous(), g.contiguous(), float(mhsa.scaling),
+                                           decay, keep=False)[0]
+    return mhsa.out_proj(out)

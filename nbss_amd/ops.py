@@ -538,62 +538,84 @@ def graph_guard_check(ctx, what: str):
     if ctx.saved is None:
         raise RuntimeError(f"{what}: trying to backward through the graph a second time: the native path frees its saved state after the first backward "
                            "(retain_graph is not supported)")
-    for p, v in zip(ctx.params, ctx.versions):
+    for p, v in zip(getattr(ctx, "params", ()), getattr(ctx, "versions", ())):  # (a node that saved no parameters has none to check)
         if p._version != v:
             raise RuntimeError(f"{what}: a parameter needed for the gradient computation was modified in place between forward and backward "
                                f"(shape {tuple(p.shape)}, version {p._version}, expected {v})")
 
 
-# ---- OnlineSpatialNet: the causal T-ConvFFN for training (csrc/online_train.hip) ----------------------------------------------------------------
-def _online_train_dims(x: Tensor):
-    if x.dim() != 4 or x.shape[-1] != 96 or x.dtype not in (torch.float32, torch.bfloat16):
-        raise NbssError(f"online T-ConvFFN: x must be [B,F,T,96] in fp32 or bf16, got {tuple(x.shape)} {x.dtype}")
-    return (NBSS_BF16 if x.dtype == torch.bfloat16 else NBSS_F32, *x.shape[:3])
-
-
-def _online_train_bytes(lib: Lib, name: str, dtype: int, B: int, F: int, T: int) -> int:
-    n = getattr(lib, name)(dtype, B, F, T)
+# ---- OnlineSpatialNet: the three blocks for training (csrc/online_train.hip, online_ret_train.hip, online_xband_train.hip) ------------------------
+def _online_bytes(lib: Lib, name: str, *dims: int) -> int:
+    n = getattr(lib, name)(*dims)
     if n < 0:
         raise NbssError(f"{name} failed: {_ERR.get(n, n)}")
     return n
 
 
+def _online_train_dims(x: Tensor, what: str = "online T-ConvFFN"):
+    if x.dim() != 4 or x.shape[-1] != 96 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise NbssError(f"{what}: x must be [B,F,T,96] in fp32 or bf16, got {tuple(x.shape)} {x.dtype}")
+    return (NBSS_BF16 if x.dtype == torch.bfloat16 else NBSS_F32, *x.shape[:3])
+
+
+def _online_block_fwd(lib: Lib, entry: str, what: str, params: List[Tensor], x: Tensor, save_bytes, ws, check=None):
+    """the forward of a block y = x + block(x) on the [B,F,T,96] stream: `save_bytes(lib, dtype, B, F, T)` sizes what backward needs (None: keep nothing),
+    `ws(lib, x)` provides the workspace, `check(which, tensors, F)` (optional) the sizes of the parameters -> (y, save)"""
+    dt, B, F, T = _online_train_dims(x, what)
+    if check is not None:
+        check("params", params, F)
+    y = torch.empty_like(x)
+    save = None if save_bytes is None else scratch(save_bytes(lib, dt, B, F, T), x.device)
+    buf = ws(lib, x)  # (held until the call returns)
+    lib.call(entry, dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save), _ptr(lib, buf), _stream(lib, x))
+    return y, save
+
+
+def _online_block_bwd(lib: Lib, entry: str, what: str, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads, new_grad, ws, check=None):
+    """the backward of the same: `new_grad(p)` makes the gradient buffer of a parameter when `grads` is None -> (dx, grads)"""
+    dt, B, F, T = _online_train_dims(x, what)
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise NbssError(f"{what}: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    if check is not None:
+        check("params", params, F)
+    if grads is None:
+        grads = [new_grad(p) for p in params]
+    if check is not None:
+        check("grads", grads, F)
+    dx, buf = torch.empty_like(x), ws(lib, x)
+    lib.call(entry, dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy), _ptr(lib, dx),
+             *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, buf), _stream(lib, x))
+    return dx, grads
+
+
+# the causal T-ConvFFN
 def online_tconvffn_train_save_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_train_bytes(lib, "nbss_online_tconvffn_train_save_bytes", dtype, B, F, T)
+    return _online_bytes(lib, "nbss_online_tconvffn_train_save_bytes", dtype, B, F, T)
 
 
 def online_tconvffn_train_ws_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_train_bytes(lib, "nbss_online_tconvffn_train_ws_bytes", dtype, B, F, T)
+    return _online_bytes(lib, "nbss_online_tconvffn_train_ws_bytes", dtype, B, F, T)
+
+
+def _online_tconvffn_ws(lib: Lib, x: Tensor) -> Tensor:
+    """a fresh workspace per call"""
+    return scratch(online_tconvffn_train_ws_bytes(lib, *_online_train_dims(x)), x.device)
 
 
 def online_tconvffn_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True):
     """y = x + T-ConvFFN(x) on x [B,F,T,96] (fp32 or bf16); params: the 14 fp32 tensors in the order of include/nbss_hip.h (state_dict layout).
     -> (y, save): `save` is what online_tconvffn_train_bwd needs (None with keep=False: inference)"""
-    dt, B, F, T = _online_train_dims(x)
-    y = torch.empty_like(x)
-    save = scratch(online_tconvffn_train_save_bytes(lib, dt, B, F, T), x.device) if keep else None
-    ws = scratch(online_tconvffn_train_ws_bytes(lib, dt, B, F, T), x.device)
-    lib.call("nbss_online_tconvffn_train_fwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save),
-             _ptr(lib, ws), _stream(lib, x))
-    return y, save
+    return _online_block_fwd(lib, "nbss_online_tconvffn_train_fwd", "online T-ConvFFN", params, x, online_tconvffn_train_save_bytes if keep else None,
+                             _online_tconvffn_ws)
 
 
 def online_tconvffn_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None):
     """-> (dx, grads): dx includes the residual path; the 14 fp32 parameter gradients are ACCUMULATED into `grads` (zeros of the parameters' shapes when
     not given)"""
-    dt, B, F, T = _online_train_dims(x)
-    if dy.shape != x.shape or dy.dtype != x.dtype:
-        raise NbssError(f"online T-ConvFFN: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
-    if grads is None:
-        grads = [torch.zeros_like(p) for p in params]
-    dx = torch.empty_like(x)
-    ws = scratch(online_tconvffn_train_ws_bytes(lib, dt, B, F, T), x.device)
-    lib.call("nbss_online_tconvffn_train_bwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
-             _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, x))
-    return dx, grads
+    return _online_block_bwd(lib, "nbss_online_tconvffn_train_bwd", "online T-ConvFFN", params, x, save, dy, grads, torch.zeros_like, _online_tconvffn_ws)
 
 
-# ---- OnlineSpatialNet: the chunkwise retention core for training (csrc/online_ret_train.hip) ----------------------------------------------------
+# the chunkwise retention core
 def _online_ret_dims(q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor):
     if q.dim() != 3 or q.shape[-1] != 96 or q.dtype not in (torch.float32, torch.bfloat16):
         raise NbssError(f"online retention: q must be [BF,T,96] in fp32 or bf16, got {tuple(q.shape)} {q.dtype}")
@@ -604,20 +626,13 @@ def _online_ret_dims(q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor):
     return NBSS_BF16 if q.dtype == torch.bfloat16 else NBSS_F32, BF, T
 
 
-def _online_ret_bytes(lib: Lib, name: str, dtype: int, BF: int, T: int) -> int:
-    n = getattr(lib, name)(dtype, BF, T)
-    if n < 0:
-        raise NbssError(f"{name} failed: {_ERR.get(n, n)}")
-    return n
-
-
 def online_ret_train_fwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, keep: bool = True):
     """out [BF,T,192] = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)); k = None shares the keys with q; decay [4] fp32: the per-head gamma.
     -> (out, save): `save` is what online_ret_train_bwd needs (None with keep=False: inference)"""
     dt, BF, T = _online_ret_dims(q, k, v, g)
     out = torch.empty_like(v)
-    save = scratch(_online_ret_bytes(lib, "nbss_online_ret_train_save_bytes", dt, BF, T), q.device) if keep else None
-    ws = scratch(_online_ret_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
+    save = scratch(_online_bytes(lib, "nbss_online_ret_train_save_bytes", dt, BF, T), q.device) if keep else None
+    ws = scratch(_online_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
     lib.call("nbss_online_ret_train_fwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
              _ptr(lib, out), _ptr(lib, save), _ptr(lib, ws), _stream(lib, q))
     return out, save
@@ -629,19 +644,19 @@ def online_ret_train_bwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g:
     if d_out.shape != v.shape or d_out.dtype != v.dtype:
         raise NbssError(f"online retention: d_out {tuple(d_out.shape)} {d_out.dtype} does not match v {tuple(v.shape)} {v.dtype}")
     dq, dk, dv, dg = torch.empty_like(q), None if k is None else torch.empty_like(q), torch.empty_like(v), torch.empty_like(v)
-    ws = scratch(_online_ret_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
+    ws = scratch(_online_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
     lib.call("nbss_online_ret_train_bwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
              _ptr(lib, save), _ptr(lib, d_out), _ptr(lib, dq), _ptr(lib, dk), _ptr(lib, dv), _ptr(lib, dg), _ptr(lib, ws), _stream(lib, q))
     return dq, dk, dv, dg
 
 
-# ---- OnlineSpatialNet: the cross-band trio for training (csrc/online_xband_train.hip) -----------------------------------------------------------
+# the cross-band trio
 def online_xband_save_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_train_bytes(lib, "nbss_online_xband_save_bytes", dtype, B, F, T)
+    return _online_bytes(lib, "nbss_online_xband_save_bytes", dtype, B, F, T)
 
 
 def online_xband_ws_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_train_bytes(lib, "nbss_online_xband_ws_bytes", dtype, B, F, T)
+    return _online_bytes(lib, "nbss_online_xband_ws_bytes", dtype, B, F, T)
 
 
 def _online_xband_check(what: str, tensors: List[Tensor], F: int):
@@ -659,7 +674,7 @@ def online_xband_ws(lib: Lib, x: Tensor) -> Tensor:
     """the workspace of the cross-band entry points for the shape of x: ONE buffer per (library, device, dtype, shape), shared by every layer and by both
     directions (its largest part is the reused backward kernels' workspace, ~0.9 GB at batch 4 in fp32; the calls are in order on one stream and each
     writes what it reads).  A new shape on the same device and dtype replaces the old buffer."""
-    dt, B, F, T = _online_train_dims(x)
+    dt, B, F, T = _online_train_dims(x, "online cross-band")
     slot, shape = (id(lib), x.device, dt), (B, F, T)
     have = _XBAND_WS.get(slot)
     if have is None or have[0] != shape:
@@ -671,29 +686,15 @@ def online_xband_ws(lib: Lib, x: Tensor) -> Tensor:
 def online_xband_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True, ws: Optional[Tensor] = None):
     """y = the cross-band trio (x + fconv1, + full, + fconv2) on x [B,F,T,96] (fp32 or bf16); params: the 18 fp32 tensors in state_dict order.
     -> (y, save): `save` (the inputs of the second and third block) is what online_xband_train_bwd needs (None with keep=False: inference)"""
-    dt, B, F, T = _online_train_dims(x)
-    _online_xband_check("params", params, F)
-    y = torch.empty_like(x)
-    save = scratch(online_xband_save_bytes(lib, dt, B, F, T), x.device) if keep else None
-    ws = online_xband_ws(lib, x) if ws is None else ws
-    lib.call("nbss_online_xband_train_fwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save),
-             _ptr(lib, ws), _stream(lib, x))
-    return y, save
+    return _online_block_fwd(lib, "nbss_online_xband_train_fwd", "online cross-band", params, x, online_xband_save_bytes if keep else None,
+                             online_xband_ws if ws is None else lambda lib, x: ws, _online_xband_check)
 
 
 def online_xband_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None,
                            ws: Optional[Tensor] = None):
     """-> (dx, grads): dx includes the residual paths; the 18 fp32 parameter gradients are WRITTEN into `grads` (uninitialised buffers of the parameters'
     shapes when not given)"""
-    dt, B, F, T = _online_train_dims(x)
-    if dy.shape != x.shape or dy.dtype != x.dtype:
-        raise NbssError(f"online cross-band: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
-    _online_xband_check("params", params, F)
-    if grads is None:
-        grads = [torch.empty_like(p) for p in params]
-    _online_xband_check("grads", grads, F)
-    dx = torch.empty_like(x)
-    ws = online_xband_ws(lib, x) if ws is None else ws
-    lib.call("nbss_online_xband_train_bwd", dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
-             _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, x))
-    return dx, grads
+    return _online_block_bwd(lib, "nbss_online_xband_train_bwd", "online cross-band", params, x, save, dy, grads, torch.empty_like,
+                             online_xband_ws if ws is None else lambda lib, x: ws, _online_xband_check)
+
+

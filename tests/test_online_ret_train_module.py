@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from nbss_amd import online_train
-from util import rel_l2
+from util import check_against_fp64, fit_with_switch, fp64_reference, grad_fns, online_net, rel_l2
 
 ROOT = Path(__file__).resolve().parent.parent
 FWD_TOL, GRAD_TOL = 2e-5, 1e-4
@@ -19,30 +19,7 @@ RET, TCF = "OnlineRetentionFnBackward", "OnlineTConvFFNFnBackward"
 
 
 def _net(**kw):
-    from models.arch.OnlineSpatialNet import OnlineSpatialNet
-    torch.manual_seed(13)
-    args = dict(dim_input=4, dim_output=4, num_layers=1, dim_squeeze=8, num_freqs=F, dim_hidden=96, dim_ffn=192, num_heads=4, attention="ret(2)",
-                decay=[4, 5, 9, 10])
-    args.update(kw)
-    net = OnlineSpatialNet(**args).train()
-    with torch.no_grad():
-        for p in net.parameters():
-            if p.dim() == 1:
-                p.add_(0.2 * torch.randn_like(p))
-    return net
-
-
-def _grad_fns(t):
-    """names of every node of the autograd graph behind t"""
-    seen, todo, names = set(), [t.grad_fn], set()
-    while todo:
-        f = todo.pop()
-        if f is None or f in seen:
-            continue
-        seen.add(f)
-        names.add(type(f).__name__)
-        todo += [g for g, _ in f.next_functions]
-    return names
+    return online_net(13, F, **{"decay": [4, 5, 9, 10], **kw})
 
 
 @pytest.fixture(scope="module", params=["ret(2)", "ret(2,not_share_qk)"])
@@ -50,11 +27,7 @@ def reference(request):
     """a 1-layer model ('ret(2)' with rope=False shares q and k; the other form has a k_proj) and its switch-off run in fp64 on the CPU: computed once"""
     net = _net(attention=request.param)
     assert net.layers[0].mhsa.share_qk == (request.param == "ret(2)") and net.rope is False
-    x, r = torch.randn(B, F, T, 4), torch.randn(B, F, T, 4)
-    n64 = copy.deepcopy(net).double()
-    y = n64(x.double())
-    (y * r.double()).sum().backward()
-    return net, x, r, y.detach(), {k: p.grad for k, p in n64.named_parameters()}
+    return fp64_reference(net, B, F, T)
 
 
 @pytest.mark.parametrize("both", [False, True], ids=["ret", "ret+tconvffn"])
@@ -65,14 +38,14 @@ def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch, both
     monkeypatch.delenv("NBSS_ONLINE_NATIVE_RET", raising=False)
     monkeypatch.delenv("NBSS_ONLINE_NATIVE_TRAIN", raising=False)
     with online_train.use_lib(backend.lib):
-        assert RET not in _grad_fns(net(xd))  # off by default
+        assert RET not in grad_fns(net(xd))  # off by default
         monkeypatch.setenv("NBSS_ONLINE_NATIVE_RET", "0")
-        assert RET not in _grad_fns(net(xd))
+        assert RET not in grad_fns(net(xd))
         monkeypatch.setenv("NBSS_ONLINE_NATIVE_RET", "1")
         if both:
             monkeypatch.setenv("NBSS_ONLINE_NATIVE_TRAIN", "1")
         y = net(xd)
-        fns = _grad_fns(y)
+        fns = grad_fns(y)
         assert RET in fns and (TCF in fns) == both
         (y * rd).sum().backward()
         grads = {k: p.grad.clone() for k, p in net.named_parameters()}  # (the refused second backward below may reach some leaves before it is refused)
@@ -85,13 +58,9 @@ def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch, both
         a_train = layer._tsa(h, pos, True, net.rope)[0]
         with torch.no_grad():
             a_inf = layer._tsa(h, pos, True, net.rope)[0]
-            assert RET not in _grad_fns(net(xd))
-    assert RET in _grad_fns(a_train) and a_inf.grad_fn is None and torch.equal(a_inf, a_train.detach())
-    ey = rel_l2(y.detach().cpu(), wy)
-    errs = {k: rel_l2(g.cpu(), wg[k]) for k, g in grads.items()}
-    print(f"y {ey:.1e}; worst grad {max(errs, key=errs.get)} {max(errs.values()):.1e}")
-    assert set(errs) == set(wg) and ey <= FWD_TOL, ey
-    assert max(errs.values()) <= GRAD_TOL, {k: v for k, v in errs.items() if v > GRAD_TOL}
+            assert RET not in grad_fns(net(xd))
+    assert RET in grad_fns(a_train) and a_inf.grad_fn is None and torch.equal(a_inf, a_train.detach())
+    check_against_fp64(y, grads, wy, wg, FWD_TOL, GRAD_TOL)
 
 
 @pytest.mark.parametrize("kw,reason", [(dict(rope=True), "rope must be False"), (dict(num_heads=2, decay=[4, 5]), "num_heads must be 4")], ids=["rope", "heads"])
@@ -105,7 +74,7 @@ def test_unsupported_call_warns_once_and_runs_torch(backend, monkeypatch, kw, re
         with warnings.catch_warnings():
             warnings.simplefilter("error")  # once per module and reason
             y2 = net(x)
-    assert RET not in _grad_fns(y) and torch.equal(y, y2)
+    assert RET not in grad_fns(y) and torch.equal(y, y2)
 
 
 def test_recurrent_and_streaming_calls_never_take_the_native_core(backend, monkeypatch):
@@ -119,12 +88,12 @@ def test_recurrent_and_streaming_calls_never_take_the_native_core(backend, monke
         assert online_train.ret_eligible(layer, u, pos, True, False, None, False) is None
         assert online_train.ret_eligible(layer, u, pos, True, False, {}, False) == "streaming or recurrent call"
         assert online_train.ret_eligible(layer, u, pos, True, False, None, True) == "streaming or recurrent call"
-        assert RET not in _grad_fns(net(x, inference=True))
+        assert RET not in grad_fns(net(x, inference=True))
         st = net.init_stream(1, device=backend.device)
         y = torch.cat([net.forward_stream(x[:, :, :4], st), net.forward_stream(x[:, :, 4:], st)], 2)
-        assert RET not in _grad_fns(y)
+        assert RET not in grad_fns(y)
         whole = net(x)
-    assert RET in _grad_fns(whole)
+    assert RET in grad_fns(whole)
     assert rel_l2(y.detach(), whole.detach()) < 1e-4  # (the streamed frames are the whole-utterance ones)
 
 
@@ -143,30 +112,7 @@ def test_supported_names_the_geometry():
 def test_fit_on_the_device_with_the_switch(monkeypatch):
     """TrainCLI fit, configs/onlineSpatialNet.yaml, synthetic data, 2 layers, 1.1-s segments (69 frames: two chunks), two epochs of two steps: the first
     step's loss is the switch-off run's to 1e-4 relative, and the loss decreases"""
-    import SharedTrainer
-    from SharedTrainer import TrainCLI
     argv = ["fit", "--config", str(ROOT / "configs" / "onlineSpatialNet.yaml"), "--config", str(ROOT / "configs" / "datasets" / "synthetic.yaml"),
             "--model.arch.dim_input=12", "--model.arch.dim_output=4", "--model.arch.num_freqs=129", "--model.arch.num_layers=2", "--data.num_samples=[4,2,2]",
             "--data.audio_time_len=[1.1,1.1,1.1]", "--data.batch_size=[2,1]", "--trainer.max_epochs=2"]
-    steps = []
-    orig = SharedTrainer.TrainModule.training_step
-
-    def recording(self, *a, **k):
-        loss = orig(self, *a, **k)
-        steps.append((float(loss.detach()), RET in _grad_fns(loss)))
-        return loss
-
-    monkeypatch.setattr(SharedTrainer.TrainModule, "training_step", recording)
-    monkeypatch.delenv("NBSS_ONLINE_NATIVE_RET", raising=False)
-    monkeypatch.delenv("NBSS_ONLINE_NATIVE_TRAIN", raising=False)
-    TrainCLI(argv=argv)
-    off, steps[:] = list(steps), []
-    monkeypatch.setenv("NBSS_ONLINE_NATIVE_RET", "1")
-    log = TrainCLI(argv=argv).result["log"]
-    on = list(steps)
-    print("switch off:", off, "\nswitch on: ", on)
-    assert len(log) == 2 and len(on) == len(off) == 4 and log[0]["device"].startswith("cuda")
-    assert not any(n for _, n in off) and all(n for _, n in on)
-    assert abs(on[0][0] - off[0][0]) <= 1e-4 * abs(off[0][0]), (on[0], off[0])
-    key = next(k for k in log[0] if k.startswith("train/"))
-    assert log[1][key] < log[0][key], log
+    fit_with_switch(monkeypatch, argv, ["NBSS_ONLINE_NATIVE_RET"], RET)

@@ -2,13 +2,15 @@
 graph, every p.grad of a model against the switch-off run in fp64 on the CPU (the project's fp32 bars: forward <= 2e-5, gradients <= 1e-4 rel-L2), the
 refusals, and one `TrainCLI fit` on the device."""
 import copy
+import types
+import warnings
 from pathlib import Path
 
 import pytest
 import torch
 
-from nbss_amd import online_train
-from util import rel_l2
+from nbss_amd import online_train, ops
+from util import ONLINE_SWITCHES, check_against_fp64, fit_with_switch, fp64_reference, grad_fns, online_net, rel_l2
 
 ROOT = Path(__file__).resolve().parent.parent
 FWD_TOL, GRAD_TOL = 2e-5, 1e-4
@@ -16,40 +18,13 @@ F, T = 5, 20
 
 
 def _net(**kw):
-    from models.arch.OnlineSpatialNet import OnlineSpatialNet
-    torch.manual_seed(11)
-    args = dict(dim_input=4, dim_output=4, num_layers=1, dim_squeeze=8, num_freqs=F, dim_hidden=96, dim_ffn=192, num_heads=4, attention="ret(2)")
-    args.update(kw)
-    net = OnlineSpatialNet(**args).train()
-    with torch.no_grad():
-        for p in net.parameters():
-            if p.dim() == 1:
-                p.add_(0.2 * torch.randn_like(p))
-    return net
-
-
-def _grad_fns(t):
-    """names of every node of the autograd graph behind t"""
-    seen, todo, names = set(), [t.grad_fn], set()
-    while todo:
-        f = todo.pop()
-        if f is None or f in seen:
-            continue
-        seen.add(f)
-        names.add(type(f).__name__)
-        todo += [g for g, _ in f.next_functions]
-    return names
+    return online_net(11, F, **kw)
 
 
 @pytest.fixture(scope="module")
 def reference():
     """the switch-off run in fp64 on the CPU: computed once"""
-    net = _net()
-    x, r = torch.randn(2, F, T, 4), torch.randn(2, F, T, 4)
-    n64 = copy.deepcopy(net).double()
-    y = n64(x.double())
-    (y * r.double()).sum().backward()
-    return net, x, r, y.detach(), {k: p.grad for k, p in n64.named_parameters()}
+    return fp64_reference(_net(), 2, F, T)
 
 
 def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch):
@@ -59,21 +34,17 @@ def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch):
     monkeypatch.delenv("NBSS_ONLINE_NATIVE_TRAIN", raising=False)
     with online_train.use_lib(backend.lib):
         y_off = net(xd)
-        assert "OnlineTConvFFNFnBackward" not in _grad_fns(y_off)  # off by default
+        assert "OnlineTConvFFNFnBackward" not in grad_fns(y_off)  # off by default
         monkeypatch.setenv("NBSS_ONLINE_NATIVE_TRAIN", "1")
         y = net(xd)
-        assert "OnlineTConvFFNFnBackward" in _grad_fns(y)
+        assert "OnlineTConvFFNFnBackward" in grad_fns(y)
         (y * rd).sum().backward()
         with pytest.raises(RuntimeError, match="second time|retain_graph"):
             (y * rd).sum().backward()
         with torch.no_grad():  # inference obeys the same switch: the forward entry alone, nothing kept
             y_inf = net(xd)
     assert torch.equal(y_inf, y.detach())
-    ey = rel_l2(y.detach().cpu(), wy)
-    errs = {k: rel_l2(p.grad.cpu(), wg[k]) for k, p in net.named_parameters()}
-    print(f"y {ey:.1e}; worst grad {max(errs, key=errs.get)} {max(errs.values()):.1e}")
-    assert set(errs) == set(wg) and ey <= FWD_TOL, ey
-    assert max(errs.values()) <= GRAD_TOL, {k: v for k, v in errs.items() if v > GRAD_TOL}
+    check_against_fp64(y, {k: p.grad for k, p in net.named_parameters()}, wy, wg, FWD_TOL, GRAD_TOL)
 
 
 def test_unsupported_geometry_warns_once_and_runs_torch(backend, monkeypatch):
@@ -83,11 +54,10 @@ def test_unsupported_geometry_warns_once_and_runs_torch(backend, monkeypatch):
     with online_train.use_lib(backend.lib):
         with pytest.warns(RuntimeWarning, match="dim_ffn must be 192"):
             y = net(x)
-        import warnings
         with warnings.catch_warnings():
             warnings.simplefilter("error")  # once per module and reason
             y2 = net(x)
-    assert "OnlineTConvFFNFnBackward" not in _grad_fns(y) and torch.equal(y, y2)
+    assert "OnlineTConvFFNFnBackward" not in grad_fns(y) and torch.equal(y, y2)
 
 
 def test_streaming_call_never_takes_the_native_block(backend, monkeypatch):
@@ -98,39 +68,64 @@ def test_streaming_call_never_takes_the_native_block(backend, monkeypatch):
         assert online_train.eligible(net.layers[0], torch.zeros(1, F, 8, 96, device=backend.device), {}) == "streaming call"
         st = net.init_stream(1, device=backend.device)
         y = torch.cat([net.forward_stream(x[:, :, :4], st), net.forward_stream(x[:, :, 4:], st)], 2)
-        assert "OnlineTConvFFNFnBackward" not in _grad_fns(y)
+        assert "OnlineTConvFFNFnBackward" not in grad_fns(y)
         whole = net(x)
-    assert "OnlineTConvFFNFnBackward" in _grad_fns(whole)
+    assert "OnlineTConvFFNFnBackward" in grad_fns(whole)
     assert rel_l2(y.detach(), whole.detach()) < 1e-4  # (the streamed frames are the whole-utterance ones)
+
+
+def test_library_for_another_device_goes_to_torch_silently(backend, monkeypatch):
+    """all three blocks: under a `use_lib` override whose backend does not match the tensor's device the gate says so, the layer runs torch.nn — the bits
+    of the switch-off run — and nothing warns.  The override is the backend's library and the tensors are on the other kind of device; where no HIP device
+    exists the emulator backend takes the other direction instead: CPU tensors under a stand-in for a library that is not the emulator (the gate asks the
+    library nothing else)."""
+    if backend.device.type == "cpu" and not torch.cuda.is_available():
+        lib, dev = types.SimpleNamespace(_is_emu=False), torch.device("cpu")
+    else:
+        lib, dev = backend.lib, torch.device("cuda" if backend.device.type == "cpu" else "cpu")
+    net = _net().to(dev)
+    layer, x = net.layers[0], torch.randn(1, F, 6, 4, device=dev)
+    h, pos = torch.zeros(1, F, 6, 96, device=dev), net.get_causal_mask(slen=6, device=dev)
+    why = "no library for the tensor's device"
+    for s in ONLINE_SWITCHES:
+        monkeypatch.delenv(s, raising=False)
+    with online_train.use_lib(lib), warnings.catch_warnings():
+        warnings.simplefilter("error")
+        y_off = net(x)
+        for s in ONLINE_SWITCHES:
+            monkeypatch.setenv(s, "1")
+        assert online_train.eligible(layer, h, None) == why and online_train.xband_eligible(layer, h, None) == why
+        assert online_train.ret_eligible(layer, h[0], pos, True, False, None, False) == why
+        y = net(x)
+    assert not {n for n in grad_fns(y) if n.startswith("Online")} and torch.equal(y, y_off)
+
+
+@pytest.mark.parametrize("block", ["tconvffn", "retention"])
+def test_no_grad_forward_keeps_nothing(backend, monkeypatch, block):
+    """under no_grad, with parameters that require gradients, the block's forward entry runs alone (keep=False), its output has no grad_fn and the bits of
+    the training output; T 70 spans two 64-frame chunks of the retention kernels"""
+    entry, switch, frames = {"tconvffn": ("online_tconvffn_train_fwd", "NBSS_ONLINE_NATIVE_TRAIN", T),
+                             "retention": ("online_ret_train_fwd", "NBSS_ONLINE_NATIVE_RET", 70)}[block]
+    net = _net().to(backend.device)
+    layer, h = net.layers[0], torch.randn(2, F, frames, 96, device=backend.device)
+    pos = net.get_causal_mask(slen=frames, device=backend.device)
+    run = (lambda: layer._tconvffn(h, residual=True)) if block == "tconvffn" else (lambda: layer._tsa(h, pos, True, net.rope)[0])
+    keeps, orig = [], getattr(ops, entry)
+    monkeypatch.setattr(ops, entry, lambda *a, **k: (keeps.append(k.get("keep")), orig(*a, **k))[1])
+    monkeypatch.setenv(switch, "1")
+    with online_train.use_lib(backend.lib):
+        y_train = run()
+        with torch.no_grad():
+            y_inf = run()
+    assert all(p.requires_grad for p in layer.parameters()) and keeps == [True, False]
+    assert y_train.grad_fn is not None and y_inf.grad_fn is None and torch.equal(y_inf, y_train.detach())
 
 
 @pytest.mark.gpu
 def test_fit_on_the_device_with_the_switch(monkeypatch):
     """TrainCLI fit, configs/onlineSpatialNet.yaml, synthetic data, 2 layers, 1-s segments, two epochs of two steps: the first step's loss is the switch-off
     run's to 1e-4 relative, and the loss decreases"""
-    import SharedTrainer
-    from SharedTrainer import TrainCLI
     argv = ["fit", "--config", str(ROOT / "configs" / "onlineSpatialNet.yaml"), "--config", str(ROOT / "configs" / "datasets" / "synthetic.yaml"),
             "--model.arch.dim_input=12", "--model.arch.dim_output=4", "--model.arch.num_freqs=129", "--model.arch.num_layers=2", "--data.num_samples=[4,2,2]",
             "--data.audio_time_len=[1.0,1.0,1.0]", "--data.batch_size=[2,1]", "--trainer.max_epochs=2"]
-    steps = []
-    orig = SharedTrainer.TrainModule.training_step
-
-    def recording(self, *a, **k):
-        loss = orig(self, *a, **k)
-        steps.append((float(loss.detach()), "OnlineTConvFFNFnBackward" in _grad_fns(loss)))
-        return loss
-
-    monkeypatch.setattr(SharedTrainer.TrainModule, "training_step", recording)
-    monkeypatch.delenv("NBSS_ONLINE_NATIVE_TRAIN", raising=False)
-    TrainCLI(argv=argv)
-    off, steps[:] = list(steps), []
-    monkeypatch.setenv("NBSS_ONLINE_NATIVE_TRAIN", "1")
-    log = TrainCLI(argv=argv).result["log"]
-    on = list(steps)
-    print("switch off:", off, "\nswitch on: ", on)
-    assert len(log) == 2 and len(on) == len(off) == 4 and log[0]["device"].startswith("cuda")
-    assert not any(n for _, n in off) and all(n for _, n in on)
-    assert abs(on[0][0] - off[0][0]) <= 1e-4 * abs(off[0][0]), (on[0], off[0])
-    key = next(k for k in log[0] if k.startswith("train/"))
-    assert log[1][key] < log[0][key], log
+    fit_with_switch(monkeypatch, argv, ["NBSS_ONLINE_NATIVE_TRAIN"], "OnlineTConvFFNFnBackward")

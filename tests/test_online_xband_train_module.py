@@ -11,40 +11,17 @@ import pytest
 import torch
 
 from nbss_amd import online_train, ops
-from util import rel_l2
+from util import ONLINE_SWITCHES as SWITCHES, check_against_fp64, fit_with_switch, fp64_reference, grad_fns, online_net, rel_l2
 
 ROOT = Path(__file__).resolve().parent.parent
 FWD_TOL, GRAD_TOL = 2e-5, 1e-4
 BF16_FWD_TOL, BF16_FCONV_TOL, BF16_TOL = 1.5e-2, 5e-2, 3e-2  # tests/test_online_xband_train.py
 F, T = 17, 7
 NODE = "OnlineXBandFnBackward"
-SWITCHES = ("NBSS_ONLINE_NATIVE_XBAND", "NBSS_ONLINE_NATIVE_TRAIN", "NBSS_ONLINE_NATIVE_RET")
 
 
 def _net(**kw):
-    from models.arch.OnlineSpatialNet import OnlineSpatialNet
-    torch.manual_seed(23)
-    args = dict(dim_input=4, dim_output=4, num_layers=2, dim_squeeze=8, num_freqs=F, dim_hidden=96, dim_ffn=192, num_heads=4, attention="ret(2)", full_share=0)
-    args.update(kw)
-    net = OnlineSpatialNet(**args).train()
-    with torch.no_grad():
-        for p in net.parameters():
-            if p.dim() == 1:
-                p.add_(0.2 * torch.randn_like(p))
-    return net
-
-
-def _grad_fns(t):
-    """names of every node of the autograd graph behind t"""
-    seen, todo, names = set(), [t.grad_fn], set()
-    while todo:
-        f = todo.pop()
-        if f is None or f in seen:
-            continue
-        seen.add(f)
-        names.add(type(f).__name__)
-        todo += [g for g, _ in f.next_functions]
-    return names
+    return online_net(23, F, **{"num_layers": 2, "full_share": 0, **kw})
 
 
 def _all_off(monkeypatch):
@@ -57,19 +34,11 @@ def reference(request):
     """the switch-off run in fp64 on the CPU: computed once per attention"""
     net = _net(attention=request.param)
     assert net.layers[1].full is net.layers[0].full  # full_share = 0: one LinearGroup for both layers
-    x, r = torch.randn(2, F, T, 4), torch.randn(2, F, T, 4)
-    n64 = copy.deepcopy(net).double()
-    y = n64(x.double())
-    (y * r.double()).sum().backward()
-    return net, x, r, y.detach(), {k: p.grad for k, p in n64.named_parameters()}
+    return fp64_reference(net, 2, F, T)
 
 
 def _check_against(net, y, wy, wg):
-    ey = rel_l2(y.detach().cpu(), wy)
-    errs = {k: rel_l2(p.grad.cpu(), wg[k]) for k, p in net.named_parameters()}
-    print(f"y {ey:.1e}; worst grad {max(errs, key=errs.get)} {max(errs.values()):.1e}; layers.0.full.weight {errs['layers.0.full.weight']:.1e}")
-    assert set(errs) == set(wg) and ey <= FWD_TOL, ey
-    assert max(errs.values()) <= GRAD_TOL, {k: v for k, v in errs.items() if v > GRAD_TOL}
+    check_against_fp64(y, {k: p.grad for k, p in net.named_parameters()}, wy, wg, FWD_TOL, GRAD_TOL, also=["layers.0.full.weight"])
 
 
 def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch):
@@ -78,10 +47,10 @@ def test_switch_on_matches_switch_off_fp64(backend, reference, monkeypatch):
     xd, rd = x.to(backend.device), r.to(backend.device)
     _all_off(monkeypatch)
     with online_train.use_lib(backend.lib):
-        assert NODE not in _grad_fns(net(xd))  # off by default
+        assert NODE not in grad_fns(net(xd))  # off by default
         monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
         y = net(xd)
-        names = _grad_fns(y)
+        names = grad_fns(y)
         assert NODE in names and "OnlineTConvFFNFnBackward" not in names and "OnlineRetentionFnBackward" not in names  # independent of the other two
         (y * rd).sum().backward()
         with pytest.raises(RuntimeError, match="second time|retain_graph"):
@@ -105,7 +74,7 @@ def test_all_three_switches_together(backend, reference, monkeypatch):
     with online_train.use_lib(backend.lib), warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)  # (mhsa model: the retention switch names its reason)
         y = net(xd)
-        assert want <= _grad_fns(y)
+        assert want <= grad_fns(y)
         (y * rd).sum().backward()
     _check_against(net, y, wy, wg)
 
@@ -138,7 +107,7 @@ def test_unsupported_layer_warns_once_and_runs_torch(backend, monkeypatch, kw, r
         with warnings.catch_warnings():
             warnings.simplefilter("error", RuntimeWarning)  # once per module and reason
             y2 = net(x)
-    assert NODE not in _grad_fns(y) and torch.equal(y, y_off) and torch.equal(y, y2)
+    assert NODE not in grad_fns(y) and torch.equal(y, y_off) and torch.equal(y, y2)
 
 
 def test_supported_says_why():
@@ -175,9 +144,9 @@ def test_streaming_call_never_takes_the_native_blocks(backend, monkeypatch):
         assert online_train.xband_eligible(net.layers[0], torch.zeros(1, F, 8, 96, device=backend.device), None) is None
         st = net.init_stream(1, device=backend.device)
         y = torch.cat([net.forward_stream(x[:, :, :4], st), net.forward_stream(x[:, :, 4:], st)], 2)
-        assert NODE not in _grad_fns(y)
+        assert NODE not in grad_fns(y)
         whole = net(x)
-    assert NODE in _grad_fns(whole)
+    assert NODE in grad_fns(whole)
     assert rel_l2(y.detach(), whole.detach()) < 1e-4  # (the streamed frames are the whole-utterance ones)
 
 
@@ -207,7 +176,7 @@ def test_257_frames_fall_back_with_gradients_and_run_natively_without(backend, m
         monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
         with pytest.warns(RuntimeWarning, match="with gradients T <= 256"):
             y = net(x)
-        assert NODE not in _grad_fns(y) and not calls
+        assert NODE not in grad_fns(y) and not calls
         # (torch's own modules both times, but not the same kernels with and without autograd on the device: fp32 against fp32, the forward bar)
         assert rel_l2(y.detach(), y_off) <= FWD_TOL
         with torch.no_grad(), warnings.catch_warnings():
@@ -233,7 +202,7 @@ def test_bf16_autocast(backend, monkeypatch):
     monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
     with online_train.use_lib(backend.lib), torch.autocast(backend.device.type, dtype=torch.bfloat16):
         y = lay._xband(xd)
-        assert y.dtype == torch.float32 and NODE in _grad_fns(y)
+        assert y.dtype == torch.float32 and NODE in grad_fns(y)
         with torch.no_grad():
             assert lay._xband(xd).dtype == torch.float32
     (y * r.to(backend.device)).sum().backward()
@@ -252,29 +221,7 @@ def test_bf16_autocast(backend, monkeypatch):
 def test_fit_on_the_device_with_the_switch(monkeypatch):
     """TrainCLI fit, configs/onlineSpatialNet.yaml, synthetic data, 2 layers, 1-s segments, two epochs of two steps: the first step's loss is the switch-off
     run's to 1e-4 relative, and the loss decreases"""
-    import SharedTrainer
-    from SharedTrainer import TrainCLI
     argv = ["fit", "--config", str(ROOT / "configs" / "onlineSpatialNet.yaml"), "--config", str(ROOT / "configs" / "datasets" / "synthetic.yaml"),
             "--model.arch.dim_input=12", "--model.arch.dim_output=4", "--model.arch.num_freqs=129", "--model.arch.num_layers=2", "--data.num_samples=[4,2,2]",
             "--data.audio_time_len=[1.0,1.0,1.0]", "--data.batch_size=[2,1]", "--trainer.max_epochs=2"]
-    steps = []
-    orig = SharedTrainer.TrainModule.training_step
-
-    def recording(self, *a, **k):
-        loss = orig(self, *a, **k)
-        steps.append((float(loss.detach()), NODE in _grad_fns(loss)))
-        return loss
-
-    monkeypatch.setattr(SharedTrainer.TrainModule, "training_step", recording)
-    _all_off(monkeypatch)
-    TrainCLI(argv=argv)
-    off, steps[:] = list(steps), []
-    monkeypatch.setenv("NBSS_ONLINE_NATIVE_XBAND", "1")
-    log = TrainCLI(argv=argv).result["log"]
-    on = list(steps)
-    print("switch off:", off, "\nswitch on: ", on)
-    assert len(log) == 2 and len(on) == len(off) == 4 and log[0]["device"].startswith("cuda")
-    assert not any(n for _, n in off) and all(n for _, n in on)
-    assert abs(on[0][0] - off[0][0]) <= 1e-4 * abs(off[0][0]), (on[0], off[0])
-    key = next(k for k in log[0] if k.startswith("train/"))
-    assert log[1][key] < log[0][key], log
+    fit_with_switch(monkeypatch, argv, ["NBSS_ONLINE_NATIVE_XBAND"], NODE)

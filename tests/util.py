@@ -1,4 +1,6 @@
 """helpers shared by the kernel parity tests"""
+import copy
+
 import torch
 
 from nbss_amd import ops
@@ -24,6 +26,85 @@ def rel_l2(a, b):
 
 def max_abs(a, b):
     return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
+
+
+# ---- the native blocks inside models.arch.OnlineSpatialNet (tests/test_online_*_train_module.py) ---------------------------------------------------------
+ONLINE_SWITCHES = ("NBSS_ONLINE_NATIVE_XBAND", "NBSS_ONLINE_NATIVE_TRAIN", "NBSS_ONLINE_NATIVE_RET")
+
+
+def online_net(seed, num_freqs, **kw):
+    """a small OnlineSpatialNet in train mode at the kernels' geometry, with non-trivial norm weights and biases"""
+    from models.arch.OnlineSpatialNet import OnlineSpatialNet
+    torch.manual_seed(seed)
+    args = dict(dim_input=4, dim_output=4, num_layers=1, dim_squeeze=8, num_freqs=num_freqs, dim_hidden=96, dim_ffn=192, num_heads=4, attention="ret(2)")
+    args.update(kw)
+    net = OnlineSpatialNet(**args).train()
+    with torch.no_grad():
+        for p in net.parameters():
+            if p.dim() == 1:
+                p.add_(0.2 * torch.randn_like(p))
+    return net
+
+
+def grad_fns(t):
+    """names of every node of the autograd graph behind t"""
+    seen, todo, names = set(), [t.grad_fn], set()
+    while todo:
+        f = todo.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        names.add(type(f).__name__)
+        todo += [g for g, _ in f.next_functions]
+    return names
+
+
+def fp64_reference(net, B, F, T):
+    """-> net, x, r, y, {name: grad}: the run of `net` (switches off) in fp64 on the CPU on random x [B,F,T,4], loss = sum(y r)"""
+    x, r = torch.randn(B, F, T, 4), torch.randn(B, F, T, 4)
+    n64 = copy.deepcopy(net).double()
+    y = n64(x.double())
+    (y * r.double()).sum().backward()
+    return net, x, r, y.detach(), {k: p.grad for k, p in n64.named_parameters()}
+
+
+def check_against_fp64(y, grads, wy, wg, fwd_tol, grad_tol, also=()):
+    """y and every gradient of {name: grad} against the fp64 run, rel-L2"""
+    ey = rel_l2(y.detach().cpu(), wy)
+    errs = {k: rel_l2(g.cpu(), wg[k]) for k, g in grads.items()}
+    print(f"y {ey:.1e}; worst grad {max(errs, key=errs.get)} {max(errs.values()):.1e}" + "".join(f"; {k} {errs[k]:.1e}" for k in also))
+    assert set(errs) == set(wg) and ey <= fwd_tol, ey
+    assert max(errs.values()) <= grad_tol, {k: v for k, v in errs.items() if v > grad_tol}
+
+
+def fit_with_switch(monkeypatch, argv, on, node):
+    """`TrainCLI fit` twice, with every switch off and with those of `on` set: four steps in two epochs each on the device, no step of the first run and
+    every step of the second has `node` in the graph of its loss, the first step's loss is the switch-off run's to 1e-4 relative, and the loss decreases"""
+    import SharedTrainer
+    from SharedTrainer import TrainCLI
+    steps = []
+    orig = SharedTrainer.TrainModule.training_step
+
+    def recording(self, *a, **k):
+        loss = orig(self, *a, **k)
+        steps.append((float(loss.detach()), node in grad_fns(loss)))
+        return loss
+
+    monkeypatch.setattr(SharedTrainer.TrainModule, "training_step", recording)
+    for s in ONLINE_SWITCHES:
+        monkeypatch.delenv(s, raising=False)
+    TrainCLI(argv=argv)
+    off, steps[:] = list(steps), []
+    for s in on:
+        monkeypatch.setenv(s, "1")
+    log = TrainCLI(argv=argv).result["log"]
+    on = list(steps)
+    print("switch off:", off, "\nswitch on: ", on)
+    assert len(log) == 2 and len(on) == len(off) == 4 and log[0]["device"].startswith("cuda")
+    assert not any(n for _, n in off) and all(n for _, n in on)
+    assert abs(on[0][0] - off[0][0]) <= 1e-4 * abs(off[0][0]), (on[0], off[0])
+    key = next(k for k in log[0] if k.startswith("train/"))
+    assert log[1][key] < log[0][key], log
 
 
 class Case:
