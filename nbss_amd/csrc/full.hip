@@ -4,8 +4,9 @@
 //  one F x F matrix per squeeze channel, shared by all layers when full_share=0).
 //
 // One workgroup = one (b, 8 consecutive frames) slab.  Only the squeezed activations
-// s[8][tt][F] and z[F][tt][8] live in LDS (38 KB bf16); the H-wide stream is streamed through
-// registers twice (squeeze pass, unsqueeze+residual pass — the second read hits L2/MALL).
+// s[8][tt][F] and z[F][tt][8] live in LDS (38 KB bf16); the H-wide stream is read twice (squeeze
+// pass, unsqueeze+residual pass — the second read hits L2/MALL), one tile ahead: through per-wave
+// LDS slots in the flagship instance (row slots, below), through registers in the others.
 //   pass 1  rows (f,tt) as MFMA N dim: LN in registers -> s = SiLU(Ws u + bs)
 //   pass 2  per squeeze channel c: z[:,tt] = Wf[c] (F x F) * s[c][tt][:]   (N = 8 frames)
 //   pass 3  y = x + SiLU(Wu z + bu)
@@ -28,6 +29,48 @@
 #define FL_KSF_MAX 5  // ceil(160 / 32): the 8-kHz geometry (F <= 160)
 #define FL_KSF_BIG 9  // ceil(272 / 32): 16 kHz (n_fft 512 -> F = 257)
 #define FL_THREADS 512  // 8 waves: one workgroup per CU (256 slabs), so the waves of a workgroup are all the latency hiding there is
+
+// a wave-uniform value, known as such to the compiler (address arithmetic built on it stays in SGPRs)
+NBSS_DEV int wave_uniform(int v) {
+#ifdef NBSS_EMU
+    return v;
+#else
+    return __builtin_amdgcn_readfirstlane(v);
+#endif
+}
+// this wave's LDS reads have returned (lgkmcnt(0); vmcnt untouched)
+NBSS_DEV void lds_wait() {
+#ifndef NBSS_EMU
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+#endif
+}
+
+// Row slots (bf16 stream, 8-frame slabs, H = 96): every wave owns one slot that holds ONE row tile of the H-wide stream (16 rows x 192 bytes, the rows'
+// memory image), filled by LDS-DMA while the wave works on the tile before it — no registers in flight — and read back in the register layout the
+// global loads produced.  A tile image is 192 pieces of 16 bytes: piece p = row p / 12 (= 8 x frequency of the pair + frame), bytes 16 (p % 12) of
+// the row; a lane's three pieces keep their frame / column offset for a whole pass (row_tile_pieces), a tile adds its two wave-uniform frequency rows.
+// FL_ROW_SLOTS=0 builds the kernels without the slots (A/B flavour: the row passes load through registers as before).
+#ifndef FL_ROW_SLOTS
+#define FL_ROW_SLOTS 1
+#endif
+#define FL_ROW_TILE (16 * FL_H * 2)                 // bytes of a 16-row bf16 tile
+template <class T, int HH, int TT> constexpr bool full_row_slots() { return FL_ROW_SLOTS && sizeof(T) == 2 && TT == 8 && HH == FL_H; }
+NBSS_DEV void row_tile_pieces(int lane, int t0, int T_, int (&pcst)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int p = 64 * i + lane, r = p / 12, tq = t0 + (r & 7);
+        pcst[i] = (tq < T_ ? tq : T_ - 1) * FL_H + (p - 12 * r) * 8;
+    }
+}
+// row tile ntn (wave-uniform) of utterance b: frequencies 2 ntn and 2 ntn + 1, clamped like every prefetch address of this file
+template <class T>
+NBSS_DEV void row_tile_request(char* dst, const T* __restrict__ src, int b, int F, int T_, int ntn, int lane, const int (&pcst)[3]) {
+    const int f0 = 2 * ntn < F ? 2 * ntn : F - 1, f1 = 2 * ntn + 1 < F ? 2 * ntn + 1 : F - 1;
+    const size_t r0 = ((size_t)b * F + f0) * T_ * FL_H, r1 = ((size_t)b * F + f1) * T_ * FL_H;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        dma16_to_lds(dst + i * 1024, src + (i == 0 || (i == 1 && lane < 32) ? r0 : r1) + pcst[i]);  // pieces 0..95: the first frequency of the pair
+}
 
 
 // LinearGroup pass: task = (squeeze channel ch, 16-row tile mt of the F x F matrix), acc = W[ch] tile x s[ch][:, tt]; the body between BEGIN and
@@ -65,6 +108,9 @@
         }
 #define FL_TASK_LOOP_END }
 
+// the forward kernel has its row slots where two workgroups still share a CU with them (F <= 160; at F = 257 the images alone are 71 680 bytes)
+template <class T, int KSFM, int HH, int TT> constexpr bool full_fwd_slots() { return full_row_slots<T, HH, TT>() && KSFM == FL_KSF_MAX; }
+
 // KSFM: LinearGroup k-steps the fragment arrays are sized for; HH / NSQ = dim_hidden / dim_squeeze (geom.h)
 template <class T, int KSFM, int HH, int NSQ, int TT>
 __global__ __launch_bounds__(FL_THREADS, HH == 96 && TT == 8 ? 4 : 1)  // small geometry, full grids: <= 128 VGPRs, two workgroups per CU
@@ -84,8 +130,19 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int lane = lane_id(), l15 = lane & 15, g4 = lane >> 4, w = wave_id(), nw = nthr >> 6;
     const int ntile = cdiv(F, 16 / TT);  // n-tiles of (16 / TT freqs x TT frames)
+    // behind the images: the row slots (one x tile per wave: both row passes read the same rows) and the two bias rows the row passes read per
+    // tile — as global loads inside `if (valid)` each of them waited for everything the wave had in flight, the rows requested ahead included
+    constexpr bool SLOTS = full_fwd_slots<T, KSFM, HH, TT>();
+    char* slots = reinterpret_cast<char*>(z + FM * TT * NSQ);
+    float* prm = reinterpret_cast<float*>(slots + (SLOTS ? (FL_THREADS / 64) * FL_ROW_TILE : 0));  // bu [HH] | bs [NSQ]
+    const int wu = wave_id_u();
+    char* slot = slots + (size_t)wu * FL_ROW_TILE;
+    int pcst[3];
+    row_tile_pieces(lane, t0, T_, pcst);
+    if (SLOTS && wu < ntile) row_tile_request(slot, x, b, F, T_, wu, lane, pcst);  // pass 1's first tile: in flight during the zero fill
 
     for (int i = tid; i < NSQ * TT * FK + FM * TT * NSQ; i += nthr) store1(s + i, 0.f);
+    for (int i = tid; i < HH + NSQ; i += nthr) prm[i] = i < HH ? bu[i] : bs[i - HH];
     lds_barrier();
 
     // ---- pass 1: LN + squeeze + SiLU ---------------------------------------------------------
@@ -103,7 +160,7 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
             return x + (((size_t)b * F + (f < F ? f : F - 1)) * T_ + tclf) * HH;
         };
         Frag<T> xnext[(HH / 32)];
-        if (w < ntile) {
+        if (!SLOTS && w < ntile) {
 #pragma unroll
             for (int ks = 0; ks < (HH / 32); ++ks) frag_load(xnext[ks], row_of_f(w) + ks * 32 + 8 * g4);
         }
@@ -111,9 +168,20 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
             const int f = (16 / TT) * nt + (l15 / TT), tt = l15 % TT;
             const bool valid = f < F && t0 + tt < T_;
             Frag<T> xcur[(HH / 32)];
+            if constexpr (SLOTS) {
+                const int ntu = wave_uniform(nt);
+                dma_wait_all();   // this tile's copy, requested one tile ago
+                wave_lds_sync();  // (a lane reads pieces that other lanes of its wave copied)
+                const T* xs = reinterpret_cast<const T*>(slot) + l15 * HH + 8 * g4;  // lane = row l15 of the tile, B-fragment layout
 #pragma unroll
-            for (int ks = 0; ks < (HH / 32); ++ks) xcur[ks] = xnext[ks];
-            {
+                for (int ks = 0; ks < (HH / 32); ++ks) frag_load(xcur[ks], xs + ks * 32);
+                lds_wait();  // the slot has been read: the next tile may land in it
+                wave_lds_sync();
+                // after the wave's last tile: the FIRST tile of pass 3 (the same rows), in flight during the LinearGroup pass
+                row_tile_request(slot, x, b, F, T_, ntu + nw < ntile ? ntu + nw : wu, lane, pcst);
+            } else {
+#pragma unroll
+                for (int ks = 0; ks < (HH / 32); ++ks) xcur[ks] = xnext[ks];
                 const T* nx = row_of_f(nt + nw < ntile ? nt + nw : nt);
 #pragma unroll
                 for (int ks = 0; ks < (HH / 32); ++ks) frag_load(xnext[ks], nx + ks * 32 + 8 * g4);
@@ -136,7 +204,7 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int ch = 4 * g4 + r;
-                    store1(s + ((size_t)ch * TT + tt) * FK + f, silu_f(acc[r] + bs[ch]));
+                    store1(s + ((size_t)ch * TT + tt) * FK + f, silu_f(acc[r] + prm[HH + ch]));
                 }
             }
         }
@@ -169,7 +237,7 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
             return x + (((size_t)b * F + (f < F ? f : F - 1)) * T_ + tcl3) * HH;
         };
         RawC4<T> rnext[(HH / 16)];
-        if (w < ntile) {
+        if (!SLOTS && w < ntile) {
 #pragma unroll
             for (int mt = 0; mt < (HH / 16); ++mt) rawc_load(rnext[mt], row_of_3(w) + 16 * mt + 4 * g4);
         }
@@ -177,9 +245,19 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
             const int f = (16 / TT) * nt + (l15 / TT), tt = l15 % TT;
             const bool valid = f < F && t0 + tt < T_;
             RawC4<T> rcur[(HH / 16)];
+            if constexpr (SLOTS) {  // (as in pass 1; the first tile was requested at the end of pass 1)
+                const int ntu = wave_uniform(nt);
+                dma_wait_all();
+                wave_lds_sync();
+                const T* xs = reinterpret_cast<const T*>(slot) + l15 * HH + 4 * g4;  // lane = row l15 of the tile, C layout
 #pragma unroll
-            for (int mt = 0; mt < (HH / 16); ++mt) rcur[mt] = rnext[mt];
-            {
+                for (int mt = 0; mt < (HH / 16); ++mt) rawc_load(rcur[mt], xs + 16 * mt);
+                lds_wait();
+                wave_lds_sync();
+                row_tile_request(slot, x, b, F, T_, ntu + nw < ntile ? ntu + nw : ntu, lane, pcst);  // (unconditional: the last tile is copied twice)
+            } else {
+#pragma unroll
+                for (int mt = 0; mt < (HH / 16); ++mt) rcur[mt] = rnext[mt];
                 const T* nx = row_of_3(nt + nw < ntile ? nt + nw : nt);
 #pragma unroll
                 for (int mt = 0; mt < (HH / 16); ++mt) rawc_load(rnext[mt], nx + 16 * mt + 4 * g4);
@@ -197,11 +275,12 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
                     rawc_get(rcur[mt], xv);
                     float o[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = xv[r] + round_to(silu_f(acc[r] + bu[ch + r]), x);
+                    for (int r = 0; r < 4; ++r) o[r] = xv[r] + round_to(silu_f(acc[r] + prm[ch + r]), x);
                     store4(y + go + ch, o[0], o[1], o[2], o[3]);
                 }
             }
         }
+        if (SLOTS) dma_wait_all();  // (the last tile's second copy)
     }
 }
 
@@ -216,11 +295,20 @@ void full_fwd_kernel(nbss_cfg c, const float* __restrict__ lnw, const float* __r
 // The three weight gradients (squeeze, LinearGroup, unsqueeze) are contracted by wgrad.hip.
 #define FL_FKP(F) (((F) + 3) & ~3)   // padded F stride of the global s / dz operands
 #define FL_WFR 15  // weight fragments staged in LDS by the backward kernel: Wusq 6 | WusqT 3 | WsqT 6
+#define FL_WFR3 9  // ... of which p3 reads the first nine, p5 the last six
+
+// Row slots of p5 (above: full_row_slots): a slot of the backward kernel holds the x tile and the dy tile of one row tile.  The slots lie over what is
+// dead in p5 — the s / dz image, the s_pre image and p3's nine weight fragments (the backward kernel's LDS starts with these three, padded to the
+// slots' size).  At F = 129: 49 152 (front, 1 024 of them padding) + 18 432 (z) + 6 144 + 544 + 768 (parameter rows) = 75 040 bytes, 1 792 more than
+// without slots and parameter rows, two workgroups per CU as before.  A ring of whole tiles BESIDE the images does not fit: without the slots the
+// kernel holds 74 016 of the 81 920 bytes a workgroup may have, 7 904 free = 2.6 tiles for eight waves.
+#define FL_SLOT (2 * FL_ROW_TILE)                   // x | dy
+#define FL_SLOTS_BYTES ((FL_THREADS / 64) * FL_SLOT)
 
 template <class T, int KSFM, int TT>
-// bf16 stream: <= 128 VGPRs (a few spilled registers) so that two workgroups share a CU: 4.72 -> 4.17 ms per step together with the LDS-resident
-// weight fragments and the LayerNorm affine sums moved out of the row loop; the software prefetch of the row loops (round 2: worth 10 % at one
-// workgroup per CU) costs more registers than it hides latency at two (4.57 with, 4.17 without)
+// bf16 stream: <= 128 VGPRs so that two workgroups share a CU: 4.72 -> 4.17 ms per step together with the LDS-resident weight fragments and the
+// LayerNorm affine sums moved out of the row loop.  p5's rows come in through per-wave LDS slots (no registers in flight), p3's dy rows through a
+// one-tile register prefetch, and the parameter rows of p3 / p5 are read from LDS (no spills in the flagship instance)
 __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void full_bwd_kernel(nbss_cfg c, LayerPtrs lp, const float* __restrict__ P, float* __restrict__ part, int layer,
                                                        const T* __restrict__ Wsq, const T* __restrict__ Wfull, const T* __restrict__ Wusq,
                                                        const T* __restrict__ WsqT, const T* __restrict__ WfullT, const T* __restrict__ WusqT,
@@ -232,12 +320,15 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
     const int mtf = cdiv(F, 16), ksf = cdiv(F, 32), FK = ksf * 32, FM = mtf * 16, FKP = FL_FKP(F);
     T* s = reinterpret_cast<T*>(smem);             // [SQ][TT][FK]   s, later dz
     T* sp = s + FL_SQ * TT * FK;                // [FM][TT][SQ]   s_pre
-    T* z = sp + FM * TT * FL_SQ;                // [FM][TT][SQ]   z, later ds_pre
-    float* aff = reinterpret_cast<float*>(z + FM * TT * FL_SQ);  // [SQ][17] squeeze bias gradient sums (fp32), one slot per (channel, frequency tile) task —
+    T* wl3 = sp + FM * TT * FL_SQ;              // [FL_WFR3][512] p3's weight fragments (below)
+    constexpr bool SLOTS = full_row_slots<T, FL_H, TT>();
+    const size_t front = (size_t)((wl3 + FL_WFR3 * 512) - s) * sizeof(T);  // s | s_pre | p3's fragments: dead in p5, where the row slots lie over them
+    T* z = reinterpret_cast<T*>(smem + (SLOTS && front < FL_SLOTS_BYTES ? (size_t)FL_SLOTS_BYTES : front));  // [FM][TT][SQ]   z, later ds_pre
+    float* aff =reinterpret_cast<float*>(z + FM * TT * FL_SQ);  // [SQ][17] squeeze bias gradient sums (fp32), one slot per (channel, frequency tile) task —
                                                                  // added in tile order at the end (waves adding to one slot with LDS atomics: order-dependent bits)
     // the unsqueeze / squeeze weight fragments of the two row loops live in LDS, not in 60 registers per lane: with the LayerNorm affine
     // sums gone as well (below) the kernel fits 128 VGPRs and TWO workgroups share a CU — its row loops are bound by exposed latency
-    T* wl = reinterpret_cast<T*>(aff + FL_SQ * 17);                    // [FL_WFR][512]
+    T* wl5 = reinterpret_cast<T*>(aff + FL_SQ * 17);                   // [FL_WFR - FL_WFR3][512] p5's weight fragments
     const int ntt = cdiv(T_, TT);
     const int bid = flip_bid(flip);  // (launch.h: consecutive kernels of a walk traverse the utterances in opposite order)
     const int b = bid / ntt, t0 = (bid % ntt) * TT;
@@ -250,17 +341,26 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
     const float* bfull = lp.p[P_FULL_B];
     const float* bu = lp.p[P_USQ_B];
 
-    for (int i = tid; i < FL_SQ * TT * FK + 2 * FM * TT * FL_SQ; i += nthr) store1(s + i, 0.f);
+    for (int i = tid; i < FL_SQ * TT * FK + FM * TT * FL_SQ; i += nthr) store1(s + i, 0.f);
+    for (int i = tid; i < FM * TT * FL_SQ; i += nthr) store1(z + i, 0.f);
     for (int i = tid; i < FL_SQ * 17; i += nthr) aff[i] = 0.f;
     {
         constexpr int VPF = 512 * (int)sizeof(T) / 16;  // 16-byte pieces per fragment (64 bf16, 128 fp32)
         for (int v = tid; v < FL_WFR * VPF; v += nthr) {
             const int fr = v / VPF, pc = v % VPF;
             const T* src = fr < 6 ? Wusq + (size_t)fr * 512 : fr < 9 ? WusqT + (size_t)(fr - 6) * 512 : WsqT + (size_t)(fr - 9) * 512;
-            reinterpret_cast<u32x4*>(wl)[v] = reinterpret_cast<const u32x4*>(src)[pc];
+            T* dst = fr < FL_WFR3 ? wl3 + (size_t)fr * 512 : wl5 + (size_t)(fr - FL_WFR3) * 512;
+            reinterpret_cast<u32x4*>(dst)[pc] = reinterpret_cast<const u32x4*>(src)[pc];
         }
     }
-    PHASE_BEGIN(wl + FL_WFR * 512);
+    // the two parameter rows the row loops of p3 / p5 read per tile (unsqueeze bias, LayerNorm weight) in LDS as well: as global loads each of them
+    // waited for everything the wave had in flight (one in-order vmcnt) — the rows requested ahead for the NEXT tile included
+    float* prm = reinterpret_cast<float*>(wl5 + (FL_WFR - FL_WFR3) * 512);  // [2][FL_H]: bu | lnw
+    for (int i = tid; i < FL_H; i += nthr) {
+        prm[i] = bu[i];
+        prm[FL_H + i] = lnw[i];
+    }
+    PHASE_BEGIN(prm + 2 * FL_H);
     lds_barrier();
     PHASE(0);
 
@@ -330,15 +430,14 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
 
     // ---- p3: recompute y_pre, dy_pre, dz = Wu^T dy_pre (dz overwrites s) ----
     {
-        const T* wa = wl + (size_t)lane * 8;  // fragment fr of the window: wa + fr * 512
+        const T* wa = wl3 + (size_t)lane * 8;  // fragment fr of the window: wa + fr * 512
         // software pipeline: the dy pieces of the wave's NEXT row tile are requested before this tile's math (clamped addresses)
         const int tcl = t0 + (l15 % TT) < T_ ? t0 + (l15 % TT) : T_ - 1;
         auto row_of = [&](int nt) -> size_t {
             const int f = (16 / TT) * nt + (l15 / TT);
             return ((size_t)b * F + (f < F ? f : F - 1)) * T_ + tcl;
         };
-        // (round 6, under the file's iterative-minreg schedule: 469 / 475 -> 460 / 466 us per launch with the prefetch in THIS pass — twelve registers;
-        //  in p5, twenty-four registers and 55 instead of 28 spilled: 561 us)
+        // (twelve registers; it overlaps the tile's math only since bu is read from LDS — as global loads in a branch, each waited with vmcnt(0))
         constexpr bool PF = true;
         RawC4<T> dnext[BK_MT];
         if (PF && w < ntile) rawc_load_row<T>(dnext, dy + row_of(w) * FL_H);
@@ -376,7 +475,7 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
                 float dv[4];
                 rawc_get(dcur[mt], dv);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dyp[mt][r] = valid ? dv[r] * dsilu_f(acc[r] + bu[ch + r]) : 0.f;
+                for (int r = 0; r < 4; ++r) dyp[mt][r] = valid ? dv[r] * dsilu_f(acc[r] + prm[ch + r]) : 0.f;
                 if (valid) store4(dyp_out + n * FL_H + ch, dyp[mt][0], dyp[mt][1], dyp[mt][2], dyp[mt][3]);
             }
             f32x4 dzt = F32X4_ZERO;
@@ -429,7 +528,7 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
 
     // ---- p5: du = Ws^T ds_pre, LayerNorm backward + residual ----
     {
-        const T* wa = wl + (size_t)(9 * 512) + (size_t)lane * 8;  // the six Ws^T fragments
+        const T* wa = wl5 + (size_t)lane * 8;  // the six Ws^T fragments
         // (no LayerNorm affine sums here: dgamma / dbeta follow from the squeeze weight gradient itself, D = ds_pre^T xhat —
         //  dgamma[i] = sum_o Ws[o][i] D[o][i], dbeta[i] = sum_o Ws[o][i] dbs[o] — in full_sq_finalize_kernel; 48 accumulators per lane gone)
         const int tcl = t0 + (l15 % TT) < T_ ? t0 + (l15 % TT) : T_ - 1;
@@ -437,23 +536,34 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
             const int f = (16 / TT) * nt + (l15 / TT);
             return ((size_t)b * F + (f < F ? f : F - 1)) * T_ + tcl;
         };
-        constexpr bool PF = false;  // (see p3)
-        RawC4<T> xnext[BK_MT], dnext[BK_MT];
-        if (PF && w < ntile) {
-            rawc_load_row<T>(xnext, x + row_of(w) * FL_H);
-            rawc_load_row<T>(dnext, dy + row_of(w) * FL_H);
-        }
+        // row slots (FL_SLOT): the wave's NEXT x and dy tile are copied global -> LDS while this one is worked on, no registers in flight
+        const int wu = wave_id_u();
+        char* slot = smem + (size_t)wu * FL_SLOT;
+        int pcst[3];
+        row_tile_pieces(lane, t0, T_, pcst);
+        auto slot_request = [&](int ntn) {  // ntn: wave-uniform
+            row_tile_request(slot, x, b, F, T_, ntn, lane, pcst);
+            row_tile_request(slot + FL_ROW_TILE, dy, b, F, T_, ntn, lane, pcst);
+        };
+        if (SLOTS && wu < ntile) slot_request(wu);
         for (int nt = w; nt < ntile; nt += nw) {
             const int f = (16 / TT) * nt + (l15 / TT), tt = l15 % TT;
             const bool valid = f < F && t0 + tt < T_;
             const size_t n = ((size_t)b * F + f) * T_ + t0 + tt;
             RawC4<T> xcur[BK_MT], dcur[BK_MT];
-            if (PF) {
+            if constexpr (SLOTS) {
+                const int ntu = wave_uniform(nt);
+                dma_wait_all();   // this tile's copies, requested one iteration ago (behind them in the queue: the previous tile's stores only)
+                wave_lds_sync();  // (a lane reads pieces that other lanes of its wave copied)
+                const T* xs = reinterpret_cast<const T*>(slot) + l15 * FL_H + 4 * g4;  // lane = row l15 of the tile, C layout
 #pragma unroll
-                for (int mt = 0; mt < BK_MT; ++mt) { xcur[mt] = xnext[mt]; dcur[mt] = dnext[mt]; }
-                const size_t nn = row_of(nt + nw < ntile ? nt + nw : nt);
-                rawc_load_row<T>(xnext, x + nn * FL_H);
-                rawc_load_row<T>(dnext, dy + nn * FL_H);
+                for (int mt = 0; mt < BK_MT; ++mt) {
+                    rawc_load(xcur[mt], xs + 16 * mt);
+                    rawc_load(dcur[mt], xs + 16 * FL_H + 16 * mt);
+                }
+                lds_wait();  // the slot has been read: the next tile may land in it
+                wave_lds_sync();
+                slot_request(ntu + nw < ntile ? ntu + nw : ntu);  // (unconditional, like every prefetch of this file: the last tile is copied twice)
             } else {
                 rawc_load_row<T>(xcur, x + row_of(nt) * FL_H);
                 rawc_load_row<T>(dcur, dy + row_of(nt) * FL_H);
@@ -475,8 +585,9 @@ __global__ __launch_bounds__(FL_THREADS, sizeof(T) == 2 && TT == 8 ? 4 : 2) void
                 frag_load(am, wa + mt * 512);
                 du[mt] = mma(am, bq, F32X4_ZERO);
             }
-            ln_bwd_row_raw<true>(du, xcur, dcur, dx + n * FL_H, stats + n * 2, valid, lnw);
+            ln_bwd_row_raw<true>(du, xcur, dcur, dx + n * FL_H, stats + n * 2, valid, prm + FL_H);
         }
+        if (SLOTS) dma_wait_all();  // (the last tile's second copy)
     }
     PHASE(9);
     lds_barrier();
@@ -518,8 +629,12 @@ static int full_tt(const nbss_cfg& c) {
 static size_t full_bwd_lds(const nbss_cfg& c, int tt) {
     const size_t esz = c.dtype == NBSS_BF16 ? 2 : 4;
     const int mtf = cdiv(c.F, 16), ksf = cdiv(c.F, 32);
-    return ((size_t)FL_SQ * tt * ksf * 32 + (size_t)2 * mtf * 16 * tt * FL_SQ + (size_t)FL_WFR * 512) * esz + FL_SQ * 17 * sizeof(float) + PHASE_LDS_BYTES;
+    // s | s_pre | p3's fragments, padded to p5's row slots where the kernel has them (full_row_slots) — z | aff | p5's fragments
+    size_t front = ((size_t)FL_SQ * tt * ksf * 32 + (size_t)mtf * 16 * tt * FL_SQ + (size_t)FL_WFR3 * 512) * esz;
+    if (FL_ROW_SLOTS && c.dtype == NBSS_BF16 && tt == 8 && front < FL_SLOTS_BYTES) front = FL_SLOTS_BYTES;
+    return front + ((size_t)mtf * 16 * tt * FL_SQ + (size_t)(FL_WFR - FL_WFR3) * 512) * esz + (FL_SQ * 17 + 2 * FL_H) * sizeof(float) + PHASE_LDS_BYTES;
 }
+static_assert(full_row_slots<bf16_t, FL_H, 8>() == (FL_ROW_SLOTS != 0) && !full_row_slots<float, FL_H, 8>() && !full_row_slots<bf16_t, FL_H, 4>(), "full_bwd_lds");
 // ... and the width the backward pass runs at: full_tt(), narrowed until the squeezed images fit (fp32 stream at F = 257: 213 KB at 8 frames, 136 KB at 4)
 static int full_bwd_width(const nbss_cfg& c) {
     int tt = full_tt(c);
@@ -637,7 +752,9 @@ template <class T, int KSFM, class G, int TT>
 static int full_fwd_tt(const nbss_cfg& c, const float* P, const void* packed, int layer, const void* x, void* y, hipStream_t st) {
     const LayerPtrs lp = layer_ptrs(c, P, layer);
     const int mtf = cdiv(c.F, 16), ksf = cdiv(c.F, 32);
-    const size_t lds = ((size_t)G::SQ * TT * ksf * 32 + (size_t)mtf * 16 * TT * G::SQ) * sizeof(T);
+    // s | z | row slots (at F = 129: 38 912 + 24 576 of the 81 920 bytes a workgroup may hold at two per CU; a second tile per wave would not fit) | bu, bs
+    const size_t lds = ((size_t)G::SQ * TT * ksf * 32 + (size_t)mtf * 16 * TT * G::SQ) * sizeof(T) +
+                       (full_fwd_slots<T, KSFM, G::H, TT>() ? (size_t)(FL_THREADS / 64) * FL_ROW_TILE : 0) + (G::H + G::SQ) * sizeof(float);
     const T* pk = (const T*)packed;
     if (ksf > KSFM || lds > 160 * 1024) return NBSS_EUNSUPPORTED;
     int e = NBSS_SET_MAX_LDS((full_fwd_kernel<T, KSFM, G::H, G::SQ, TT>), lds);
