@@ -447,6 +447,36 @@ int nbss_online_ret_train_fwd(int dtype, int64_t BF, int T, const void* q, const
 int nbss_online_ret_train_bwd(int dtype, int64_t BF, int T, const void* q, const void* k, const void* v, const void* g, float k_scale,
                               const float* decay, const void* save, const void* d_out, void* dq, void* dk, void* dv, void* dg, void* ws, void* stream);
 
+/* ---- OnlineSpatialNet: the whole retention block for training (csrc/online_tsa_train.hip; nbss_amd/online_train.py) ---------------------------
+ * y = x + out_proj(SiLU(g) * RMSNorm_head(chunk_retention(q, k, v))) with u = LayerNorm(x) (eps 1e-5, affine), q = wq u, k = 24^-0.5 wk u, v = wv u,
+ * g = wg u — `SpatialNetLayer._tsa` of models/arch/OnlineSpatialNet.py with attention 'ret(2,*)' plus the residual of its caller — on BF sequences of T
+ * frames, forward and backward.  x, y, dy, dx [BF][T][96], contiguous and of `dtype` (NBSS_F32: fp32 MFMA; NBSS_BF16: bf16 MFMA operands, fp32
+ * accumulation; LayerNorm, RMS and decay statistics fp32 in either).  The parameters are the module's own fp32 tensors in state_dict layout, without
+ * bias: ln_w ln_b [96], wq wk [96][96], wv wg [192][96], wo [96][192]; decay [4]: the per-head gamma (fp32, on the device).  The core between the
+ * projections and out_proj is nbss_online_ret_train_fwd / _bwd (4 heads, key width 24, value width 48, chunks of 64 frames, no rotary positions, no
+ * look-ahead); out_proj with the residual is nbss_nb_conv_t with taps = 1 (the same launches: y has the bits of chaining the two on the saved q, k, v, g).
+ * wk = NULL: shared keys ('share_qk': k = q, unscaled); then d_wk must be NULL, and `share_qk` of the two *_bytes calls must be non-zero.
+ * save: nbss_online_tsa_save_bytes() bytes that the forward fills for the backward, each piece 256-byte aligned: q [BF][T][96] | k (absent with shared
+ *   keys) | v [BF][T][192] | g | the gated core output (the input of out_proj) [BF][T][192], all of `dtype` | (mean, rstd) [BF][T][2] fp32 | the core's
+ *   chunk states (nbss_online_ret_train_save_bytes()).  The gated core output is KEPT, not recomputed (it is the operand of d_wo; the core's backward never
+ *   writes it).  Per token: NBSS_F32 3 368 bytes, NBSS_BF16 1 832 (shared keys: 384 / 192 less).  u = LayerNorm(x) is never stored by the forward; the
+ *   backward recomputes it into `ws` for the weight gradients.  save = NULL: forward only (inference), nothing is kept.
+ * ws: nbss_online_tsa_ws_bytes() bytes of scratch, for either call (it holds the workspace of nbss_nb_conv_t_bwd, ~62 MB: allocate it once per shape).
+ * bwd: dx includes the residual path; the seven d_* buffers are WRITTEN (not accumulated; they may be uninitialised): the call zeroes them before the
+ *   accumulating building blocks (nbss_nb_conv_t_bwd, the fold of the LayerNorm partial rows) add to them.
+ * NBSS_EINVAL: dtype outside {NBSS_F32, NBSS_BF16}, BF < 1, a NULL pointer other than wk, d_wk or the forward's `save`, d_wk without wk or wk without
+ * d_wk, y == x, dx == dy, dx == x.  NBSS_EUNSUPPORTED: T outside 1 .. NBSS_T_MAX (4096), more than 2^28 tokens.  The two *_bytes calls return the same
+ * codes (negative) instead of a size.  Nothing is launched after a refusal.
+ * One workgroup per 128 rows in the two projection kernels (no grid cap).  No atomics, every sum in a fixed order: two calls give the same bits, and a
+ * sequence's rows of y and dx do not depend on the other sequences of the launch. */
+int64_t nbss_online_tsa_save_bytes(int dtype, int64_t BF, int T, int share_qk);
+int64_t nbss_online_tsa_ws_bytes(int dtype, int64_t BF, int T, int share_qk);
+int nbss_online_tsa_train_fwd(int dtype, int64_t BF, int T, const float* ln_w, const float* ln_b, const float* wq, const float* wk, const float* wv,
+                              const float* wg, const float* wo, const float* decay, const void* x, void* y, void* save, void* ws, void* stream);
+int nbss_online_tsa_train_bwd(int dtype, int64_t BF, int T, const float* ln_w, const float* ln_b, const float* wq, const float* wk, const float* wv,
+                              const float* wg, const float* wo, const float* decay, const void* x, const void* save, const void* dy, void* dx,
+                              float* d_ln_w, float* d_ln_b, float* d_wq, float* d_wk, float* d_wv, float* d_wg, float* d_wo, void* ws, void* stream);
+
 /* ---- OnlineSpatialNet: the cross-band trio for training (csrc/online_xband_train.hip; nbss_amd/online_train.py) -------------------------------
  * x1 = x + fconv1(x), x2 = x1 + full(x1), y = x2 + fconv2(x2) of models/arch/OnlineSpatialNet.py `SpatialNetLayer.forward` on x, y [B][F][T][96] of
  * `dtype`, forward and backward, through the SpatialNet-small kernels behind nbss_fconv_fwd / nbss_full_fwd and their _bwd (the same launches: the results

@@ -90,8 +90,15 @@ class SpatialNetLayer(nn.Module):
     def forward(self, x: Tensor, att_mask=None, chunkwise_recurrent: bool = True, rope=True, state: Dict[int, Any] = None, inference: bool = False):
         """x [B,F,T,H] -> (x, attention weights or None)"""
         x = self._xband(x, state)
-        a, attn = self._tsa(x, att_mask, chunkwise_recurrent, rope, state=state, inference=inference)
-        x = x + a
+        # x + the whole retention block (LayerNorm, projections, chunkwise core, out_proj) runs as ONE autograd node through the HIP kernels of
+        # nbss_amd/online_train.py when the switch of its TSA block is on (off by default) and `take` accepts the call; it wins over RETENTION in `_tsa`
+        from nbss_amd import online_train
+        if isinstance(self.mhsa, MultiScaleRetention) and online_train.take(online_train.TSA, self, x, state is not None or inference, att_mask,
+                                                                              chunkwise_recurrent, rope):
+            x, attn = online_train.tsa_residual(self, x, att_mask, chunkwise_recurrent, rope), None
+        else:
+            a, attn = self._tsa(x, att_mask, chunkwise_recurrent, rope, state=state, inference=inference)
+            x = x + a
         x = self._tconvffn(x, state=state, residual=True)
         return x, attn
 

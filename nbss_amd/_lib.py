@@ -116,6 +116,10 @@ SIGNATURES = {
     "nbss_online_ret_train_ws_bytes": (C.c_int64, [_I, C.c_int64, _I]),
     "nbss_online_ret_train_fwd": (_I, [_I, C.c_int64, _I, _P, _P, _P, _P, C.c_float] + [_P] * 5),
     "nbss_online_ret_train_bwd": (_I, [_I, C.c_int64, _I, _P, _P, _P, _P, C.c_float] + [_P] * 9),
+    "nbss_online_tsa_save_bytes": (C.c_int64, [_I, C.c_int64, _I, _I]),
+    "nbss_online_tsa_ws_bytes": (C.c_int64, [_I, C.c_int64, _I, _I]),
+    "nbss_online_tsa_train_fwd": (_I, [_I, C.c_int64, _I] + [_P] * 13),
+    "nbss_online_tsa_train_bwd": (_I, [_I, C.c_int64, _I] + [_P] * 21),
     "nbss_online_stft_step": (_I, [_I] * 6 + [_P] * 7),
     "nbss_online_istft_step": (_I, [_I] * 5 + [_P] * 6),
     "nbss_nb_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),

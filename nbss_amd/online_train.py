@@ -1,17 +1,19 @@
-"""Native training paths of the OnlineSpatialNet's three blocks, each behind an opt-in switch of its own (off unless exactly '1', read at call time,
+"""Native training paths of the OnlineSpatialNet's blocks, each behind an opt-in switch of its own (off unless exactly '1', read at call time,
 independent of the others):
 
     TCONVFFN   NBSS_ONLINE_NATIVE_TRAIN   csrc/online_train.hip        x + causal T-ConvFFN(x) on the [B,F,T,96] stream        OnlineTConvFFNFn
     RETENTION  NBSS_ONLINE_NATIVE_RET     csrc/online_ret_train.hip    the chunkwise retention core between the projections    OnlineRetentionFn
     XBAND      NBSS_ONLINE_NATIVE_XBAND   csrc/online_xband_train.hip  x + fconv1, + full-band, + fconv2 as one node           OnlineXBandFn
+    TSA        NBSS_ONLINE_NATIVE_TSA     csrc/online_tsa_train.hip    x + the whole retention block (LayerNorm, the four      OnlineTSAFn
+                                                                       projections, the core, out_proj) as one node
 
 A block is one `Block` record: its switch, its label, its `supported` and the checks of the call.  Everything else is written once.  `take` is what
 `models.arch.OnlineSpatialNet.SpatialNetLayer` asks per call: the common gate (`_gate`: switch, streaming call, device, library, geometry, stream dtype — fp32,
 or bf16 under autocast), then the block's checks, then one warning when the switch is on and the layer or call does not fit (a reason that starts with '!');
-every other refusal is an ordinary torch.nn case.  The two blocks of the form y = x + block(x) with N parameter inputs share one autograd Function body
-(`_residual_fn`) and one driver (`_residual`); retention has inputs of its own (q, k, v, g) and keeps its Function, with the module's nn.Linear projections
-around it.  Without autograd (no_grad, or nothing requires a gradient) the forward entry runs alone under no_grad and keeps nothing.  With all three switches
-on, what stays torch.nn in a training layer is the LayerNorm and the linear projections around retention."""
+every other refusal is an ordinary torch.nn case.  The three blocks of the form y = x + block(x) with N parameter inputs share one autograd Function body
+(`_residual_fn`) and one driver (`_residual`); the retention core alone (RETENTION) has inputs of its own (q, k, v, g) and keeps its Function, with the
+module's nn.Linear projections around it; where both TSA and RETENTION accept a call, TSA takes it.  Without autograd (no_grad, or nothing requires a gradient)
+the forward entry runs alone under no_grad and keeps nothing.  With TCONVFFN, TSA and XBAND on, a 'ret(2)' training layer is three native nodes and no torch op."""
 from __future__ import annotations
 
 import contextlib
@@ -110,6 +112,23 @@ def ret_supported(mhsa) -> Optional[str]:
     return None
 
 
+def tsa_supported(layer) -> Optional[str]:
+    """None when the layer's norm_mhsa, retention and dropout are what the whole-block kernels are built for, else the reason"""
+    why = ret_supported(layer.mhsa)
+    if why is not None:
+        return why
+    norm, mhsa = layer.norm_mhsa, layer.mhsa
+    if type(norm).__name__ != "LayerNorm" or tuple(norm.normalized_shape) != (96,) or norm.eps != 1e-5 or norm.weight is None or norm.bias is None:
+        return "norms[0] (norm_mhsa) must be LayerNorm(96, eps=1e-5) with weight and bias"
+    if any(lin is not None and lin.bias is not None for lin in (mhsa.q_proj, mhsa.k_proj, mhsa.v_proj, mhsa.g_proj, mhsa.out_proj)):
+        return "the projections must have no bias"
+    if (mhsa.k_proj is None) != bool(mhsa.share_qk):
+        return "k_proj must be absent exactly with share_qk"
+    if layer.dropout_mhsa.p > 0:
+        return "dropout[0] (dropout_mhsa) must be 0"
+    return None
+
+
 def xband_supported(layer) -> Optional[str]:
     """None when the layer's fconv1 / full-band block / fconv2 are the geometry the kernels are built for (SpatialNet-small's cross-band blocks), else the reason"""
     for name, norm in (("norms[3]", layer.fconv1[0]), ("norms[4]", layer.fconv2[0]), ("norms[5]", layer.norm_full)):
@@ -165,6 +184,15 @@ def xband_params(layer) -> List[Tensor]:
     return out
 
 
+def tsa_params(layer, rel_pos, *_) -> List[Optional[Tensor]]:
+    """the retention block's seven parameters (the module's live tensors; None at k_proj with share_qk) in the order of the C ABI, then the per-head decay
+    of this call's `rel_pos` (fp32 on the parameters' device; a constant)"""
+    m = layer.mhsa
+    decay = rel_pos[1][2].detach().to(device=m.q_proj.weight.device, dtype=torch.float32).contiguous()
+    return [layer.norm_mhsa.weight, layer.norm_mhsa.bias, m.q_proj.weight, None if m.k_proj is None else m.k_proj.weight, m.v_proj.weight, m.g_proj.weight,
+            m.out_proj.weight, decay]
+
+
 # ---- the checks of one call, after the common gate (a reason starts with '!': the switch is on and the call does not fit) ---------------------------------
 def _tconvffn_call(layer, x: Tensor) -> Optional[str]:
     if x.dim() != 4 or x.shape[-1] != 96:
@@ -189,6 +217,12 @@ def _ret_call(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope) -> Opt
     return None
 
 
+def _tsa_call(layer, x: Tensor, rel_pos, chunkwise_recurrent: bool, rope) -> Optional[str]:
+    if x.dim() != 4 or x.shape[0] < 1:
+        return f"!input must be [B,F,T,96], got {tuple(x.shape)}"
+    return _ret_call(layer, x[0], rel_pos, chunkwise_recurrent, rope)  # (a view [F,T,96]: the checks read T and the width)
+
+
 def _xband_call(layer, x: Tensor) -> Optional[str]:
     if x.dim() != 4 or x.shape[-1] != 96:
         return f"!input must be [B,F,T,96], got {tuple(x.shape)}"
@@ -211,7 +245,7 @@ class Block:
     call: Callable  # (layer, x, *what the call adds) -> None, or '!' and why this call does not fit
     streaming: str = "streaming call"  # the reason given to a call that carries a state
     # the y = x + block(x) form only:
-    params: Optional[Callable] = None  # (layer) -> the parameter inputs in the order of the C ABI
+    params: Optional[Callable] = None  # (layer, *what the call adds) -> the parameter inputs in the order of the C ABI (None: an absent one)
     entry: Optional[str] = None  # ops.<entry>_fwd / ops.<entry>_bwd (looked up at call time)
 
     @property
@@ -222,15 +256,17 @@ class Block:
 TCONVFFN = Block("NBSS_ONLINE_NATIVE_TRAIN", "T-ConvFFN", supported, _tconvffn_call, params=tconvffn_params, entry="online_tconvffn_train")
 RETENTION = Block("NBSS_ONLINE_NATIVE_RET", "retention", lambda layer: ret_supported(layer.mhsa), _ret_call, streaming="streaming or recurrent call")
 XBAND = Block("NBSS_ONLINE_NATIVE_XBAND", "cross-band blocks", xband_supported, _xband_call, params=xband_params, entry="online_xband_train")
+TSA = Block("NBSS_ONLINE_NATIVE_TSA", "retention block", tsa_supported, _tsa_call, streaming="streaming or recurrent call", params=tsa_params,
+            entry="online_tsa_train")
 
 
-# ---- the scaffold: written once for the three blocks ------------------------------------------------------------------------------------------------------
+# ---- the scaffold: written once for the four blocks -------------------------------------------------------------------------------------------------------
 def _on(block: Block) -> bool:
     return os.environ.get(block.switch, "0") == "1"
 
 
 # the switches, read at call time (like NBSS_NBC2_NATIVE); each off unless it is exactly '1'
-enabled, ret_enabled, xband_enabled = (functools.partial(_on, b) for b in (TCONVFFN, RETENTION, XBAND))
+enabled, ret_enabled, xband_enabled, tsa_enabled = (functools.partial(_on, b) for b in (TCONVFFN, RETENTION, XBAND, TSA))
 
 
 def _stream_dtype(x: Tensor) -> Optional[torch.dtype]:
@@ -274,6 +310,11 @@ def ret_eligible(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope, sta
     return _gate(RETENTION, layer, u, state is not None or inference, rel_pos, chunkwise_recurrent, rope)
 
 
+def tsa_eligible(layer, x: Tensor, rel_pos, chunkwise_recurrent: bool, rope, state, inference: bool) -> Optional[str]:
+    """`_gate` for the whole retention block of a call of `SpatialNetLayer.forward`"""
+    return _gate(TSA, layer, x, state is not None or inference, rel_pos, chunkwise_recurrent, rope)
+
+
 def xband_eligible(layer, x: Tensor, state) -> Optional[str]:
     """`_gate` for the cross-band trio of a call of `SpatialNetLayer._xband`"""
     return _gate(XBAND, layer, x, state is not None)
@@ -296,9 +337,9 @@ def _lib_for(block: Block, x: Tensor) -> Lib:
     return lib
 
 
-def _kernel_params(params) -> List[Tensor]:
-    """fp32 and contiguous (views where the module's tensors already are: the 1x1 weights [O][I][1] are their matrices as they lie)"""
-    return [p.detach().float().contiguous() for p in params]
+def _kernel_params(params) -> List[Optional[Tensor]]:
+    """fp32 and contiguous (views where the module's tensors already are: the 1x1 weights [O][I][1] are their matrices as they lie); None stays None"""
+    return [None if p is None else p.detach().float().contiguous() for p in params]
 
 
 _xband_kernel_params = _kernel_params  # (the name tests/test_online_xband_train.py calls it by)
@@ -311,8 +352,9 @@ def _residual_fn(name: str, block: Block, doc: str):
         xk = x.contiguous()
         p32 = _kernel_params(params)
         y, save = getattr(ops, block.entry + "_fwd")(lib, p32, xk, keep=True)
-        ctx.lib, ctx.saved, ctx.params = lib, (xk, save, p32), params
-        ctx.versions = [p._version for p in params]
+        ctx.lib, ctx.saved, ctx.inputs = lib, (xk, save, p32), params
+        ctx.params = [p for p in params if p is not None]  # (what ops.graph_guard_check watches)
+        ctx.versions = [p._version for p in ctx.params]
         return y
 
     @torch.autograd.function.once_differentiable
@@ -321,7 +363,7 @@ def _residual_fn(name: str, block: Block, doc: str):
         xk, save, p32 = ctx.saved
         dx, grads = getattr(ops, block.entry + "_bwd")(ctx.lib, p32, xk, save, dy.contiguous())
         ctx.saved = None
-        out = [g.reshape(p.shape).to(p.dtype) if ctx.needs_input_grad[2 + i] else None for i, (g, p) in enumerate(zip(grads, ctx.params))]
+        out = [g.reshape(p.shape).to(p.dtype) if ctx.needs_input_grad[2 + i] else None for i, (g, p) in enumerate(zip(grads, ctx.inputs))]
         return (None, dx if ctx.needs_input_grad[1] else None, *out)
 
     return type(name, (torch.autograd.Function,), {"forward": staticmethod(forward), "backward": staticmethod(backward), "__doc__": doc,
@@ -331,13 +373,16 @@ def _residual_fn(name: str, block: Block, doc: str):
 OnlineTConvFFNFn = _residual_fn("OnlineTConvFFNFn", TCONVFFN, "y = x + T-ConvFFN(x); inputs (lib, x, *the 14 parameters).  Saved: x and the kernels' activations.")
 OnlineXBandFn = _residual_fn("OnlineXBandFn", XBAND, "y = the cross-band trio; inputs (lib, x, *the 18 parameters) (a LinearGroup shared by several layers is an "
                              "input of several nodes: autograd sums).  Saved: x and the two block inputs the forward keeps.")
+OnlineTSAFn = _residual_fn("OnlineTSAFn", TSA, "y = x + out_proj(SiLU(g) * RMSNorm_head(chunk_retention(q, k, v))) on LayerNorm(x); inputs (lib, x, ln.weight, "
+                           "ln.bias, q_proj, k_proj or None, v_proj, g_proj, out_proj, decay).  Saved: x, q, k, v, g, the gated core output, the row statistics "
+                           "and the core's chunk states.")
 
 
-def _residual(block: Block, fn, layer, x: Tensor) -> Tensor:
-    """x + block(x) for a call the gate accepted; in the dtype of x.  Without autograd (no_grad, or nothing requires a gradient) the forward runs alone and
-    keeps nothing."""
+def _residual(block: Block, fn, layer, x: Tensor, *call) -> Tensor:
+    """x + block(x) for a call the gate accepted (`call`: what the call adds, as `take` got it); in the dtype of x.  Without autograd (no_grad, or nothing
+    requires a gradient) the forward runs alone and keeps nothing."""
     lib = _lib_for(block, x)
-    params = block.params(layer)
+    params = block.params(layer, *call)
     xs = x.to(_stream_dtype(x))
     if _needs_grad(x, params):
         y = fn.apply(lib, xs, *params)
@@ -347,9 +392,11 @@ def _residual(block: Block, fn, layer, x: Tensor) -> Tensor:
     return y.to(x.dtype)
 
 
-# x + T-ConvFFN(x) for a call `eligible` accepted, and x + fconv1, + full, + fconv2 for a call `xband_eligible` accepted: (layer, x) -> y
+# x + T-ConvFFN(x) for a call `eligible` accepted, and x + fconv1, + full, + fconv2 for a call `xband_eligible` accepted: (layer, x) -> y;
+# x + the retention block for a call `tsa_eligible` accepted: (layer, x, rel_pos) -> y
 tconvffn_residual = functools.partial(_residual, TCONVFFN, OnlineTConvFFNFn)
 xband_residual = functools.partial(_residual, XBAND, OnlineXBandFn)
+tsa_residual = functools.partial(_residual, TSA, OnlineTSAFn)
 
 
 class OnlineRetentionFn(torch.autograd.Function):

@@ -544,7 +544,7 @@ def graph_guard_check(ctx, what: str):
                                f"(shape {tuple(p.shape)}, version {p._version}, expected {v})")
 
 
-# ---- OnlineSpatialNet: the three blocks for training (csrc/online_train.hip, online_ret_train.hip, online_xband_train.hip) ------------------------
+# ---- OnlineSpatialNet: the blocks for training (csrc/online_train.hip, online_ret_train.hip, online_tsa_train.hip, online_xband_train.hip) --------
 def _online_bytes(lib: Lib, name: str, *dims: int) -> int:
     n = getattr(lib, name)(*dims)
     if n < 0:
@@ -648,6 +648,76 @@ def online_ret_train_bwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g:
     lib.call("nbss_online_ret_train_bwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
              _ptr(lib, save), _ptr(lib, d_out), _ptr(lib, dq), _ptr(lib, dk), _ptr(lib, dv), _ptr(lib, dg), _ptr(lib, ws), _stream(lib, q))
     return dq, dk, dv, dg
+
+
+# the whole retention block: y = x + out_proj(SiLU(g) * RMSNorm_head(chunk_retention(q, k, v))) on LayerNorm(x)
+def _online_tsa_dims(params: List[Optional[Tensor]], x: Tensor):
+    """params: (ln_w, ln_b, wq, wk or None, wv, wg, wo, decay); x [BF,T,96] or [B,F,T,96] -> (dtype, BF, T, share_qk)"""
+    if x.dim() not in (3, 4) or x.shape[-1] != 96 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise NbssError(f"online retention block: x must be [BF,T,96] or [B,F,T,96] in fp32 or bf16, got {tuple(x.shape)} {x.dtype}")
+    want = [96, 96, 96 * 96, 96 * 96, 192 * 96, 192 * 96, 96 * 192, 4]
+    if len(params) != 8 or any(i != 3 if t is None else t.numel() != n for i, (t, n) in enumerate(zip(params, want))):
+        raise NbssError("online retention block: params must be (ln_w, ln_b, wq, wk or None, wv, wg, wo, decay) of 96, 96, 96x96, 96x96, 192x96, 192x96, 96x192 "
+                        f"and 4 elements (got sizes {[None if t is None else t.numel() for t in params]})")
+    return NBSS_BF16 if x.dtype == torch.bfloat16 else NBSS_F32, x.numel() // (x.shape[-2] * 96), x.shape[-2], int(params[3] is None)
+
+
+_TSA_WS: Dict[tuple, Tensor] = {}
+
+
+def online_tsa_ws(lib: Lib, dt: int, BF: int, T: int, share: int, device) -> Tensor:
+    """the workspace of the retention-block entry points: ONE buffer per (library, device, dtype, keys), shared by every layer and both directions (the calls
+    are in order on one stream and each writes what it reads); a new shape replaces the old buffer"""
+    slot, shape = (id(lib), device, dt, share), (BF, T)
+    have = _TSA_WS.get(slot)
+    if have is None or have[0] != shape:
+        _TSA_WS.pop(slot, None)
+        have = _TSA_WS[slot] = (shape, scratch(_online_bytes(lib, "nbss_online_tsa_ws_bytes", dt, BF, T, share), device))
+    return have[1]
+
+
+def online_tsa_save_views(lib: Lib, save: Tensor, x: Tensor, share_qk: bool) -> Dict[str, Optional[Tensor]]:
+    """q, k (None with shared keys), v, g, go (the gated core output) and stats as views of what online_tsa_train_fwd kept (include/nbss_hip.h: the layout)"""
+    BF, T = x.numel() // (x.shape[-2] * 96), x.shape[-2]
+    esz, out, o = x.element_size(), {}, 0
+    flat = save.view(torch.uint8).reshape(-1)
+    for name, width, dtype, size in (("q", 96, x.dtype, esz), ("k", 96, x.dtype, esz), ("v", 192, x.dtype, esz), ("g", 192, x.dtype, esz),
+                                     ("go", 192, x.dtype, esz), ("stats", 2, torch.float32, 4)):
+        if name == "k" and share_qk:
+            out[name] = None
+            continue
+        n = BF * T * width * size
+        out[name] = flat[o:o + n].view(dtype).reshape(BF, T, width)
+        o += (n + 255) // 256 * 256
+    return out
+
+
+def online_tsa_train_fwd(lib: Lib, params: List[Optional[Tensor]], x: Tensor, keep: bool = True):
+    """y = x + the retention block on x [BF,T,96] or [B,F,T,96] (fp32 or bf16); params: the fp32 tensors (ln_w, ln_b, wq, wk or None: shared keys, wv, wg, wo)
+    in state_dict layout and decay [4], the per-head gamma.  -> (y, save): `save` is what online_tsa_train_bwd needs (None with keep=False: inference)"""
+    dt, BF, T, share = _online_tsa_dims(params, x)
+    y = torch.empty_like(x)
+    save = scratch(_online_bytes(lib, "nbss_online_tsa_save_bytes", dt, BF, T, share), x.device) if keep else None
+    ws = online_tsa_ws(lib, dt, BF, T, share, x.device)
+    lib.call("nbss_online_tsa_train_fwd", dt, BF, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save),
+             _ptr(lib, ws), _stream(lib, x))
+    return y, save
+
+
+def online_tsa_train_bwd(lib: Lib, params: List[Optional[Tensor]], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Optional[Tensor]]] = None):
+    """-> (dx, grads): dx includes the residual path; the fp32 gradients of the seven parameters are WRITTEN into `grads` (eight entries in the order of
+    `params`: None at wk with shared keys and at decay; uninitialised buffers of the parameters' shapes when not given)"""
+    dt, BF, T, share = _online_tsa_dims(params, x)
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise NbssError(f"online retention block: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    if grads is None:
+        grads = [None if p is None else torch.empty_like(p) for p in params[:7]] + [None]
+    if len(grads) != 8 or grads[7] is not None or any(g is not None and (p is None or g.numel() != p.numel()) for g, p in zip(grads, params)):
+        raise NbssError("online retention block: grads must match the seven parameters (None where the parameter is absent, and at decay)")
+    dx, ws = torch.empty_like(x), online_tsa_ws(lib, dt, BF, T, share, x.device)
+    lib.call("nbss_online_tsa_train_bwd", dt, BF, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
+             _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads[:7]), _ptr(lib, ws), _stream(lib, x))
+    return dx, grads
 
 
 # the cross-band trio
