@@ -477,6 +477,33 @@ int nbss_online_tsa_train_bwd(int dtype, int64_t BF, int T, const float* ln_w, c
                               const float* wg, const float* wo, const float* decay, const void* x, const void* save, const void* dy, void* dx,
                               float* d_ln_w, float* d_ln_b, float* d_wq, float* d_wk, float* d_wv, float* d_wg, float* d_wo, void* ws, void* stream);
 
+/* ---- OnlineSpatialNet: the core of a Mamba block for training (csrc/online_mamba_train.hip; nbss_amd/online_train.py) ---------------------------
+ * What models/arch/base/mamba.py computes between in_proj and out_proj (Mamba.core) for d_model 96, expand 2, d_state 16, d_conv 4, dt_rank 6 — the
+ * causal depthwise convolution with its SiLU, x_proj, dt_proj with its softplus, the selective scan h_t = exp(dt_t A) h_{t-1} + dt_t B_t x_t,
+ * y_t = C_t h_t + D x_t, and the gate y * SiLU(z) — on BF sequences of T frames, forward and backward.  xz, dxz [BF][T][384] (x | z: the output of
+ * in_proj); y, dy [BF][T][192]; all contiguous and of `dtype` (NBSS_F32 or NBSS_BF16; all arithmetic is fp32 in either).  The parameters are the
+ * module's own fp32 tensors in state_dict layout: conv_w [192][1][4], conv_b [192], xproj_w [38][192], dt_w [192][6], dt_b [192], A_log [192][16], D [192].
+ * save: nbss_online_mamba_train_save_bytes() bytes that the forward fills for the backward, each piece 256-byte aligned: the fp32 state h at the START
+ *   of every run of 8 frames [BF][ceil(T / 8)][16][192] | the x_proj outputs (dt_r, B, C) [BF][T][38] fp32.  The backward walks the runs in reverse,
+ *   recomputes the states of a run into LDS from its checkpoint and carries the state's gradient (no division by the decay).  save = NULL: forward only
+ *   (inference), nothing is kept.
+ * ws: nbss_online_mamba_train_ws_bytes() bytes, for either call (the backward's per-workgroup partial parameter gradients, min(BF, 512) rows of 67 x 192).
+ * bwd: dxz and the seven d_* buffers (fp32, the parameters' layouts) are WRITTEN (not accumulated; they may be uninitialised).
+ * NBSS_EINVAL: BF < 1, T outside 1 .. NBSS_T_MAX (4096), a NULL pointer other than the forward's `save`, y == xz, dxz == xz or dy.
+ * NBSS_EUNSUPPORTED: dtype outside {NBSS_F32, NBSS_BF16}, more than 2^28 tokens.  The two *_bytes calls return the same codes (negative) instead of a
+ * size.  Nothing is launched after a refusal.
+ * One workgroup of 192 threads (a thread per channel, its 16 states in registers) per sequence; more than 512 sequences are covered by a grid-stride
+ * loop.  No atomics, every sum in a fixed order (the sums over the channels through LDS, the parameter gradients as per-workgroup partial rows that a
+ * second launch folds): two calls give the same bits, and a sequence's rows of y and dxz do not depend on the other sequences of the launch. */
+int64_t nbss_online_mamba_train_save_bytes(int dtype, int64_t BF, int T);
+int64_t nbss_online_mamba_train_ws_bytes(int dtype, int64_t BF, int T);
+int nbss_online_mamba_train_fwd(int dtype, int64_t BF, int T, const void* xz, const float* conv_w, const float* conv_b, const float* xproj_w,
+                                const float* dt_w, const float* dt_b, const float* A_log, const float* D, void* y, void* save, void* ws, void* stream);
+int nbss_online_mamba_train_bwd(int dtype, int64_t BF, int T, const void* xz, const float* conv_w, const float* conv_b, const float* xproj_w,
+                                const float* dt_w, const float* dt_b, const float* A_log, const float* D, const void* save, const void* dy, void* dxz,
+                                float* d_conv_w, float* d_conv_b, float* d_xproj_w, float* d_dt_w, float* d_dt_b, float* d_A_log, float* d_D, void* ws,
+                                void* stream);
+
 /* ---- OnlineSpatialNet: the cross-band trio for training (csrc/online_xband_train.hip; nbss_amd/online_train.py) -------------------------------
  * x1 = x + fconv1(x), x2 = x1 + full(x1), y = x2 + fconv2(x2) of models/arch/OnlineSpatialNet.py `SpatialNetLayer.forward` on x, y [B][F][T][96] of
  * `dtype`, forward and backward, through the SpatialNet-small kernels behind nbss_fconv_fwd / nbss_full_fwd and their _bwd (the same launches: the results

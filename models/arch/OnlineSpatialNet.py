@@ -5,12 +5,18 @@ frames from a state), the GroupNorm inside the T-ConvFFN normalises each FRAME o
 a sequence over time, and the narrow-band attention is causal:
     'mhsa(N)'  masked multi-head self-attention over the last N frames ('inf': all past frames; rope='ALiBi' adds linear biases),
     'ret(2)'   multi-scale retention (models/arch/base/retention.py), parallel / chunkwise for training, recurrent for streaming,
-    'mamba(..)' needs mamba_ssm, which is neither pinned by the reference nor installed here: raises.
+    'mamba(N,K)' / 'mamba(N,K,not_replace_ffn)'  the reference's default: a Mamba block (models/arch/base/mamba.py, d_state N, d_conv K) in place of the
+               attention and, unless 'not_replace_ffn', a second one behind `norm_tconvffn` in place of the T-ConvFFN.  The reference takes the block
+               from mamba_ssm, a CUDA-only wheel it does not pin; the module here is a port from the published equations with mamba_ssm's state_dict
+               keys, parity with that package is NOT pinned.  Hence opt-in: constructing the variant raises unless NBSS_ONLINE_MAMBA=1 (read at
+               construction, off unless exactly '1').  Its core trains through the HIP kernels of nbss_amd/online_train.py (MAMBA) when
+               NBSS_ONLINE_NATIVE_MAMBA=1; `inference=True` and the streaming interface walk the module's step form (a fixed-size state per block).
 Besides the reference's whole-utterance forward this module offers an explicit streaming interface — `init_stream(batch)` /
 `forward_stream(x_chunk, state)` — that carries conv states, a K/V ring (mhsa) or the retention state across chunks; with fixed
 chunk shapes a step is a static kernel sequence and can be captured in a HIP graph (`OnlineStreamer`).
 Plain PyTorch (BASELINE config 5)."""
 import math
+import os
 from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
@@ -20,6 +26,7 @@ from torch import Tensor
 from torch.nn import MultiheadAttention
 
 from models.arch.base.linear_group import LinearGroup
+from models.arch.base.mamba import Mamba
 from models.arch.base.norm import new_norm
 from models.arch.base.retention import MultiScaleRetention, RetNetRelPos
 
@@ -72,8 +79,14 @@ class SpatialNetLayer(nn.Module):
             factor, share = attention[4:-1].split(",")
             assert share in ("share_qk", "not_share_qk"), attention
             self.mhsa = MultiScaleRetention(embed_dim=dim_hidden, num_heads=num_heads, value_factor=int(factor), share_qk=share == "share_qk")
-        elif attention.startswith("mamba"):
-            raise NotImplementedError("attention='mamba(..)' needs mamba_ssm (unpinned in the reference's requirements.txt, not installed): use mhsa(N) or ret(2)")
+        elif attention.startswith("mamba"):  # mamba(<d_state>,<d_conv>[,not_replace_ffn])
+            if os.environ.get("NBSS_ONLINE_MAMBA", "0") != "1":
+                raise NotImplementedError("attention='mamba(..)' needs mamba_ssm (unpinned in the reference's requirements.txt, not installed): use mhsa(N) or "
+                                          "ret(2), or set NBSS_ONLINE_MAMBA=1 for this project's own Mamba (models/arch/base/mamba.py: a port from the published "
+                                          "equations with mamba_ssm's state_dict keys; parity with mamba_ssm is not pinned, hence the switch)")
+            params = attention[6:-1].split(",")
+            d_state, d_conv = int(params[0]), int(params[1])
+            self.mhsa = Mamba(d_model=dim_hidden, d_state=d_state, d_conv=d_conv, layer_idx=0)
         else:
             self.mhsa = MultiheadAttention(embed_dim=dim_hidden, num_heads=num_heads, batch_first=True)
         self.attention = attention
@@ -82,9 +95,14 @@ class SpatialNetLayer(nn.Module):
         def tconv():
             return CausalConv1d(dim_ffn, dim_ffn, kernel_size=tk, groups=tg)
 
-        self.tconvffn = nn.ModuleList([new_norm(norms[1], dim_hidden, seq_last=True, group_size=None, num_groups=tg), nn.Conv1d(dim_hidden, dim_ffn, kernel_size=1),
-                                       nn.SiLU(), tconv(), nn.SiLU(), tconv(), new_norm(norms[2], dim_ffn, seq_last=True, group_size=None, num_groups=tg),
-                                       nn.SiLU(), tconv(), nn.SiLU(), nn.Conv1d(dim_ffn, dim_hidden, kernel_size=1)])
+        if attention.startswith("mamba") and "not_replace_ffn" not in attention:
+            self.norm_tconvffn = new_norm(norms[1], dim_hidden, seq_last=False, group_size=None, num_groups=tg)
+            self.tconvffn = Mamba(d_model=dim_hidden, d_state=d_state, d_conv=d_conv, layer_idx=0)
+        else:
+            self.tconvffn = nn.ModuleList([new_norm(norms[1], dim_hidden, seq_last=True, group_size=None, num_groups=tg),
+                                           nn.Conv1d(dim_hidden, dim_ffn, kernel_size=1), nn.SiLU(), tconv(), nn.SiLU(), tconv(),
+                                           new_norm(norms[2], dim_ffn, seq_last=True, group_size=None, num_groups=tg), nn.SiLU(), tconv(), nn.SiLU(),
+                                           nn.Conv1d(dim_ffn, dim_hidden, kernel_size=1)])
         self.dropout_tconvffn = nn.Dropout(dropout[1])
 
     def forward(self, x: Tensor, att_mask=None, chunkwise_recurrent: bool = True, rope=True, state: Dict[int, Any] = None, inference: bool = False):
@@ -93,13 +111,18 @@ class SpatialNetLayer(nn.Module):
         # x + the whole retention block (LayerNorm, projections, chunkwise core, out_proj) runs as ONE autograd node through the HIP kernels of
         # nbss_amd/online_train.py when the switch of its TSA block is on (off by default) and `take` accepts the call; it wins over RETENTION in `_tsa`
         from nbss_amd import online_train
-        if isinstance(self.mhsa, MultiScaleRetention) and online_train.take(online_train.TSA, self, x, state is not None or inference, att_mask,
+        if isinstance(self.mhsa, Mamba):
+            x, attn = x + self._mamba(x, self.mhsa, self.norm_mhsa, self.dropout_mhsa, state, inference), None
+        elif isinstance(self.mhsa, MultiScaleRetention) and online_train.take(online_train.TSA, self, x, state is not None or inference, att_mask,
                                                                               chunkwise_recurrent, rope):
             x, attn = online_train.tsa_residual(self, x, att_mask, chunkwise_recurrent, rope), None
         else:
             a, attn = self._tsa(x, att_mask, chunkwise_recurrent, rope, state=state, inference=inference)
             x = x + a
-        x = self._tconvffn(x, state=state, residual=True)
+        if isinstance(self.tconvffn, Mamba):
+            x = x + self._mamba(x, self.tconvffn, self.norm_tconvffn, self.dropout_tconvffn, state, inference)
+        else:
+            x = self._tconvffn(x, state=state, residual=True)
         return x, attn
 
     # ---- narrow-band -----------------------------------------------------------------------------------------------------------
@@ -121,6 +144,25 @@ class SpatialNetLayer(nn.Module):
             st: Dict[str, Any] = {}
             u = torch.cat([self.mhsa(u[:, i:i + 1], rel_pos=attn_mask[i], incremental_state=st, rope=rope) for i in range(T)], dim=1)
         return self.dropout_mhsa(u.reshape(B, Fq, T, H)), attn
+
+    def _mamba(self, x: Tensor, mamba: Mamba, norm: nn.Module, dropout: nn.Module, state: Dict[int, Any] = None, inference: bool = False) -> Tensor:
+        """dropout(mamba(norm(x))) on the B F sequences of x [B,F,T,H] (the reference's `_mamba`, :167-182).  A whole-utterance training call runs the
+        block's core — everything between in_proj and out_proj — as ONE autograd node through the HIP kernels of nbss_amd/online_train.py when the switch
+        of its MAMBA block is on (off by default) and `take` accepts the call (else, with the switch on, the torch module and one warning that names the
+        reason); `inference=True` walks the step form frame by frame from an empty state, a `state` dict (keyed by id(mamba): streaming) from that state"""
+        from nbss_amd import online_train
+        B, Fq, T, H = x.shape
+        u = norm(x).reshape(B * Fq, T, H)
+        if state is not None or inference:
+            st = mamba.init_state(B * Fq, device=u.device, dtype=u.dtype) if state is None or id(mamba) not in state else state[id(mamba)]
+            u = torch.cat([mamba.step(u[:, i:i + 1], st) for i in range(T)], dim=1)
+            if state is not None:
+                state[id(mamba)] = st
+        elif online_train.take(online_train.MAMBA, mamba, u, False):
+            u = online_train.mamba_forward(mamba, u)
+        else:
+            u = mamba(u)
+        return dropout(u.reshape(B, Fq, T, H))
 
     def _tconvffn(self, x: Tensor, state: Dict[int, Any] = None, residual: bool = False) -> Tensor:
         """the block's output, or x + it with `residual`.  The residual form of a whole-utterance call (state is None) runs through the HIP kernels of
@@ -189,6 +231,8 @@ class OnlineSpatialNet(nn.Module):
         self.pos = None
         if attention.startswith("ret"):
             self.pos = RetNetRelPos(embed_dim=dim_hidden, num_heads=num_heads, recurrent_chunk_size=64, decay=decay)
+        elif attention.startswith("mamba"):
+            self.attn_scope = 1
         elif attention.startswith("mhsa"):
             self.attn_scope = math.inf if attention[5:-1] == "inf" else int(attention[5:-1])
         self.encoder = CausalConv1d(dim_input, dim_hidden, kernel_size=encoder_kernel_size, look_ahead=0)
@@ -242,7 +286,7 @@ class OnlineSpatialNet(nn.Module):
     # ---- streaming -------------------------------------------------------------------------------------------------------------
     def init_stream(self, batch: int, device=None, dtype=torch.float32) -> Dict[str, Any]:
         """empty state for `forward_stream`: causal-conv tails, per-layer K/V ring (mhsa: the last attn_scope - 1 frames, with a
-        device-side count of the slots that hold a frame) or retention state, frame counter.  Every tensor has a fixed shape (except
+        device-side count of the slots that hold a frame), retention state or the two states of each Mamba, frame counter.  Every tensor has a fixed shape (except
         the K/V cache of 'mhsa(inf)', which grows), so a step can be replayed from a HIP graph."""
         dev = device if device is not None else self.decoder.weight.device
         Fq, H, n = self.layers[0].full.in_features, self.decoder.in_features, batch * self.layers[0].full.in_features
@@ -255,6 +299,11 @@ class OnlineSpatialNet(nn.Module):
                 keep = 0 if self.attn_scope is math.inf else self.attn_scope - 1
                 st["attn"].append({"k": torch.zeros(n, keep, H, device=dev, dtype=dtype), "v": torch.zeros(n, keep, H, device=dev, dtype=dtype),
                                    "valid": torch.zeros(1, dtype=torch.long, device=dev)})
+            elif isinstance(layer.mhsa, Mamba):  # the two states of each Mamba of the layer: the convolution's last K - 1 inputs and h
+                ast = dict(layer.mhsa.init_state(n, device=dev, dtype=dtype))
+                if isinstance(layer.tconvffn, Mamba):
+                    ast.update({"ffn_" + k: v for k, v in layer.tconvffn.init_state(n, device=dev, dtype=dtype).items()})
+                st["attn"].append(ast)
             else:  # zero state with zero running scale == "no frame seen yet" in MultiScaleRetention.recurrent_forward
                 r = layer.mhsa
                 st["attn"].append({"prev_key_value": torch.zeros(n, r.num_heads, r.key_dim, r.head_dim, device=dev, dtype=dtype),
@@ -271,6 +320,13 @@ class OnlineSpatialNet(nn.Module):
             h = h + layer._fconv(layer.fconv1, h)
             h = h + layer._full(h)
             h = h + layer._fconv(layer.fconv2, h)
+            if isinstance(layer.mhsa, Mamba):
+                h = h + self._mamba_stream(layer, layer.mhsa, layer.norm_mhsa, layer.dropout_mhsa, h, ast, "")
+                if isinstance(layer.tconvffn, Mamba):
+                    h = h + self._mamba_stream(layer, layer.tconvffn, layer.norm_tconvffn, layer.dropout_tconvffn, h, ast, "ffn_")
+                else:
+                    h = h + layer._tconvffn(h, state=conv)
+                continue
             u = layer.norm_mhsa(h).reshape(B * Fq, C, -1)
             if isinstance(layer.mhsa, MultiheadAttention):
                 u = self._mhsa_stream(layer.mhsa, u, ast)
@@ -281,6 +337,14 @@ class OnlineSpatialNet(nn.Module):
             h = h + layer._tconvffn(h, state=conv)
         state["t"] = t0 + C
         return self.decoder(h).contiguous()
+
+    @staticmethod
+    def _mamba_stream(layer: SpatialNetLayer, mamba: Mamba, norm: nn.Module, dropout: nn.Module, h: Tensor, ast: Dict[str, Any], prefix: str) -> Tensor:
+        """`layer._mamba` on the next frames from the block's two states `ast[prefix + 'conv' | 'ssm']`, which are replaced by the new ones"""
+        one = {id(mamba): {"conv": ast[prefix + "conv"], "ssm": ast[prefix + "ssm"]}}
+        out = layer._mamba(h, mamba, norm, dropout, state=one)
+        ast[prefix + "conv"], ast[prefix + "ssm"] = one[id(mamba)]["conv"], one[id(mamba)]["ssm"]
+        return out
 
     def _mhsa_stream(self, mha: MultiheadAttention, u: Tensor, ast: Dict[str, Any]) -> Tensor:
         """causal windowed attention of C new frames against the cached keys / values of the last attn_scope - 1 frames"""
@@ -305,7 +369,7 @@ class OnlineSpatialNet(nn.Module):
 
 
 class OnlineStreamer:
-    """Fixed-shape streaming step of an OnlineSpatialNet ('mhsa(N)' with finite N, or 'ret(..)' without rotary positions): every call
+    """Fixed-shape streaming step of an OnlineSpatialNet ('mhsa(N)' with finite N, 'ret(..)' without rotary positions, or 'mamba(..)'): every call
     consumes `chunk` frames.  The whole state lives in pre-allocated device buffers that a step updates in place, so a step is a
     static kernel sequence; on a HIP device it is captured once into a HIP graph (torch.cuda.CUDAGraph) and replayed — BASELINE
     config 5's "causal chunked inference with hipGraph-captured steps"."""
@@ -314,7 +378,7 @@ class OnlineStreamer:
         self.net, self.B, self.C = net.eval(), batch, chunk
         self.dev = torch.device(device) if device is not None else net.decoder.weight.device
         if getattr(net, "attn_scope", 0) is math.inf or (net.pos is not None and net.rope is not False):
-            raise NotImplementedError("OnlineStreamer needs a fixed-size state: mhsa(N) with finite N, or retention without rotary positions")
+            raise NotImplementedError("OnlineStreamer needs a fixed-size state: mhsa(N) with finite N, retention without rotary positions, or mamba")
         self.Fq, self.din = net.layers[0].full.in_features, net.encoder.in_channels
         self.use_graph = self.dev.type == "cuda" if use_graph is None else use_graph
         self.x = torch.zeros(batch, self.Fq, chunk, self.din, device=self.dev)

@@ -120,6 +120,10 @@ SIGNATURES = {
     "nbss_online_tsa_ws_bytes": (C.c_int64, [_I, C.c_int64, _I, _I]),
     "nbss_online_tsa_train_fwd": (_I, [_I, C.c_int64, _I] + [_P] * 13),
     "nbss_online_tsa_train_bwd": (_I, [_I, C.c_int64, _I] + [_P] * 21),
+    "nbss_online_mamba_train_save_bytes": (C.c_int64, [_I, C.c_int64, _I]),
+    "nbss_online_mamba_train_ws_bytes": (C.c_int64, [_I, C.c_int64, _I]),
+    "nbss_online_mamba_train_fwd": (_I, [_I, C.c_int64, _I] + [_P] * 12),
+    "nbss_online_mamba_train_bwd": (_I, [_I, C.c_int64, _I] + [_P] * 20),
     "nbss_online_stft_step": (_I, [_I] * 6 + [_P] * 7),
     "nbss_online_istft_step": (_I, [_I] * 5 + [_P] * 6),
     "nbss_nb_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),

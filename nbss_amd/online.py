@@ -5,7 +5,7 @@ buffers — a fixed launch sequence that is captured once into a HIP graph and r
 
 `NativeOnlineStreamer(net, batch, chunk)` has the interface of models.arch.OnlineSpatialNet.OnlineStreamer (step / reset / graph) and serves
 the geometry the kernels are built for: attention 'ret(F, share_qk | not_share_qk)' with value factor 2 and no rotary positions, or causal windowed
-attention 'mhsa(N)' over a K / V ring, dim_hidden 96,
+attention 'mhsa(N)' over a K / V ring (not the 'mamba(..)' variant: refused with a reason), dim_hidden 96,
 dim_ffn 192, dim_squeeze 8, 4 heads, kernel sizes (5, 3), conv groups (8, 8), encoder kernel 5, norms LN/LN/GN/LN/LN/LN; everything else
 raises NotImplementedError (callers fall back to OnlineStreamer, the torch.nn step)."""
 from __future__ import annotations
@@ -26,6 +26,8 @@ def supported(net) -> Optional[str]:
     from models.arch.base.retention import MultiScaleRetention, RetNetRelPos
     l0 = net.layers[0]
     r = l0.mhsa
+    if type(r).__name__ == "Mamba" or type(l0.tconvffn).__name__ == "Mamba":
+        return "the 'mamba(..)' variant has no native streaming step (OnlineStreamer walks the module's step form)"
     if isinstance(r, torch.nn.MultiheadAttention):
         if net.rope is not False or getattr(net, "attn_scope", math.inf) is math.inf or net.attn_scope > 4096:
             return "windowed attention needs a finite window 'mhsa(N)' (N <= 4096) and no ALiBi / rotary positions"

@@ -6,13 +6,19 @@ independent of the others):
     XBAND      NBSS_ONLINE_NATIVE_XBAND   csrc/online_xband_train.hip  x + fconv1, + full-band, + fconv2 as one node           OnlineXBandFn
     TSA        NBSS_ONLINE_NATIVE_TSA     csrc/online_tsa_train.hip    x + the whole retention block (LayerNorm, the four      OnlineTSAFn
                                                                        projections, the core, out_proj) as one node
+    MAMBA      NBSS_ONLINE_NATIVE_MAMBA   csrc/online_mamba_train.hip  the core of a Mamba block between in_proj and out_proj  OnlineMambaFn
+                                                                       (conv, SiLU, x_proj, dt_proj + softplus, the selective
+                                                                       scan, the D skip, the gate) as one node
 
 A block is one `Block` record: its switch, its label, its `supported` and the checks of the call.  Everything else is written once.  `take` is what
 `models.arch.OnlineSpatialNet.SpatialNetLayer` asks per call: the common gate (`_gate`: switch, streaming call, device, library, geometry, stream dtype — fp32,
 or bf16 under autocast), then the block's checks, then one warning when the switch is on and the layer or call does not fit (a reason that starts with '!');
 every other refusal is an ordinary torch.nn case.  The three blocks of the form y = x + block(x) with N parameter inputs share one autograd Function body
 (`_residual_fn`) and one driver (`_residual`); the retention core alone (RETENTION) has inputs of its own (q, k, v, g) and keeps its Function, with the
-module's nn.Linear projections around it; where both TSA and RETENTION accept a call, TSA takes it.  Without autograd (no_grad, or nothing requires a gradient)
+module's nn.Linear projections around it; where both TSA and RETENTION accept a call, TSA takes it.  MAMBA (the 'mamba(16,4)' variant, which itself is
+behind NBSS_ONLINE_MAMBA=1 at construction: models/arch/OnlineSpatialNet.py) is asked per Mamba module, not per layer: its node has the inputs (xz, the seven
+parameters of the core) and the module's in_proj / out_proj stay torch GEMMs around it (`mamba_forward`); the backward recomputes the states from checkpoints
+every MAMBA_CKPT frames.  Without autograd (no_grad, or nothing requires a gradient)
 the forward entry runs alone under no_grad and keeps nothing.  With TCONVFFN, TSA and XBAND on, a 'ret(2)' training layer is three native nodes and no torch op."""
 from __future__ import annotations
 
@@ -30,6 +36,7 @@ from ._lib import Lib, hip
 
 TCONVFFN_T_MAX, TCONVFFN_F_MAX = 4096, 272
 RET_CHUNK, RET_T_MAX = 64, 4096
+MAMBA_CKPT, MAMBA_T_MAX, MAMBA_GRID_CAP = 8, 4096, 512  # (csrc/online_mamba_train.hip: MB_CKPT, NBSS_T_MAX, MB_GRID_CAP)
 XBAND_F_MAX, XBAND_T_MAX, XBAND_T_TRAIN_MAX, XBAND_F_TRAIN_MAX_FP32 = 272, 4096, 256, 160
 # (module index in layer.tconvffn, attribute) in the order of the C ABI's parameter list
 PARAM_SLOTS = ((0, "weight"), (0, "bias"), (1, "weight"), (1, "bias"), (3, "weight"), (3, "bias"), (5, "weight"), (5, "bias"), (6, "weight"), (6, "bias"),
@@ -67,6 +74,8 @@ def supported(layer) -> Optional[str]:
     else the reason"""
     from models.arch.OnlineSpatialNet import CausalConv1d
     tc = layer.tconvffn
+    if not isinstance(tc, torch.nn.ModuleList):
+        return f"the T-ConvFFN must be the ModuleList of the mhsa / ret variants (got {type(tc).__name__})"
     kinds = [type(m).__name__ for m in tc]
     if kinds != ["LayerNorm", "Conv1d", "SiLU", "CausalConv1d", "SiLU", "CausalConv1d", "GroupNorm", "SiLU", "CausalConv1d", "SiLU", "Conv1d"]:
         return f"the T-ConvFFN must be LN, 1x1, SiLU, conv, SiLU, conv, GN, SiLU, conv, SiLU, 1x1 (got {kinds})"
@@ -170,6 +179,30 @@ def xband_supported(layer) -> Optional[str]:
     return None
 
 
+def mamba_supported(mamba) -> Optional[str]:
+    """None when the module is the Mamba the kernels are built for (OnlineSpatialNet's 'mamba(16,4)' at width 96), else the reason"""
+    if type(mamba).__name__ != "Mamba":
+        return f"the block must be Mamba (got {type(mamba).__name__})"
+    if mamba.d_model != 96 or mamba.d_inner != 192:
+        return f"d_model must be 96 and expand 2 (got {mamba.d_model}, {mamba.expand})"
+    if mamba.d_state != 16:
+        return f"d_state must be 16 (got {mamba.d_state})"
+    if mamba.d_conv != 4:
+        return f"d_conv must be 4 (got {mamba.d_conv})"
+    if mamba.dt_rank != 6:
+        return f"dt_rank must be 6 (got {mamba.dt_rank})"
+    if mamba.in_proj.bias is not None or mamba.x_proj.bias is not None or mamba.out_proj.bias is not None:
+        return "in_proj, x_proj and out_proj must have no bias"
+    if mamba.conv1d.bias is None or mamba.dt_proj.bias is None:
+        return "conv1d and dt_proj must have a bias"
+    return None
+
+
+def mamba_params(mamba, *_) -> List[Tensor]:
+    """the seven parameters of the core (the module's live tensors) in the order of the C ABI"""
+    return [mamba.conv1d.weight, mamba.conv1d.bias, mamba.x_proj.weight, mamba.dt_proj.weight, mamba.dt_proj.bias, mamba.A_log, mamba.D]
+
+
 def tconvffn_params(layer) -> List[Tensor]:
     """the block's 14 parameters (the module's live tensors) in the order of the C ABI"""
     return [getattr(layer.tconvffn[i], a) for i, a in PARAM_SLOTS]
@@ -236,9 +269,17 @@ def _xband_call(layer, x: Tensor) -> Optional[str]:
     return None
 
 
+def _mamba_call(mamba, u: Tensor) -> Optional[str]:
+    if u.dim() != 3 or u.shape[-1] != 96:
+        return f"!input must be [B F,T,96], got {tuple(u.shape)}"
+    if u.shape[0] < 1 or not 1 <= u.shape[1] <= MAMBA_T_MAX:
+        return f"!1 <= T <= {MAMBA_T_MAX} (got T = {u.shape[1]})"
+    return None
+
+
 @dataclass(frozen=True)
 class Block:
-    """one natively trainable block of a SpatialNetLayer"""
+    """one natively trainable block of a SpatialNetLayer (MAMBA: `layer` is the Mamba module itself, a layer has up to two)"""
     switch: str  # the environment variable that turns it on
     what: str  # in warnings "OnlineSpatialNet <what>", in errors "OnlineSpatialNet native <what>"
     supported: Callable  # (layer) -> None, or why the layer is not what the kernels are built for
@@ -258,15 +299,17 @@ RETENTION = Block("NBSS_ONLINE_NATIVE_RET", "retention", lambda layer: ret_suppo
 XBAND = Block("NBSS_ONLINE_NATIVE_XBAND", "cross-band blocks", xband_supported, _xband_call, params=xband_params, entry="online_xband_train")
 TSA = Block("NBSS_ONLINE_NATIVE_TSA", "retention block", tsa_supported, _tsa_call, streaming="streaming or recurrent call", params=tsa_params,
             entry="online_tsa_train")
+MAMBA = Block("NBSS_ONLINE_NATIVE_MAMBA", "Mamba core", mamba_supported, _mamba_call, streaming="streaming or inference call", params=mamba_params,
+              entry="online_mamba_train")
 
 
-# ---- the scaffold: written once for the four blocks -------------------------------------------------------------------------------------------------------
+# ---- the scaffold: written once for the five blocks -------------------------------------------------------------------------------------------------------
 def _on(block: Block) -> bool:
     return os.environ.get(block.switch, "0") == "1"
 
 
 # the switches, read at call time (like NBSS_NBC2_NATIVE); each off unless it is exactly '1'
-enabled, ret_enabled, xband_enabled, tsa_enabled = (functools.partial(_on, b) for b in (TCONVFFN, RETENTION, XBAND, TSA))
+enabled, ret_enabled, xband_enabled, tsa_enabled, mamba_enabled = (functools.partial(_on, b) for b in (TCONVFFN, RETENTION, XBAND, TSA, MAMBA))
 
 
 def _stream_dtype(x: Tensor) -> Optional[torch.dtype]:
@@ -313,6 +356,11 @@ def ret_eligible(layer, u: Tensor, rel_pos, chunkwise_recurrent: bool, rope, sta
 def tsa_eligible(layer, x: Tensor, rel_pos, chunkwise_recurrent: bool, rope, state, inference: bool) -> Optional[str]:
     """`_gate` for the whole retention block of a call of `SpatialNetLayer.forward`"""
     return _gate(TSA, layer, x, state is not None or inference, rel_pos, chunkwise_recurrent, rope)
+
+
+def mamba_eligible(mamba, u: Tensor, state, inference: bool) -> Optional[str]:
+    """`_gate` for the core of one Mamba of a call of `SpatialNetLayer._mamba`"""
+    return _gate(MAMBA, mamba, u, state is not None or inference)
 
 
 def xband_eligible(layer, x: Tensor, state) -> Optional[str]:
@@ -378,6 +426,12 @@ OnlineTSAFn = _residual_fn("OnlineTSAFn", TSA, "y = x + out_proj(SiLU(g) * RMSNo
                            "and the core's chunk states.")
 
 
+# (not a residual form, but the same shape of node: inputs (lib, xz, *parameters), one saved blob, every gradient from one backward entry)
+OnlineMambaFn = _residual_fn("OnlineMambaFn", MAMBA, "out = y * SiLU(z) of a Mamba block on xz = in_proj(u); inputs (lib, xz, conv1d.weight, conv1d.bias, "
+                             "x_proj.weight, dt_proj.weight, dt_proj.bias, A_log, D).  Saved: xz, the x_proj rows (dt_r, B, C) and the state h every "
+                             "MAMBA_CKPT frames; the backward recomputes the states of an interval from its checkpoint.")
+
+
 def _residual(block: Block, fn, layer, x: Tensor, *call) -> Tensor:
     """x + block(x) for a call the gate accepted (`call`: what the call adds, as `take` got it); in the dtype of x.  Without autograd (no_grad, or nothing
     requires a gradient) the forward runs alone and keeps nothing."""
@@ -397,6 +451,20 @@ def _residual(block: Block, fn, layer, x: Tensor, *call) -> Tensor:
 tconvffn_residual = functools.partial(_residual, TCONVFFN, OnlineTConvFFNFn)
 xband_residual = functools.partial(_residual, XBAND, OnlineXBandFn)
 tsa_residual = functools.partial(_residual, TSA, OnlineTSAFn)
+
+
+def mamba_forward(mamba, u: Tensor) -> Tensor:
+    """Mamba.forward(u) for a call `mamba_eligible` accepted: in_proj and out_proj are the module's own nn.Linear's (torch GEMMs, autocast like any other),
+    the core between them is native.  Without autograd the forward runs alone and keeps nothing."""
+    lib = _lib_for(MAMBA, u)
+    xz = mamba.in_proj(u).to(_stream_dtype(u))
+    params = mamba_params(mamba)
+    if _needs_grad(xz, params):
+        out = OnlineMambaFn.apply(lib, xz, *params)
+    else:
+        with torch.no_grad():
+            out = ops.online_mamba_train_fwd(lib, _kernel_params(params), xz.contiguous(), keep=False)[0]
+    return mamba.out_proj(out)
 
 
 class OnlineRetentionFn(torch.autograd.Function):

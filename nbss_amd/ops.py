@@ -544,7 +544,7 @@ def graph_guard_check(ctx, what: str):
                                f"(shape {tuple(p.shape)}, version {p._version}, expected {v})")
 
 
-# ---- OnlineSpatialNet: the blocks for training (csrc/online_train.hip, online_ret_train.hip, online_tsa_train.hip, online_xband_train.hip) --------
+# ---- OnlineSpatialNet: the blocks for training (csrc/online_train.hip, online_ret_train.hip, online_tsa_train.hip, online_xband_train.hip, online_mamba_train.hip)
 def _online_bytes(lib: Lib, name: str, *dims: int) -> int:
     n = getattr(lib, name)(*dims)
     if n < 0:
@@ -718,6 +718,46 @@ def online_tsa_train_bwd(lib: Lib, params: List[Optional[Tensor]], x: Tensor, sa
     lib.call("nbss_online_tsa_train_bwd", dt, BF, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
              _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads[:7]), _ptr(lib, ws), _stream(lib, x))
     return dx, grads
+
+
+# the core of a Mamba block: y * SiLU(z) from xz = in_proj(u)
+MAMBA_PARAM_SIZES = (192 * 4, 192, 38 * 192, 192 * 6, 192, 192 * 16, 192)  # conv1d.weight, conv1d.bias, x_proj.weight, dt_proj.weight, dt_proj.bias, A_log, D
+
+
+def _online_mamba_dims(params: List[Tensor], xz: Tensor, which: str = "params"):
+    if xz.dim() != 3 or xz.shape[-1] != 384 or xz.dtype not in (torch.float32, torch.bfloat16):
+        raise NbssError(f"online Mamba core: xz must be [BF,T,384] in fp32 or bf16, got {tuple(xz.shape)} {xz.dtype}")
+    if len(params) != 7 or any(t is None or t.numel() != n for t, n in zip(params, MAMBA_PARAM_SIZES)):
+        raise NbssError(f"online Mamba core: {which} must be (conv1d.weight, conv1d.bias, x_proj.weight, dt_proj.weight, dt_proj.bias, A_log, D) of "
+                        f"{MAMBA_PARAM_SIZES} elements (got sizes {[None if t is None else t.numel() for t in params]})")
+    return NBSS_BF16 if xz.dtype == torch.bfloat16 else NBSS_F32, xz.shape[0], xz.shape[1]
+
+
+def online_mamba_train_fwd(lib: Lib, params: List[Tensor], xz: Tensor, keep: bool = True):
+    """out [BF,T,192] = y * SiLU(z) of Mamba(96, d_state 16, d_conv 4, expand 2) on xz [BF,T,384] (fp32 or bf16); params: the seven fp32 tensors in
+    state_dict layout.  -> (out, save): `save` is what online_mamba_train_bwd needs (None with keep=False: inference)"""
+    dt, BF, T = _online_mamba_dims(params, xz)
+    out = torch.empty(BF, T, 192, dtype=xz.dtype, device=xz.device)
+    save = scratch(_online_bytes(lib, "nbss_online_mamba_train_save_bytes", dt, BF, T), xz.device) if keep else None
+    ws = scratch(_online_bytes(lib, "nbss_online_mamba_train_ws_bytes", dt, BF, T), xz.device)
+    lib.call("nbss_online_mamba_train_fwd", dt, BF, T, _ptr(lib, xz), *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, out), _ptr(lib, save),
+             _ptr(lib, ws), _stream(lib, xz))
+    return out, save
+
+
+def online_mamba_train_bwd(lib: Lib, params: List[Tensor], xz: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None):
+    """-> (dxz, grads): the seven fp32 parameter gradients are WRITTEN into `grads` (uninitialised buffers of the parameters' shapes when not given)"""
+    dt, BF, T = _online_mamba_dims(params, xz)
+    if tuple(dy.shape) != (BF, T, 192) or dy.dtype != xz.dtype:
+        raise NbssError(f"online Mamba core: dy {tuple(dy.shape)} {dy.dtype} does not match [{BF},{T},192] {xz.dtype}")
+    if grads is None:
+        grads = [torch.empty_like(p) for p in params]
+    _online_mamba_dims(grads, xz, "grads")
+    dxz = torch.empty_like(xz)
+    ws = scratch(_online_bytes(lib, "nbss_online_mamba_train_ws_bytes", dt, BF, T), xz.device)
+    lib.call("nbss_online_mamba_train_bwd", dt, BF, T, _ptr(lib, xz), *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, save), _ptr(lib, dy),
+             _ptr(lib, dxz), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, xz))
+    return dxz, grads
 
 
 # the cross-band trio
