@@ -29,15 +29,6 @@
 #include "blocks.h"
 #include "nb.h"
 
-extern "C" {
-int64_t nbss_online_ret_train_save_bytes(int dtype, int64_t BF, int T);
-int64_t nbss_online_ret_train_ws_bytes(int dtype, int64_t BF, int T);
-int nbss_online_ret_train_fwd(int dtype, int64_t BF, int T, const void* q, const void* k, const void* v, const void* g, float k_scale, const float* decay,
-                              void* out, void* save, void* ws, void* stream);
-int nbss_online_ret_train_bwd(int dtype, int64_t BF, int T, const void* q, const void* k, const void* v, const void* g, float k_scale, const float* decay,
-                              const void* save, const void* d_out, void* dq, void* dk, void* dv, void* dg, void* ws, void* stream);
-}
-
 #define TS_H 96
 #define TS_V 192
 #define TS_THREADS 256

@@ -18,8 +18,8 @@ every other refusal is an ordinary torch.nn case.  The three blocks of the form 
 module's nn.Linear projections around it; where both TSA and RETENTION accept a call, TSA takes it.  MAMBA (the 'mamba(16,4)' variant, which itself is
 behind NBSS_ONLINE_MAMBA=1 at construction: models/arch/OnlineSpatialNet.py) is asked per Mamba module, not per layer: its node has the inputs (xz, the seven
 parameters of the core) and the module's in_proj / out_proj stay torch GEMMs around it (`mamba_forward`); the backward recomputes the states from checkpoints
-every MAMBA_CKPT frames.  Without autograd (no_grad, or nothing requires a gradient)
-the forward entry runs alone under no_grad and keeps nothing.  With TCONVFFN, TSA and XBAND on, a 'ret(2)' training layer is three native nodes and no torch op."""
+every MAMBA_CKPT frames.  `_residual` and `mamba_forward` both stand on `_node`: the autograd node, or without autograd (no_grad, or nothing requires a
+gradient) the forward entry alone under no_grad, which keeps nothing.  With TCONVFFN, TSA and XBAND on, a 'ret(2)' training layer is three native nodes and no torch op."""
 from __future__ import annotations
 
 import contextlib
@@ -392,6 +392,7 @@ def _kernel_params(params) -> List[Optional[Tensor]]:
 
 _xband_kernel_params = _kernel_params  # (the name tests/test_online_xband_train.py calls it by)
 
+
 def _residual_fn(name: str, block: Block, doc: str):
     """the autograd Function `name` of y = x + block(x) through the HIP kernels; inputs (lib, x, *the block's parameters): the parameters are inputs of the
     node, so p.grad is populated the usual way.  One backward per forward: the saved state is freed by it (retain_graph and double backward are refused)."""
@@ -432,18 +433,20 @@ OnlineMambaFn = _residual_fn("OnlineMambaFn", MAMBA, "out = y * SiLU(z) of a Mam
                              "MAMBA_CKPT frames; the backward recomputes the states of an interval from its checkpoint.")
 
 
+def _node(block: Block, fn, x: Tensor, params) -> Tensor:
+    """the block's node `fn` on x (in the stream dtype already); without autograd (no_grad, or nothing requires a gradient) the forward entry alone,
+    which keeps nothing"""
+    lib = _lib_for(block, x)
+    if _needs_grad(x, params):
+        return fn.apply(lib, x, *params)
+    with torch.no_grad():
+        return getattr(ops, block.entry + "_fwd")(lib, _kernel_params(params), x.contiguous(), keep=False)[0]
+
+
 def _residual(block: Block, fn, layer, x: Tensor, *call) -> Tensor:
     """x + block(x) for a call the gate accepted (`call`: what the call adds, as `take` got it); in the dtype of x.  Without autograd (no_grad, or nothing
     requires a gradient) the forward runs alone and keeps nothing."""
-    lib = _lib_for(block, x)
-    params = block.params(layer, *call)
-    xs = x.to(_stream_dtype(x))
-    if _needs_grad(x, params):
-        y = fn.apply(lib, xs, *params)
-    else:
-        with torch.no_grad():
-            y = getattr(ops, block.entry + "_fwd")(lib, _kernel_params(params), xs.contiguous(), keep=False)[0]
-    return y.to(x.dtype)
+    return _node(block, fn, x.to(_stream_dtype(x)), block.params(layer, *call)).to(x.dtype)
 
 
 # x + T-ConvFFN(x) for a call `eligible` accepted, and x + fconv1, + full, + fconv2 for a call `xband_eligible` accepted: (layer, x) -> y;
@@ -456,15 +459,7 @@ tsa_residual = functools.partial(_residual, TSA, OnlineTSAFn)
 def mamba_forward(mamba, u: Tensor) -> Tensor:
     """Mamba.forward(u) for a call `mamba_eligible` accepted: in_proj and out_proj are the module's own nn.Linear's (torch GEMMs, autocast like any other),
     the core between them is native.  Without autograd the forward runs alone and keeps nothing."""
-    lib = _lib_for(MAMBA, u)
-    xz = mamba.in_proj(u).to(_stream_dtype(u))
-    params = mamba_params(mamba)
-    if _needs_grad(xz, params):
-        out = OnlineMambaFn.apply(lib, xz, *params)
-    else:
-        with torch.no_grad():
-            out = ops.online_mamba_train_fwd(lib, _kernel_params(params), xz.contiguous(), keep=False)[0]
-    return mamba.out_proj(out)
+    return mamba.out_proj(_node(MAMBA, OnlineMambaFn, mamba.in_proj(u).to(_stream_dtype(u)), mamba_params(mamba)))
 
 
 class OnlineRetentionFn(torch.autograd.Function):

@@ -8,7 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional
 
 import torch
 from torch import Tensor
@@ -545,6 +546,8 @@ def graph_guard_check(ctx, what: str):
 
 
 # ---- OnlineSpatialNet: the blocks for training (csrc/online_train.hip, online_ret_train.hip, online_tsa_train.hip, online_xband_train.hip, online_mamba_train.hip)
+# The four blocks with parameters are one `OnlineBlock` record each and share one driver (`_online_fwd` / `_online_bwd`); the records state where the entry
+# points differ.  The retention core alone (four tensor inputs, no parameters, four gradients) keeps its two functions on the shared `_online_dims`.
 def _online_bytes(lib: Lib, name: str, *dims: int) -> int:
     n = getattr(lib, name)(*dims)
     if n < 0:
@@ -552,128 +555,179 @@ def _online_bytes(lib: Lib, name: str, *dims: int) -> int:
     return n
 
 
-def _online_train_dims(x: Tensor, what: str = "online T-ConvFFN"):
-    if x.dim() != 4 or x.shape[-1] != 96 or x.dtype not in (torch.float32, torch.bfloat16):
-        raise NbssError(f"{what}: x must be [B,F,T,96] in fp32 or bf16, got {tuple(x.shape)} {x.dtype}")
-    return (NBSS_BF16 if x.dtype == torch.bfloat16 else NBSS_F32, *x.shape[:3])
+def _online_dims(what: str, name: str, t: Tensor, width: int, ranks=(3,)):
+    """`t` must be fp32 or bf16, `width` wide and of a rank in `ranks` -> (dtype, B, F, T) for ranks (4,), else (dtype, BF, T) with the leading sizes folded"""
+    if t.dim() not in ranks or t.shape[-1] != width or t.dtype not in (torch.float32, torch.bfloat16):
+        shapes = " or ".join(f"[BF,T,{width}]" if r == 3 else f"[B,F,T,{width}]" for r in ranks)
+        raise NbssError(f"{what}: {name} must be {shapes} in fp32 or bf16, got {tuple(t.shape)} {t.dtype}")
+    dt = NBSS_BF16 if t.dtype == torch.bfloat16 else NBSS_F32
+    return (dt, *t.shape[:3]) if ranks == (4,) else (dt, math.prod(t.shape[:-2]), t.shape[-2])
 
 
-def _online_block_fwd(lib: Lib, entry: str, what: str, params: List[Tensor], x: Tensor, save_bytes, ws, check=None):
-    """the forward of a block y = x + block(x) on the [B,F,T,96] stream: `save_bytes(lib, dtype, B, F, T)` sizes what backward needs (None: keep nothing),
-    `ws(lib, x)` provides the workspace, `check(which, tensors, F)` (optional) the sizes of the parameters -> (y, save)"""
-    dt, B, F, T = _online_train_dims(x, what)
-    if check is not None:
-        check("params", params, F)
-    y = torch.empty_like(x)
-    save = None if save_bytes is None else scratch(save_bytes(lib, dt, B, F, T), x.device)
-    buf = ws(lib, x)  # (held until the call returns)
-    lib.call(entry, dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save), _ptr(lib, buf), _stream(lib, x))
+@dataclass(frozen=True)
+class OnlineBlock:
+    """the C ABI of one block with parameters (include/nbss_hip.h).  Forward: (dtype, sizes..., inputs..., y, save, ws, stream); backward: (dtype, sizes...,
+    inputs..., save, dy, dx, one gradient per parameter..., ws, stream); the two size functions: (dtype, sizes..., extras...)."""
+    what: str  # the label in errors
+    fwd: str  # the four C symbols
+    bwd: str
+    save_bytes: str
+    ws_bytes: str
+    x: str  # the input: its name in errors, its width, the ranks it may have (`_online_dims`) and the width of the output
+    width: int
+    out_width: int
+    ranks: tuple
+    sizes: Callable  # (F, or None without a frequency axis) -> the element count of every parameter slot
+    want: str  # ... in words, for the refusal ({F}, {sizes} are filled in)
+    grads_want: Optional[str] = None  # the refusal of a wrong `grads` where it has a wording of its own
+    optional: tuple = ()  # the slots that may be None (TSA: wk, absent with shared keys)
+    consts: int = 0  # trailing slots that are inputs without a gradient (TSA: decay)
+    size_extra: Callable = lambda params: ()  # the extra integers the two size functions take (TSA: share_qk)
+    x_first: bool = False  # the input stands before the parameters in the call (Mamba), not after them
+    new_grad: Callable = torch.empty_like  # a gradient buffer when `grads` is not given: the backward WRITES it; torch.zeros_like: it ACCUMULATES (T-ConvFFN)
+    cached_ws: bool = False  # the workspace is the shared cached one (`_online_ws`), not a fresh one per call
+
+
+_T3 = 192 * 24 * 3  # a T-conv of the T-ConvFFN: 192 channels in 8 groups, 3 taps
+ONLINE_TCONVFFN = OnlineBlock(
+    what="online T-ConvFFN", fwd="nbss_online_tconvffn_train_fwd", bwd="nbss_online_tconvffn_train_bwd",
+    save_bytes="nbss_online_tconvffn_train_save_bytes", ws_bytes="nbss_online_tconvffn_train_ws_bytes", x="x", width=96, out_width=96, ranks=(4,),
+    sizes=lambda F: (96, 96, 192 * 96, 192, _T3, 192, _T3, 192, 192, 192, _T3, 192, 96 * 192, 96),
+    want="the 14 tensors of LayerNorm, 1x1, T-conv, T-conv, GroupNorm, T-conv, 1x1 (weight, bias each) of {sizes} elements", new_grad=torch.zeros_like)
+ONLINE_XBAND = OnlineBlock(
+    what="online cross-band", fwd="nbss_online_xband_train_fwd", bwd="nbss_online_xband_train_bwd", save_bytes="nbss_online_xband_save_bytes",
+    ws_bytes="nbss_online_xband_ws_bytes", x="x", width=96, out_width=96, ranks=(4,),
+    sizes=lambda F: (96, 96, 96 * 12 * 5, 96, 96, 96, 96, 8 * 96, 8, 8 * F * F, 8 * F, 96 * 8, 96, 96, 96, 96 * 12 * 5, 96, 96),
+    want="the 18 tensors of fconv1, norm_full, squeeze, full, unsqueeze, fconv2 for {F} frequencies", cached_ws=True)
+# y = x + out_proj(SiLU(g) * RMSNorm_head(chunk_retention(q, k, v))) on LayerNorm(x)
+ONLINE_TSA = OnlineBlock(
+    what="online retention block", fwd="nbss_online_tsa_train_fwd", bwd="nbss_online_tsa_train_bwd", save_bytes="nbss_online_tsa_save_bytes",
+    ws_bytes="nbss_online_tsa_ws_bytes", x="x", width=96, out_width=96, ranks=(3, 4),
+    sizes=lambda F: (96, 96, 96 * 96, 96 * 96, 192 * 96, 192 * 96, 96 * 192, 4),
+    want="(ln_w, ln_b, wq, wk or None, wv, wg, wo, decay) of 96, 96, 96x96, 96x96, 192x96, 192x96, 96x192 and 4 elements",
+    grads_want="grads must match the seven parameters (None where the parameter is absent, and at decay)", optional=(3,), consts=1,
+    size_extra=lambda params: (int(params[3] is None),), cached_ws=True)
+# y * SiLU(z) from xz = in_proj(u)
+ONLINE_MAMBA = OnlineBlock(
+    what="online Mamba core", fwd="nbss_online_mamba_train_fwd", bwd="nbss_online_mamba_train_bwd", save_bytes="nbss_online_mamba_train_save_bytes",
+    ws_bytes="nbss_online_mamba_train_ws_bytes", x="xz", width=384, out_width=192, ranks=(3,),
+    sizes=lambda F: (192 * 4, 192, 38 * 192, 192 * 6, 192, 192 * 16, 192),
+    want="(conv1d.weight, conv1d.bias, x_proj.weight, dt_proj.weight, dt_proj.bias, A_log, D) of {sizes} elements", x_first=True)
+
+
+def _online_check(rec: OnlineBlock, which: str, tensors, F, none_at):
+    """the entry points take bare pointers: `tensors` ('params' or 'grads') must have the sizes the kernels will read / write, and None exactly at `none_at`"""
+    want = rec.sizes(F)
+    expect, got = list(want), [None if t is None else t.numel() for t in tensors]
+    for i in none_at:
+        expect[i] = None
+    if got != expect:
+        if which == "grads" and rec.grads_want is not None:
+            raise NbssError(f"{rec.what}: {rec.grads_want}")
+        raise NbssError(f"{rec.what}: {which} must be {rec.want.format(F=F, sizes=want)} (got sizes {got})")
+
+
+def _online_head(rec: OnlineBlock, params, x: Tensor):
+    """the checks both directions share -> (dtype, sizes...), F or None, the size functions' extras"""
+    dims = _online_dims(rec.what, rec.x, x, rec.width, rec.ranks)
+    F = dims[2] if rec.ranks == (4,) else None
+    _online_check(rec, "params", params, F, [i for i in rec.optional if i < len(params) and params[i] is None])
+    return dims, F, rec.size_extra(params)
+
+
+def _online_ws(rec: OnlineBlock, lib: Lib, dims, extra, device) -> Tensor:
+    """the workspace of a call: fresh, or with rec.cached_ws ONE buffer per (library, device, dtype, extras), shared by every layer and both directions (the
+    calls are in order on one stream and each writes what it reads).  A new shape frees the old buffer before the new one is allocated.  The slots live on the
+    Lib object and go with it."""
+    if not rec.cached_ws:
+        return scratch(_online_bytes(lib, rec.ws_bytes, *dims, *extra), device)
+    slots, slot = vars(lib).setdefault("_online_ws", {}), (rec.ws_bytes, device, dims[0], *extra)
+    if slot not in slots or slots[slot][0] != dims[1:]:
+        slots.pop(slot, None)
+        slots[slot] = (dims[1:], scratch(_online_bytes(lib, rec.ws_bytes, *dims, *extra), device))
+    return slots[slot][1]
+
+
+def _online_ins(rec: OnlineBlock, lib: Lib, params, x: Tensor):
+    """the pointers of the inputs in the order of the block's entry points"""
+    ps, xs = [_ptr(lib, p, torch.float32) for p in params], [_ptr(lib, x)]
+    return xs + ps if rec.x_first else ps + xs
+
+
+def _online_fwd(rec: OnlineBlock, lib: Lib, params, x: Tensor, keep: bool = True, ws: Optional[Tensor] = None):
+    """the forward of a block -> (y, save): `save` is what the backward needs (None with keep=False); `ws` overrides the workspace"""
+    dims, _, extra = _online_head(rec, params, x)
+    y = torch.empty_like(x) if rec.out_width == rec.width else x.new_empty((*x.shape[:-1], rec.out_width))
+    save = scratch(_online_bytes(lib, rec.save_bytes, *dims, *extra), x.device) if keep else None
+    if ws is None:
+        ws = _online_ws(rec, lib, dims, extra, x.device)  # (held until the call returns)
+    lib.call(rec.fwd, *dims, *_online_ins(rec, lib, params, x), _ptr(lib, y), _ptr(lib, save), _ptr(lib, ws), _stream(lib, x))
     return y, save
 
 
-def _online_block_bwd(lib: Lib, entry: str, what: str, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads, new_grad, ws, check=None):
-    """the backward of the same: `new_grad(p)` makes the gradient buffer of a parameter when `grads` is None -> (dx, grads)"""
-    dt, B, F, T = _online_train_dims(x, what)
-    if dy.shape != x.shape or dy.dtype != x.dtype:
-        raise NbssError(f"{what}: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
-    if check is not None:
-        check("params", params, F)
+def _online_bwd(rec: OnlineBlock, lib: Lib, params, x: Tensor, save: Tensor, dy: Tensor, grads=None, ws: Optional[Tensor] = None):
+    """the backward of the same -> (dx, grads): `grads` has the slots of `params` (None where a parameter is absent or a constant)"""
+    dims, F, extra = _online_head(rec, params, x)
+    if tuple(dy.shape) != (*x.shape[:-1], rec.out_width) or dy.dtype != x.dtype:
+        like = f"x {tuple(x.shape)}" if rec.out_width == rec.width else f"[{dims[1]},{dims[2]},{rec.out_width}]"
+        raise NbssError(f"{rec.what}: dy {tuple(dy.shape)} {dy.dtype} does not match {like} {x.dtype}")
+    n = len(params) - rec.consts
     if grads is None:
-        grads = [new_grad(p) for p in params]
-    if check is not None:
-        check("grads", grads, F)
-    dx, buf = torch.empty_like(x), ws(lib, x)
-    lib.call(entry, dt, B, F, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy), _ptr(lib, dx),
-             *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, buf), _stream(lib, x))
+        grads = [None if p is None else rec.new_grad(p) for p in params[:n]] + [None] * rec.consts
+    else:
+        _online_check(rec, "grads", grads, F, [i for i, p in enumerate(params) if p is None or i >= n])
+    dx = torch.empty_like(x)
+    if ws is None:
+        ws = _online_ws(rec, lib, dims, extra, x.device)
+    lib.call(rec.bwd, *dims, *_online_ins(rec, lib, params, x), _ptr(lib, save), _ptr(lib, dy), _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads[:n]),
+             _ptr(lib, ws), _stream(lib, x))
     return dx, grads
 
 
-# the causal T-ConvFFN
-def online_tconvffn_train_save_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_bytes(lib, "nbss_online_tconvffn_train_save_bytes", dtype, B, F, T)
+def _online_sizer(name: str):
+    return lambda lib, dtype, B, F, T: _online_bytes(lib, name, dtype, B, F, T)
 
 
-def online_tconvffn_train_ws_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_bytes(lib, "nbss_online_tconvffn_train_ws_bytes", dtype, B, F, T)
-
-
-def _online_tconvffn_ws(lib: Lib, x: Tensor) -> Tensor:
-    """a fresh workspace per call"""
-    return scratch(online_tconvffn_train_ws_bytes(lib, *_online_train_dims(x)), x.device)
+online_tconvffn_train_save_bytes, online_tconvffn_train_ws_bytes = _online_sizer(ONLINE_TCONVFFN.save_bytes), _online_sizer(ONLINE_TCONVFFN.ws_bytes)
+online_xband_save_bytes, online_xband_ws_bytes = _online_sizer(ONLINE_XBAND.save_bytes), _online_sizer(ONLINE_XBAND.ws_bytes)
 
 
 def online_tconvffn_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True):
     """y = x + T-ConvFFN(x) on x [B,F,T,96] (fp32 or bf16); params: the 14 fp32 tensors in the order of include/nbss_hip.h (state_dict layout).
     -> (y, save): `save` is what online_tconvffn_train_bwd needs (None with keep=False: inference)"""
-    return _online_block_fwd(lib, "nbss_online_tconvffn_train_fwd", "online T-ConvFFN", params, x, online_tconvffn_train_save_bytes if keep else None,
-                             _online_tconvffn_ws)
+    return _online_fwd(ONLINE_TCONVFFN, lib, params, x, keep)
 
 
 def online_tconvffn_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None):
     """-> (dx, grads): dx includes the residual path; the 14 fp32 parameter gradients are ACCUMULATED into `grads` (zeros of the parameters' shapes when
     not given)"""
-    return _online_block_bwd(lib, "nbss_online_tconvffn_train_bwd", "online T-ConvFFN", params, x, save, dy, grads, torch.zeros_like, _online_tconvffn_ws)
+    return _online_bwd(ONLINE_TCONVFFN, lib, params, x, save, dy, grads)
 
 
-# the chunkwise retention core
-def _online_ret_dims(q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor):
-    if q.dim() != 3 or q.shape[-1] != 96 or q.dtype not in (torch.float32, torch.bfloat16):
-        raise NbssError(f"online retention: q must be [BF,T,96] in fp32 or bf16, got {tuple(q.shape)} {q.dtype}")
-    BF, T = q.shape[:2]
-    for name, t, width in (("k", k, 96), ("v", v, 192), ("g", g, 192)):
-        if t is not None and (tuple(t.shape) != (BF, T, width) or t.dtype != q.dtype):
-            raise NbssError(f"online retention: {name} must be [{BF},{T},{width}] {q.dtype}, got {tuple(t.shape)} {t.dtype}")
-    return NBSS_BF16 if q.dtype == torch.bfloat16 else NBSS_F32, BF, T
+def online_xband_ws(lib: Lib, x: Tensor) -> Tensor:
+    """the workspace of the cross-band entry points for the shape of x: ONE buffer per (library, device, dtype, shape), shared by every layer and by both
+    directions (its largest part is the reused backward kernels' workspace, ~0.9 GB at batch 4 in fp32; the calls are in order on one stream and each
+    writes what it reads).  A new shape on the same device and dtype replaces the old buffer."""
+    return _online_ws(ONLINE_XBAND, lib, _online_dims(ONLINE_XBAND.what, "x", x, 96, (4,)), (), x.device)
 
 
-def online_ret_train_fwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, keep: bool = True):
-    """out [BF,T,192] = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)); k = None shares the keys with q; decay [4] fp32: the per-head gamma.
-    -> (out, save): `save` is what online_ret_train_bwd needs (None with keep=False: inference)"""
-    dt, BF, T = _online_ret_dims(q, k, v, g)
-    out = torch.empty_like(v)
-    save = scratch(_online_bytes(lib, "nbss_online_ret_train_save_bytes", dt, BF, T), q.device) if keep else None
-    ws = scratch(_online_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
-    lib.call("nbss_online_ret_train_fwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
-             _ptr(lib, out), _ptr(lib, save), _ptr(lib, ws), _stream(lib, q))
-    return out, save
+def online_xband_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True, ws: Optional[Tensor] = None):
+    """y = the cross-band trio (x + fconv1, + full, + fconv2) on x [B,F,T,96] (fp32 or bf16); params: the 18 fp32 tensors in state_dict order.
+    -> (y, save): `save` (the inputs of the second and third block) is what online_xband_train_bwd needs (None with keep=False: inference)"""
+    return _online_fwd(ONLINE_XBAND, lib, params, x, keep, ws)
 
 
-def online_ret_train_bwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, save: Tensor, d_out: Tensor):
-    """-> (dq, dk, dv, dg), written (not accumulated); dk includes k_scale and is None when k is (dq then holds both roles of q)"""
-    dt, BF, T = _online_ret_dims(q, k, v, g)
-    if d_out.shape != v.shape or d_out.dtype != v.dtype:
-        raise NbssError(f"online retention: d_out {tuple(d_out.shape)} {d_out.dtype} does not match v {tuple(v.shape)} {v.dtype}")
-    dq, dk, dv, dg = torch.empty_like(q), None if k is None else torch.empty_like(q), torch.empty_like(v), torch.empty_like(v)
-    ws = scratch(_online_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
-    lib.call("nbss_online_ret_train_bwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
-             _ptr(lib, save), _ptr(lib, d_out), _ptr(lib, dq), _ptr(lib, dk), _ptr(lib, dv), _ptr(lib, dg), _ptr(lib, ws), _stream(lib, q))
-    return dq, dk, dv, dg
-
-
-# the whole retention block: y = x + out_proj(SiLU(g) * RMSNorm_head(chunk_retention(q, k, v))) on LayerNorm(x)
-def _online_tsa_dims(params: List[Optional[Tensor]], x: Tensor):
-    """params: (ln_w, ln_b, wq, wk or None, wv, wg, wo, decay); x [BF,T,96] or [B,F,T,96] -> (dtype, BF, T, share_qk)"""
-    if x.dim() not in (3, 4) or x.shape[-1] != 96 or x.dtype not in (torch.float32, torch.bfloat16):
-        raise NbssError(f"online retention block: x must be [BF,T,96] or [B,F,T,96] in fp32 or bf16, got {tuple(x.shape)} {x.dtype}")
-    want = [96, 96, 96 * 96, 96 * 96, 192 * 96, 192 * 96, 96 * 192, 4]
-    if len(params) != 8 or any(i != 3 if t is None else t.numel() != n for i, (t, n) in enumerate(zip(params, want))):
-        raise NbssError("online retention block: params must be (ln_w, ln_b, wq, wk or None, wv, wg, wo, decay) of 96, 96, 96x96, 96x96, 192x96, 192x96, 96x192 "
-                        f"and 4 elements (got sizes {[None if t is None else t.numel() for t in params]})")
-    return NBSS_BF16 if x.dtype == torch.bfloat16 else NBSS_F32, x.numel() // (x.shape[-2] * 96), x.shape[-2], int(params[3] is None)
-
-
-_TSA_WS: Dict[tuple, Tensor] = {}
+def online_xband_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None,
+                           ws: Optional[Tensor] = None):
+    """-> (dx, grads): dx includes the residual paths; the 18 fp32 parameter gradients are WRITTEN into `grads` (uninitialised buffers of the parameters'
+    shapes when not given)"""
+    return _online_bwd(ONLINE_XBAND, lib, params, x, save, dy, grads, ws)
 
 
 def online_tsa_ws(lib: Lib, dt: int, BF: int, T: int, share: int, device) -> Tensor:
     """the workspace of the retention-block entry points: ONE buffer per (library, device, dtype, keys), shared by every layer and both directions (the calls
     are in order on one stream and each writes what it reads); a new shape replaces the old buffer"""
-    slot, shape = (id(lib), device, dt, share), (BF, T)
-    have = _TSA_WS.get(slot)
-    if have is None or have[0] != shape:
-        _TSA_WS.pop(slot, None)
-        have = _TSA_WS[slot] = (shape, scratch(_online_bytes(lib, "nbss_online_tsa_ws_bytes", dt, BF, T, share), device))
-    return have[1]
+    return _online_ws(ONLINE_TSA, lib, (dt, BF, T), (share,), device)
 
 
 def online_tsa_save_views(lib: Lib, save: Tensor, x: Tensor, share_qk: bool) -> Dict[str, Optional[Tensor]]:
@@ -695,116 +749,55 @@ def online_tsa_save_views(lib: Lib, save: Tensor, x: Tensor, share_qk: bool) -> 
 def online_tsa_train_fwd(lib: Lib, params: List[Optional[Tensor]], x: Tensor, keep: bool = True):
     """y = x + the retention block on x [BF,T,96] or [B,F,T,96] (fp32 or bf16); params: the fp32 tensors (ln_w, ln_b, wq, wk or None: shared keys, wv, wg, wo)
     in state_dict layout and decay [4], the per-head gamma.  -> (y, save): `save` is what online_tsa_train_bwd needs (None with keep=False: inference)"""
-    dt, BF, T, share = _online_tsa_dims(params, x)
-    y = torch.empty_like(x)
-    save = scratch(_online_bytes(lib, "nbss_online_tsa_save_bytes", dt, BF, T, share), x.device) if keep else None
-    ws = online_tsa_ws(lib, dt, BF, T, share, x.device)
-    lib.call("nbss_online_tsa_train_fwd", dt, BF, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, y), _ptr(lib, save),
-             _ptr(lib, ws), _stream(lib, x))
-    return y, save
+    return _online_fwd(ONLINE_TSA, lib, params, x, keep)
 
 
 def online_tsa_train_bwd(lib: Lib, params: List[Optional[Tensor]], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Optional[Tensor]]] = None):
     """-> (dx, grads): dx includes the residual path; the fp32 gradients of the seven parameters are WRITTEN into `grads` (eight entries in the order of
     `params`: None at wk with shared keys and at decay; uninitialised buffers of the parameters' shapes when not given)"""
-    dt, BF, T, share = _online_tsa_dims(params, x)
-    if dy.shape != x.shape or dy.dtype != x.dtype:
-        raise NbssError(f"online retention block: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
-    if grads is None:
-        grads = [None if p is None else torch.empty_like(p) for p in params[:7]] + [None]
-    if len(grads) != 8 or grads[7] is not None or any(g is not None and (p is None or g.numel() != p.numel()) for g, p in zip(grads, params)):
-        raise NbssError("online retention block: grads must match the seven parameters (None where the parameter is absent, and at decay)")
-    dx, ws = torch.empty_like(x), online_tsa_ws(lib, dt, BF, T, share, x.device)
-    lib.call("nbss_online_tsa_train_bwd", dt, BF, T, *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, x), _ptr(lib, save), _ptr(lib, dy),
-             _ptr(lib, dx), *(_ptr(lib, g, torch.float32) for g in grads[:7]), _ptr(lib, ws), _stream(lib, x))
-    return dx, grads
-
-
-# the core of a Mamba block: y * SiLU(z) from xz = in_proj(u)
-MAMBA_PARAM_SIZES = (192 * 4, 192, 38 * 192, 192 * 6, 192, 192 * 16, 192)  # conv1d.weight, conv1d.bias, x_proj.weight, dt_proj.weight, dt_proj.bias, A_log, D
-
-
-def _online_mamba_dims(params: List[Tensor], xz: Tensor, which: str = "params"):
-    if xz.dim() != 3 or xz.shape[-1] != 384 or xz.dtype not in (torch.float32, torch.bfloat16):
-        raise NbssError(f"online Mamba core: xz must be [BF,T,384] in fp32 or bf16, got {tuple(xz.shape)} {xz.dtype}")
-    if len(params) != 7 or any(t is None or t.numel() != n for t, n in zip(params, MAMBA_PARAM_SIZES)):
-        raise NbssError(f"online Mamba core: {which} must be (conv1d.weight, conv1d.bias, x_proj.weight, dt_proj.weight, dt_proj.bias, A_log, D) of "
-                        f"{MAMBA_PARAM_SIZES} elements (got sizes {[None if t is None else t.numel() for t in params]})")
-    return NBSS_BF16 if xz.dtype == torch.bfloat16 else NBSS_F32, xz.shape[0], xz.shape[1]
+    return _online_bwd(ONLINE_TSA, lib, params, x, save, dy, grads)
 
 
 def online_mamba_train_fwd(lib: Lib, params: List[Tensor], xz: Tensor, keep: bool = True):
     """out [BF,T,192] = y * SiLU(z) of Mamba(96, d_state 16, d_conv 4, expand 2) on xz [BF,T,384] (fp32 or bf16); params: the seven fp32 tensors in
     state_dict layout.  -> (out, save): `save` is what online_mamba_train_bwd needs (None with keep=False: inference)"""
-    dt, BF, T = _online_mamba_dims(params, xz)
-    out = torch.empty(BF, T, 192, dtype=xz.dtype, device=xz.device)
-    save = scratch(_online_bytes(lib, "nbss_online_mamba_train_save_bytes", dt, BF, T), xz.device) if keep else None
-    ws = scratch(_online_bytes(lib, "nbss_online_mamba_train_ws_bytes", dt, BF, T), xz.device)
-    lib.call("nbss_online_mamba_train_fwd", dt, BF, T, _ptr(lib, xz), *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, out), _ptr(lib, save),
-             _ptr(lib, ws), _stream(lib, xz))
-    return out, save
+    return _online_fwd(ONLINE_MAMBA, lib, params, xz, keep)
 
 
 def online_mamba_train_bwd(lib: Lib, params: List[Tensor], xz: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None):
     """-> (dxz, grads): the seven fp32 parameter gradients are WRITTEN into `grads` (uninitialised buffers of the parameters' shapes when not given)"""
-    dt, BF, T = _online_mamba_dims(params, xz)
-    if tuple(dy.shape) != (BF, T, 192) or dy.dtype != xz.dtype:
-        raise NbssError(f"online Mamba core: dy {tuple(dy.shape)} {dy.dtype} does not match [{BF},{T},192] {xz.dtype}")
-    if grads is None:
-        grads = [torch.empty_like(p) for p in params]
-    _online_mamba_dims(grads, xz, "grads")
-    dxz = torch.empty_like(xz)
-    ws = scratch(_online_bytes(lib, "nbss_online_mamba_train_ws_bytes", dt, BF, T), xz.device)
-    lib.call("nbss_online_mamba_train_bwd", dt, BF, T, _ptr(lib, xz), *(_ptr(lib, p, torch.float32) for p in params), _ptr(lib, save), _ptr(lib, dy),
-             _ptr(lib, dxz), *(_ptr(lib, g, torch.float32) for g in grads), _ptr(lib, ws), _stream(lib, xz))
-    return dxz, grads
+    return _online_bwd(ONLINE_MAMBA, lib, params, xz, save, dy, grads)
 
 
-# the cross-band trio
-def online_xband_save_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_bytes(lib, "nbss_online_xband_save_bytes", dtype, B, F, T)
+# the chunkwise retention core
+def _online_ret_inputs(q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor):
+    dt, BF, T = _online_dims("online retention", "q", q, 96)
+    for name, t, width in (("k", k, 96), ("v", v, 192), ("g", g, 192)):
+        if t is not None and (tuple(t.shape) != (BF, T, width) or t.dtype != q.dtype):
+            raise NbssError(f"online retention: {name} must be [{BF},{T},{width}] {q.dtype}, got {tuple(t.shape)} {t.dtype}")
+    return dt, BF, T
 
 
-def online_xband_ws_bytes(lib: Lib, dtype: int, B: int, F: int, T: int) -> int:
-    return _online_bytes(lib, "nbss_online_xband_ws_bytes", dtype, B, F, T)
+def online_ret_train_fwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, keep: bool = True):
+    """out [BF,T,192] = SiLU(g) * RMSNorm_head(chunkwise retention(q, k_scale k, v)); k = None shares the keys with q; decay [4] fp32: the per-head gamma.
+    -> (out, save): `save` is what online_ret_train_bwd needs (None with keep=False: inference)"""
+    dt, BF, T = _online_ret_inputs(q, k, v, g)
+    out = torch.empty_like(v)
+    save = scratch(_online_bytes(lib, "nbss_online_ret_train_save_bytes", dt, BF, T), q.device) if keep else None
+    ws = scratch(_online_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
+    lib.call("nbss_online_ret_train_fwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
+             _ptr(lib, out), _ptr(lib, save), _ptr(lib, ws), _stream(lib, q))
+    return out, save
 
 
-def _online_xband_check(what: str, tensors: List[Tensor], F: int):
-    """the entry points take bare pointers: the 18 tensors must have the sizes the kernels will read / write"""
-    want = [96, 96, 96 * 12 * 5, 96, 96, 96, 96, 8 * 96, 8, 8 * F * F, 8 * F, 96 * 8, 96, 96, 96, 96 * 12 * 5, 96, 96]
-    if len(tensors) != 18 or any(t is None or t.numel() != n for t, n in zip(tensors, want)):
-        raise NbssError(f"online cross-band: {what} must be the 18 tensors of fconv1, norm_full, squeeze, full, unsqueeze, fconv2 for {F} frequencies "
-                        f"(got sizes {[None if t is None else t.numel() for t in tensors]})")
-
-
-_XBAND_WS: Dict[tuple, Tensor] = {}
-
-
-def online_xband_ws(lib: Lib, x: Tensor) -> Tensor:
-    """the workspace of the cross-band entry points for the shape of x: ONE buffer per (library, device, dtype, shape), shared by every layer and by both
-    directions (its largest part is the reused backward kernels' workspace, ~0.9 GB at batch 4 in fp32; the calls are in order on one stream and each
-    writes what it reads).  A new shape on the same device and dtype replaces the old buffer."""
-    dt, B, F, T = _online_train_dims(x, "online cross-band")
-    slot, shape = (id(lib), x.device, dt), (B, F, T)
-    have = _XBAND_WS.get(slot)
-    if have is None or have[0] != shape:
-        _XBAND_WS.pop(slot, None)  # (free the old shape's buffer before the new one is allocated)
-        have = _XBAND_WS[slot] = (shape, scratch(online_xband_ws_bytes(lib, dt, B, F, T), x.device))
-    return have[1]
-
-
-def online_xband_train_fwd(lib: Lib, params: List[Tensor], x: Tensor, keep: bool = True, ws: Optional[Tensor] = None):
-    """y = the cross-band trio (x + fconv1, + full, + fconv2) on x [B,F,T,96] (fp32 or bf16); params: the 18 fp32 tensors in state_dict order.
-    -> (y, save): `save` (the inputs of the second and third block) is what online_xband_train_bwd needs (None with keep=False: inference)"""
-    return _online_block_fwd(lib, "nbss_online_xband_train_fwd", "online cross-band", params, x, online_xband_save_bytes if keep else None,
-                             online_xband_ws if ws is None else lambda lib, x: ws, _online_xband_check)
-
-
-def online_xband_train_bwd(lib: Lib, params: List[Tensor], x: Tensor, save: Tensor, dy: Tensor, grads: Optional[List[Tensor]] = None,
-                           ws: Optional[Tensor] = None):
-    """-> (dx, grads): dx includes the residual paths; the 18 fp32 parameter gradients are WRITTEN into `grads` (uninitialised buffers of the parameters'
-    shapes when not given)"""
-    return _online_block_bwd(lib, "nbss_online_xband_train_bwd", "online cross-band", params, x, save, dy, grads, torch.empty_like,
-                             online_xband_ws if ws is None else lambda lib, x: ws, _online_xband_check)
-
+def online_ret_train_bwd(lib: Lib, q: Tensor, k: Optional[Tensor], v: Tensor, g: Tensor, k_scale: float, decay: Tensor, save: Tensor, d_out: Tensor):
+    """-> (dq, dk, dv, dg), written (not accumulated); dk includes k_scale and is None when k is (dq then holds both roles of q)"""
+    dt, BF, T = _online_ret_inputs(q, k, v, g)
+    if d_out.shape != v.shape or d_out.dtype != v.dtype:
+        raise NbssError(f"online retention: d_out {tuple(d_out.shape)} {d_out.dtype} does not match v {tuple(v.shape)} {v.dtype}")
+    dq, dk, dv, dg = torch.empty_like(q), None if k is None else torch.empty_like(q), torch.empty_like(v), torch.empty_like(v)
+    ws = scratch(_online_bytes(lib, "nbss_online_ret_train_ws_bytes", dt, BF, T), q.device)
+    lib.call("nbss_online_ret_train_bwd", dt, BF, T, _ptr(lib, q), _ptr(lib, k), _ptr(lib, v), _ptr(lib, g), k_scale, _ptr(lib, decay, torch.float32),
+             _ptr(lib, save), _ptr(lib, d_out), _ptr(lib, dq), _ptr(lib, dk), _ptr(lib, dv), _ptr(lib, dg), _ptr(lib, ws), _stream(lib, q))
+    return dq, dk, dv, dg
 
