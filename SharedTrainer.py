@@ -130,13 +130,15 @@ class TrainModule(nn.Module):
         # the native streamer keeps packed COPIES of the weights: the key carries a weights version (every in-place update — optimizer step,
         # load_state_dict, load_checkpoint — bumps a parameter's _version), so a cached streamer never serves stale weights
         wver = sum(int(p._version) for p in self.arch.parameters()) + sum(int(b._version) for b in self.arch.buffers())
-        key = (B, chunk, str(x.device), use_graph, native, wver, tuple(id(p) for p in self.arch.parameters()))
+        # (`supported` reads the opt-in switch of the 'mamba(16,4)' step on every call: its answer is part of the key)
+        from nbss_amd.online import NativeOnlineStreamer, supported
+        fits = supported(self.arch) is None
+        key = (B, chunk, str(x.device), use_graph, native, fits, wver, tuple(id(p) for p in self.arch.parameters()))
         if getattr(self, "_streamer_key", None) != key:
-            # on a HIP device the native step (nbss_amd/online.py: HIP kernels for the causal encoder, the recurrent retention and the causal
-            # T-ConvFFN + the cross-band kernels, one HIP graph per chunk) serves the geometry it is built for; everything else — other
-            # attention types / widths, host tensors — takes the torch.nn step (OnlineStreamer)
-            from nbss_amd.online import NativeOnlineStreamer, supported
-            if x.is_cuda and supported(self.arch) is None and chunk <= 32 and native is not False:
+            # on a HIP device the native step (nbss_amd/online.py: HIP kernels for the causal encoder, the recurrent retention, the windowed attention
+            # or the Mamba block and the causal T-ConvFFN + the cross-band kernels, one HIP graph per chunk) serves the geometry it is built for;
+            # everything else — other attention types / widths, host tensors — takes the torch.nn step (OnlineStreamer)
+            if x.is_cuda and fits and chunk <= 32 and native is not False:
                 self._streamer = NativeOnlineStreamer(self.arch, B, chunk, device=x.device, use_graph=use_graph)
             else:
                 self._streamer = OnlineStreamer(self.arch, B, chunk, device=x.device, use_graph=use_graph)

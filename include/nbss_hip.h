@@ -387,6 +387,14 @@ int nbss_online_ret_step(int BF, int C, const float* ln_w, const float* ln_b, co
 int nbss_online_mhsa_step(int BF, int C, int scope, int ring, const float* ln_w, const float* ln_b, const float* win_t, const float* bin, const float* wo_t,
                           const float* bo, float* kring, float* vring, const int32_t* pos, float* x, void* stream);
 int nbss_online_advance(int32_t* pos, int C, void* stream);
+/* 'mamba(16,4)': x += out_proj(y * SiLU(z)) with (xr, z) = in_proj(LayerNorm(x)) and y the selective scan of xr (models/arch/base/mamba.py: Mamba.step) for
+ * d_model 96, expand 2, d_state 16, d_conv 4, dt_rank 6; no bias on in_proj, x_proj, out_proj.  win_t [96][384], xproj_t [192][38] (6 dt_r | 16 B | 16 C),
+ * wo_t [192][96]: in_proj / x_proj / out_proj weights transposed; conv_w [192][4], conv_b [192], dtproj_w [192][6], dtproj_b [192], a_log [192][16], d [192]:
+ * the module's own layouts.  conv_state [BF][3][192]: the last three inputs of the convolution, oldest first; ssm_state [BF][16][192]: h, state-major.  Both
+ * are zeros for an empty stream (the transposes of Mamba.init_state's tensors).  x [BF][C][96] in place.  NBSS_EUNSUPPORTED for C > 32. */
+int nbss_online_mamba_step(int BF, int C, const float* ln_w, const float* ln_b, const float* win_t, const float* conv_w, const float* conv_b,
+                           const float* xproj_t, const float* dtproj_w, const float* dtproj_b, const float* a_log, const float* d, const float* wo_t,
+                           float* conv_state, float* ssm_state, float* x, void* stream);
 /* x += causal T-ConvFFN(x): LayerNorm -> 1x1 -> SiLU -> causal gconv -> SiLU -> causal gconv -> GroupNorm of each FRAME over (24 channels
  * x all F frequencies) -> SiLU -> causal gconv -> SiLU -> 1x1.  w1_t [96][192], w2_t [192][96] transposed; conv weights [192][24][3];
  * s1 s2 s3 [BF][2][192] = the last two input frames of the three convs; a3 [BF][C][192] and gn_sums [B + BF][C][8][2] (the per-frame

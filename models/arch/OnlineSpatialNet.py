@@ -10,7 +10,8 @@ a sequence over time, and the narrow-band attention is causal:
                from mamba_ssm, a CUDA-only wheel it does not pin; the module here is a port from the published equations with mamba_ssm's state_dict
                keys, parity with that package is NOT pinned.  Hence opt-in: constructing the variant raises unless NBSS_ONLINE_MAMBA=1 (read at
                construction, off unless exactly '1').  Its core trains through the HIP kernels of nbss_amd/online_train.py (MAMBA) when
-               NBSS_ONLINE_NATIVE_MAMBA=1; `inference=True` and the streaming interface walk the module's step form (a fixed-size state per block).
+               NBSS_ONLINE_NATIVE_MAMBA=1; `inference=True` and the streaming interface of this module walk its step form (a fixed-size state per block);
+               nbss_amd/online.py streams 'mamba(16,4)' natively (one nbss_online_mamba_step per block) when NBSS_ONLINE_NATIVE_MAMBA_STEP=1.
 Besides the reference's whole-utterance forward this module offers an explicit streaming interface — `init_stream(batch)` /
 `forward_stream(x_chunk, state)` — that carries conv states, a K/V ring (mhsa) or the retention state across chunks; with fixed
 chunk shapes a step is a static kernel sequence and can be captured in a HIP graph (`OnlineStreamer`).

@@ -103,6 +103,7 @@ SIGNATURES = {
     "nbss_online_ret_step": (_I, [_I, _I] + [_P] * 12),
     "nbss_online_mhsa_step": (_I, [_I, _I, _I, _I] + [_P] * 11),
     "nbss_online_advance": (_I, [_P, _I, _P]),
+    "nbss_online_mamba_step": (_I, [_I, _I] + [_P] * 15),
     "nbss_online_tconvffn_step": (_I, [_I, _I, _I] + [_P] * 21),
     "nbss_online_tconvffn_train_save_bytes": (C.c_int64, [_I] * 4),
     "nbss_online_tconvffn_train_ws_bytes": (C.c_int64, [_I] * 4),

@@ -17,30 +17,13 @@
 // latency-bound, not arithmetic-bound); geometry: dim_hidden 96, dim_ffn 192, 8 conv groups, 4 retention heads of 24 / 48 (value factor 2).
 #include "launch.h"
 #include "layout.h"
+#include "online.h"  // ON_H, ON_FFN, ON_CMAX, on_silu, on_layernorm (shared with online_mamba_step.hip)
 
-#define ON_H 96
-#define ON_FFN 192
 #define ON_CG 24
 #define ON_G 8
 #define ON_HEADS 4
 #define ON_DK 24
 #define ON_DV 48
-#define ON_CMAX 32  // frames per chunk
-
-NBSS_DEV float on_silu(float x) { return x / (1.0f + __expf(-x)); }
-
-// LayerNorm over H = 96 of the C frames of one sequence: wave w takes frames w, w + nw, ...; u[c][96] in LDS
-NBSS_DEV void on_layernorm(const float* __restrict__ xrow, int C, const float* __restrict__ lw, const float* __restrict__ lb, float* u) {
-    const int lane = lane_id(), w = wave_id(), nw = (int)(blockDim.x >> 6);
-    for (int c = w; c < C; c += nw) {
-        const float a = xrow[c * ON_H + lane], b = lane < 32 ? xrow[c * ON_H + 64 + lane] : 0.f;
-        const float mean = wave_sum64(a + b) * (1.0f / ON_H);
-        const float da = a - mean, db = lane < 32 ? b - mean : 0.f;
-        const float rstd = rsqrtf(wave_sum64(da * da + db * db) * (1.0f / ON_H) + 1e-5f);
-        u[c * ON_H + lane] = da * rstd * lw[lane] + lb[lane];
-        if (lane < 32) u[c * ON_H + 64 + lane] = db * rstd * lw[64 + lane] + lb[64 + lane];
-    }
-}
 
 // causal Conv1d(C_in -> 96, k = 5) with a 4-frame state: grid = B*F sequences, block = 96 (one output channel per thread)
 __global__ __launch_bounds__(ON_H) void online_encoder_kernel(int C, int C_in, const float* __restrict__ w, const float* __restrict__ b,

@@ -22,13 +22,8 @@
 // A 16, D 1) across the sequences of its workgroup and writes them as one partial row per workgroup; a second launch folds the partial rows in workgroup
 // order.  No atomics, every sum in a fixed order: two calls give the same bits, and a sequence's rows of out and dxz do not depend on the other sequences.
 #include "gb.h"
+#include "mamba_core.h"  // MB_E, MB_N, MB_K, MB_R, MB_J, MB_JL; MbChan, mb_conv, mb_dt, mb_scan_frame (shared with online_mamba_step.hip)
 
-#define MB_E 192
-#define MB_N 16
-#define MB_K 4
-#define MB_R 6
-#define MB_J (MB_R + 2 * MB_N)  // 38: the x_proj outputs of a frame (dt_r, B, C)
-#define MB_JL 40                // their row in LDS
 #define MB_CKPT 8               // frames per run: the forward saves h at the start of each
 #define MB_THREADS MB_E
 #define MB_GRID_CAP 512         // workgroups per launch; more sequences are walked by the grid-stride loop
@@ -75,32 +70,7 @@ struct MbArgs {
     int T;
 };
 
-// torch.nn.functional.softplus (threshold 20)
-NBSS_DEV float mb_softplus(float p) { return p > 20.f ? p : log1pf(expf(p)); }
-
-// the channel's parameters
-struct MbChan {
-    float cw[MB_K], cb, wdt[MB_R], bdt, A[MB_N], dp;
-};
-NBSS_DEV void mb_chan(MbChan& c, const MbArgs& a, int e) {
-#pragma unroll
-    for (int k = 0; k < MB_K; ++k) c.cw[k] = a.cw[e * MB_K + k];
-#pragma unroll
-    for (int r = 0; r < MB_R; ++r) c.wdt[r] = a.wdt[e * MB_R + r];
-#pragma unroll
-    for (int n = 0; n < MB_N; ++n) c.A[n] = -expf(a.alog[e * MB_N + n]);
-    c.cb = a.cb[e];
-    c.bdt = a.bdt[e];
-    c.dp = a.dp[e];
-}
-// dt of the channel at a frame from the frame's x_proj row; `pre` gets the value before the softplus
-NBSS_DEV float mb_dt(const MbChan& c, const float* row, float& pre) {
-    float p = c.bdt;
-#pragma unroll
-    for (int r = 0; r < MB_R; ++r) p += c.wdt[r] * row[r];
-    pre = p;
-    return mb_softplus(p);
-}
+NBSS_DEV void mb_chan(MbChan& c, const MbArgs& a, int e) { mb_chan(c, a.cw, a.cb, a.wdt, a.bdt, a.alog, a.dp, e); }
 
 template <class T>
 __global__ __launch_bounds__(MB_THREADS) void mb_fwd_kernel(MbArgs a) {
@@ -128,7 +98,7 @@ __global__ __launch_bounds__(MB_THREADS) void mb_fwd_kernel(MbArgs a) {
             }
             for (int i = 0; i < m; ++i) {
                 const float xr = load1(xz + (size_t)(t0 + i) * (2 * MB_E) + e);
-                XC[i * MB_E + e] = silu_f(c.cb + c.cw[0] * xm3 + c.cw[1] * xm2 + c.cw[2] * xm1 + c.cw[3] * xr);
+                XC[i * MB_E + e] = mb_conv(c, xm3, xm2, xm1, xr);
                 xm3 = xm2;
                 xm2 = xm1;
                 xm1 = xr;
@@ -150,15 +120,7 @@ __global__ __launch_bounds__(MB_THREADS) void mb_fwd_kernel(MbArgs a) {
             }
             __syncthreads();
             for (int i = 0; i < m; ++i) {
-                const float* row = DBC + i * MB_JL;
-                float pre;
-                const float dt = mb_dt(c, row, pre), xc = XC[i * MB_E + e], dtx = dt * xc;
-                float ys = c.dp * xc;
-#pragma unroll
-                for (int k = 0; k < MB_N; ++k) {
-                    h[k] = expf(dt * c.A[k]) * h[k] + dtx * row[MB_R + k];
-                    ys += row[MB_R + MB_N + k] * h[k];
-                }
+                const float ys = mb_scan_frame(c, h, DBC + i * MB_JL, XC[i * MB_E + e]);
                 const float z = load1(xz + (size_t)(t0 + i) * (2 * MB_E) + MB_E + e);
                 store1(y + (size_t)(t0 + i) * MB_E + e, ys * silu_f(z));
             }

@@ -5,7 +5,8 @@ buffers — a fixed launch sequence that is captured once into a HIP graph and r
 
 `NativeOnlineStreamer(net, batch, chunk)` has the interface of models.arch.OnlineSpatialNet.OnlineStreamer (step / reset / graph) and serves
 the geometry the kernels are built for: attention 'ret(F, share_qk | not_share_qk)' with value factor 2 and no rotary positions, or causal windowed
-attention 'mhsa(N)' over a K / V ring (not the 'mamba(..)' variant: refused with a reason), dim_hidden 96,
+attention 'mhsa(N)' over a K / V ring, or — opt-in, NBSS_ONLINE_NATIVE_MAMBA_STEP=1, read by `supported` on every call, else refused with a reason that
+names the switch — 'mamba(16,4)' / 'mamba(16,4,not_replace_ffn)': one nbss_online_mamba_step (csrc/online_mamba_step.hip) per Mamba block; dim_hidden 96,
 dim_ffn 192, dim_squeeze 8, 4 heads, kernel sizes (5, 3), conv groups (8, 8), encoder kernel 5, norms LN/LN/GN/LN/LN/LN; everything else
 raises NotImplementedError (callers fall back to OnlineStreamer, the torch.nn step)."""
 from __future__ import annotations
@@ -20,15 +21,30 @@ from . import ops
 from ._lib import NBSS_F32, Lib, hip, make_cfg
 
 
+MAMBA_STEP_SWITCH = "NBSS_ONLINE_NATIVE_MAMBA_STEP"
+
+
 def supported(net) -> Optional[str]:
     """None when `net` fits the native step, else the reason"""
     import math
+    import os
     from models.arch.base.retention import MultiScaleRetention, RetNetRelPos
     l0 = net.layers[0]
     r = l0.mhsa
-    if type(r).__name__ == "Mamba" or type(l0.tconvffn).__name__ == "Mamba":
-        return "the 'mamba(..)' variant has no native streaming step (OnlineStreamer walks the module's step form)"
-    if isinstance(r, torch.nn.MultiheadAttention):
+    is_mamba = lambda m: type(m).__name__ == "Mamba"  # noqa: E731
+    ffn_replaced = is_mamba(l0.tconvffn)
+    if is_mamba(r) or ffn_replaced:
+        if os.environ.get(MAMBA_STEP_SWITCH, "0") != "1":  # read per call; off unless exactly '1'
+            return (f"the 'mamba(..)' variant streams natively only with {MAMBA_STEP_SWITCH}=1 (opt-in like every native Mamba path: the project's Mamba stands in "
+                    "for mamba_ssm, parity not pinned); without it OnlineStreamer walks the module's step form")
+        from .online_train import mamba_supported
+        for layer in net.layers:
+            if is_mamba(layer.tconvffn) != ffn_replaced:
+                return "every layer must replace its T-ConvFFN by a Mamba, or none"
+            why = mamba_supported(layer.mhsa) or (mamba_supported(layer.tconvffn) if ffn_replaced else None)
+            if why is not None:
+                return "mamba: " + why
+    elif isinstance(r, torch.nn.MultiheadAttention):
         if net.rope is not False or getattr(net, "attn_scope", math.inf) is math.inf or net.attn_scope > 4096:
             return "windowed attention needs a finite window 'mhsa(N)' (N <= 4096) and no ALiBi / rotary positions"
         if (r.embed_dim, r.num_heads) != (96, 4) or r.in_proj_bias is None:
@@ -38,12 +54,14 @@ def supported(net) -> Optional[str]:
             return "attention must be 'mhsa(N)' or retention without rotary positions ('ret(2)' with rope: false)"
         if not isinstance(r, MultiScaleRetention) or (r.embed_dim, r.value_dim, r.num_heads, r.look_ahead) != (96, 192, 4, 0):
             return "retention geometry must be embed 96, value 192 (factor 2), 4 heads, no look-ahead"
-    if net.encoder.kernel_size[0] != 5 or net.encoder.in_channels > 32 or l0.squeeze[0].out_channels != 8 or l0.tconvffn[1].out_channels != 192:
+    # (a Mamba in the T-ConvFFN's place has no dim_ffn, no T-convs and no GroupNorm: its LayerNorm is `norm_tconvffn`)
+    if net.encoder.kernel_size[0] != 5 or net.encoder.in_channels > 32 or l0.squeeze[0].out_channels != 8 or (not ffn_replaced and l0.tconvffn[1].out_channels != 192):
         return "geometry must be encoder kernel 5, dim_squeeze 8, dim_ffn 192"
-    if l0.tconvffn[3].kernel_size[0] != 3 or l0.tconvffn[3].groups != 8 or l0.fconv1[1].kernel_size[0] != 5 or l0.fconv1[1].groups != 8:
+    if (not ffn_replaced and (l0.tconvffn[3].kernel_size[0] != 3 or l0.tconvffn[3].groups != 8)) or l0.fconv1[1].kernel_size[0] != 5 or l0.fconv1[1].groups != 8:
         return "kernel sizes (5, 3) and conv groups (8, 8)"
-    kinds = [type(m).__name__ for m in (l0.norm_mhsa, l0.tconvffn[0], l0.tconvffn[6], l0.fconv1[0], l0.fconv2[0], l0.norm_full)]
-    if kinds != ["LayerNorm", "LayerNorm", "GroupNorm", "LayerNorm", "LayerNorm", "LayerNorm"]:
+    ffn_norms = (l0.norm_tconvffn,) if ffn_replaced else (l0.tconvffn[0], l0.tconvffn[6])
+    kinds = [type(m).__name__ for m in (l0.norm_mhsa, *ffn_norms, l0.fconv1[0], l0.fconv2[0], l0.norm_full)]
+    if kinds != ["LayerNorm", "LayerNorm"] + ["GroupNorm"] * (not ffn_replaced) + ["LayerNorm"] * 3:
         return f"norms must be LN, LN, GN, LN, LN, LN (got {kinds})"
     if any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in net.modules()):
         return "dropout must be 0"
@@ -76,20 +94,37 @@ class NativeOnlineStreamer:
         dv = lambda t: t.contiguous().to(self.dev)  # noqa: E731
         self.enc_w, self.enc_b = dv(sd["encoder.weight"]), dv(sd["encoder.bias"])
         self.windowed = isinstance(net.layers[0].mhsa, torch.nn.MultiheadAttention)
+        self.mamba = type(net.layers[0].mhsa).__name__ == "Mamba"
+        self.ffn_mamba = type(net.layers[0].tconvffn).__name__ == "Mamba"  # 'mamba(16,4)': a second Mamba block in the T-ConvFFN's place
         self.scope = int(net.attn_scope) if self.windowed else 0
         self.ring = self.scope - 1 + chunk
-        self.decay = None if self.windowed else dv(net.pos.decay.detach().float().exp())
+        self.decay = None if (self.windowed or self.mamba) else dv(net.pos.decay.detach().float().exp())
+
+        def mamba_w(q, ln):
+            """the arguments of nbss_online_mamba_step for the Mamba at state_dict prefix `q` behind the LayerNorm at `ln`, in the call's order"""
+            return [dv(sd[ln + "weight"]), dv(sd[ln + "bias"]), dv(sd[q + "in_proj.weight"].t()), dv(sd[q + "conv1d.weight"][:, 0]), dv(sd[q + "conv1d.bias"]),
+                    dv(sd[q + "x_proj.weight"].t()), dv(sd[q + "dt_proj.weight"]), dv(sd[q + "dt_proj.bias"]), dv(sd[q + "A_log"]), dv(sd[q + "D"]),
+                    dv(sd[q + "out_proj.weight"].t())]
+
         self.layers = []
         for l in range(self.L):
             q = f"layers.{l}."
             tc = q + "tconvffn."
-            att = ({"win_t": dv(sd[q + "mhsa.in_proj_weight"].t()), "bin": dv(sd[q + "mhsa.in_proj_bias"]), "wo_t": dv(sd[q + "mhsa.out_proj.weight"].t()),
-                    "bo": dv(sd[q + "mhsa.out_proj.bias"])} if self.windowed else
-                   {"wq_t": dv(sd[q + "mhsa.q_proj.weight"].t()), "wk_t": dv(sd[q + "mhsa.k_proj.weight"].t()) if (q + "mhsa.k_proj.weight") in sd else None,
-                    "wv_t": dv(sd[q + "mhsa.v_proj.weight"].t()), "wg_t": dv(sd[q + "mhsa.g_proj.weight"].t()), "wo_t": dv(sd[q + "mhsa.out_proj.weight"].t())})
+            if self.mamba:
+                att = {"mamba": mamba_w(q + "mhsa.", q + "norm_mhsa.")}
+            elif self.windowed:
+                att = {"win_t": dv(sd[q + "mhsa.in_proj_weight"].t()), "bin": dv(sd[q + "mhsa.in_proj_bias"]), "wo_t": dv(sd[q + "mhsa.out_proj.weight"].t()),
+                       "bo": dv(sd[q + "mhsa.out_proj.bias"])}
+            else:
+                att = {"wq_t": dv(sd[q + "mhsa.q_proj.weight"].t()), "wk_t": dv(sd[q + "mhsa.k_proj.weight"].t()) if (q + "mhsa.k_proj.weight") in sd else None,
+                       "wv_t": dv(sd[q + "mhsa.v_proj.weight"].t()), "wg_t": dv(sd[q + "mhsa.g_proj.weight"].t()), "wo_t": dv(sd[q + "mhsa.out_proj.weight"].t())}
+            if not self.mamba:
+                att["ln"] = (dv(sd[q + "norm_mhsa.weight"]), dv(sd[q + "norm_mhsa.bias"]))
+            if self.ffn_mamba:
+                self.layers.append({**att, "ffn_mamba": mamba_w(tc, q + "norm_tconvffn.")})
+                continue
             self.layers.append({
                 **att,
-                "ln": (dv(sd[q + "norm_mhsa.weight"]), dv(sd[q + "norm_mhsa.bias"])),
                 "tln": (dv(sd[tc + "0.weight"]), dv(sd[tc + "0.bias"])), "w1_t": dv(sd[tc + "1.weight"][:, :, 0].t()), "b1": dv(sd[tc + "1.bias"]),
                 "c1": (dv(sd[tc + "3.weight"]), dv(sd[tc + "3.bias"])), "c2": (dv(sd[tc + "5.weight"]), dv(sd[tc + "5.bias"])),
                 "gn": (dv(sd[tc + "6.weight"]), dv(sd[tc + "6.bias"])), "c3": (dv(sd[tc + "8.weight"]), dv(sd[tc + "8.bias"])),
@@ -98,9 +133,15 @@ class NativeOnlineStreamer:
         BF, z = batch * self.F, lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)  # noqa: E731
         self.x, self.y = z(batch, self.F, chunk, self.din), z(batch, self.F, chunk, self.dout)
         self.h = [z(batch, self.F, chunk, 96), z(batch, self.F, chunk, 96)]
-        self.a3, self.gn_sums = z(BF, chunk, 192), z(batch + BF, chunk, 8, 2)  # GroupNorm sums [B] + per-frequency partials [B*F] (fixed-order fold)
-        self.state = {"enc": z(BF, 4, self.din), "s": [[z(BF, 2, 192) for _ in range(3)] for _ in range(self.L)]}
-        if self.windowed:  # K / V rings of the last scope - 1 + chunk frames per layer, one device-side frame counter for the stream
+        self.state = {"enc": z(BF, 4, self.din)}
+        if not self.ffn_mamba:
+            self.a3, self.gn_sums = z(BF, chunk, 192), z(batch + BF, chunk, 8, 2)  # GroupNorm sums [B] + per-frequency partials [B*F] (fixed-order fold)
+            self.state["s"] = [[z(BF, 2, 192) for _ in range(3)] for _ in range(self.L)]
+        if self.mamba:  # per Mamba block: the convolution's last three inputs [BF][3][192] and h [BF][16][192] (Mamba.init_state's tensors, transposed)
+            for pre in ("", "ffn_") if self.ffn_mamba else ("",):
+                self.state[pre + "conv"] = [z(BF, 3, 192) for _ in range(self.L)]
+                self.state[pre + "ssm"] = [z(BF, 16, 192) for _ in range(self.L)]
+        elif self.windowed:  # K / V rings of the last scope - 1 + chunk frames per layer, one device-side frame counter for the stream
             self.state["kring"] = [z(BF, self.ring, 96) for _ in range(self.L)]
             self.state["vring"] = [z(BF, self.ring, 96) for _ in range(self.L)]
             self.state["pos"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -111,8 +152,12 @@ class NativeOnlineStreamer:
 
     def _buffers(self):
         out = [self.state["enc"]]
-        out += (self.state["kring"] + self.state["vring"] + [self.state["pos"]]) if self.windowed else (self.state["kv"] + self.state["scale"])
-        for s in self.state["s"]:
+        if self.mamba:
+            for pre in ("", "ffn_") if self.ffn_mamba else ("",):
+                out += self.state[pre + "conv"] + self.state[pre + "ssm"]
+        else:
+            out += (self.state["kring"] + self.state["vring"] + [self.state["pos"]]) if self.windowed else (self.state["kv"] + self.state["scale"])
+        for s in self.state.get("s", ()):
             out += s
         return out
 
@@ -122,7 +167,8 @@ class NativeOnlineStreamer:
             b.zero_()
 
     def _run(self) -> None:
-        """one step: reads self.x, writes self.y, updates every state buffer in place (a fixed sequence of 6 L + 2 C-ABI calls)"""
+        """one step: reads self.x, writes self.y, updates every state buffer in place (a fixed sequence of 5 L + 2 C-ABI calls: encoder, per layer
+        fconv, full, fconv, the attention / retention / Mamba step, then the T-ConvFFN step or — 'mamba(16,4)' — a second Mamba step, and the decoder)"""
         lib, cfg, P = self.lib, C.byref(self.cfg), ops._ptr
         st = ops._stream(lib, self.x)
         BF, Cc = self.B * self.F, self.C
@@ -133,16 +179,21 @@ class NativeOnlineStreamer:
             lib.call("nbss_fconv_fwd", cfg, f(self.flat), P(lib, self.packed), l, 0, f(a), f(b), st)
             lib.call("nbss_full_fwd", cfg, f(self.flat), P(lib, self.packed), l, f(b), f(a), st)
             lib.call("nbss_fconv_fwd", cfg, f(self.flat), P(lib, self.packed), l, 1, f(a), f(b), st)
-            if self.windowed:
+            if self.mamba:
+                lib.call("nbss_online_mamba_step", BF, Cc, *map(f, w["mamba"]), f(self.state["conv"][l]), f(self.state["ssm"][l]), f(b), st)
+            elif self.windowed:
                 lib.call("nbss_online_mhsa_step", BF, Cc, self.scope, self.ring, f(w["ln"][0]), f(w["ln"][1]), f(w["win_t"]), f(w["bin"]), f(w["wo_t"]), f(w["bo"]),
                          f(self.state["kring"][l]), f(self.state["vring"][l]), P(lib, self.state["pos"], torch.int32), f(b), st)
             else:
                 lib.call("nbss_online_ret_step", BF, Cc, f(w["ln"][0]), f(w["ln"][1]), f(w["wq_t"]), f(w["wk_t"]) if w["wk_t"] is not None else None, f(w["wv_t"]),
                          f(w["wg_t"]), f(w["wo_t"]), f(self.decay), f(self.state["kv"][l]), f(self.state["scale"][l]), f(b), st)
-            s1, s2, s3 = self.state["s"][l]
-            lib.call("nbss_online_tconvffn_step", self.B, self.F, Cc, f(w["tln"][0]), f(w["tln"][1]), f(w["w1_t"]), f(w["b1"]), f(w["c1"][0]), f(w["c1"][1]),
-                     f(w["c2"][0]), f(w["c2"][1]), f(w["gn"][0]), f(w["gn"][1]), f(w["c3"][0]), f(w["c3"][1]), f(w["w2_t"]), f(w["b2"]), f(s1), f(s2), f(s3),
-                     f(self.a3), f(self.gn_sums), f(b), st)
+            if self.ffn_mamba:
+                lib.call("nbss_online_mamba_step", BF, Cc, *map(f, w["ffn_mamba"]), f(self.state["ffn_conv"][l]), f(self.state["ffn_ssm"][l]), f(b), st)
+            else:
+                s1, s2, s3 = self.state["s"][l]
+                lib.call("nbss_online_tconvffn_step", self.B, self.F, Cc, f(w["tln"][0]), f(w["tln"][1]), f(w["w1_t"]), f(w["b1"]), f(w["c1"][0]), f(w["c1"][1]),
+                         f(w["c2"][0]), f(w["c2"][1]), f(w["gn"][0]), f(w["gn"][1]), f(w["c3"][0]), f(w["c3"][1]), f(w["w2_t"]), f(w["b2"]), f(s1), f(s2), f(s3),
+                         f(self.a3), f(self.gn_sums), f(b), st)
             a, b = b, a
         if self.windowed:
             lib.call("nbss_online_advance", P(lib, self.state["pos"], torch.int32), Cc, st)

@@ -11,9 +11,12 @@ and, to say which end is the slow one and how it compares with the network's own
 entry point (time / inner per call: kernel time plus the gap to the next launch of the same graph, no graph-launch floor):
   stft, istft, encdec (nbss_online_encoder_step + nbss_decoder_fwd).
 Every (attention) run is a child process of its own under a time limit; the parent never opens the device and stops at the first child that fails.
-usage: python tools/online_wave_bench.py [--chunks 2,4,8,16,32] [--attentions "ret(2),mhsa(251)"] [--rounds 9] [--replays 200] [--json out.json]"""
+usage: python tools/online_wave_bench.py [--chunks 2,4,8,16,32] [--attentions "ret(2),mhsa(251)"] [--rounds 9] [--replays 200] [--json out.json]
+('mamba(16,4)' and 'mamba(16,4,not_replace_ffn)' are accepted as attentions: the child sets NBSS_ONLINE_MAMBA=1 and NBSS_ONLINE_NATIVE_MAMBA_STEP=1 itself)"""
 import argparse
 import json
+import os
+import re
 import statistics
 import subprocess
 import sys
@@ -68,6 +71,8 @@ def point(attention, chunks, rounds, replays, inner):
     from nbss_amd.online_io import NativeWaveStreamer
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if attention.startswith("mamba"):  # the variant's own switch and that of its native step (both opt-in)
+        os.environ["NBSS_ONLINE_MAMBA"] = os.environ["NBSS_ONLINE_NATIVE_MAMBA_STEP"] = "1"
     net = OnlineSpatialNet(dim_input=12, dim_output=4, num_layers=8, dim_squeeze=8, num_freqs=129, encoder_kernel_size=5, dim_hidden=96, dim_ffn=192,
                            num_heads=4, dropout=(0, 0, 0), kernel_size=(5, 3), conv_groups=(8, 8), norms=["LN", "LN", "GN", "LN", "LN", "LN"], full_share=0,
                            attention=attention, decay=[4, 5, 9, 10], rope=False).eval().to(dev)
@@ -132,7 +137,7 @@ def main():
         point(a.point, chunks, a.rounds, a.replays, a.inner)
         return 0
     rows = []
-    for att in a.attentions.split(","):
+    for att in re.split(r",(?![^(]*\))", a.attentions):  # commas outside parentheses: "ret(2),mamba(16,4)" names two
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--point", att, "--chunks", a.chunks, "--rounds", str(a.rounds),
                "--replays", str(a.replays), "--inner", str(a.inner)]
         r = subprocess.run(cmd, capture_output=True, text=True)
