@@ -369,10 +369,45 @@ class OnlineSpatialNet(nn.Module):
         return F.linear(o, mha.out_proj.weight, mha.out_proj.bias)
 
 
-class OnlineStreamer:
+class GraphedStep:
+    """What the streamers share (OnlineStreamer below, nbss_amd.online.NativeOnlineStreamer, nbss_amd.online_io.NativeWaveStreamer): a step is a static
+    kernel sequence over pre-allocated buffers; on a HIP device it is captured once into a HIP graph (torch.cuda.CUDAGraph) and replayed.  A subclass
+    provides `_run()` (one step, state updated in place), `_buffers()` (every state tensor `_run` advances), `dev` and `use_graph`."""
+
+    graph = None
+
+    def _capture(self) -> None:
+        saved = [b.clone() for b in self._buffers()]
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):  # warm-up outside the capture: code-object loads, LDS attribute calls
+                self._run()
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()  # a HIP graph on ROCm
+        with torch.cuda.graph(self.graph):
+            self._run()
+        for b, s0 in zip(self._buffers(), saved):  # warm-up and capture advanced the state: rewind
+            b.copy_(s0)
+
+    def _replay(self) -> None:
+        """one step: the graph (captured on first use) where `use_graph`, else the launches themselves"""
+        if not self.use_graph:
+            return self._run()
+        if self.graph is None:
+            self._capture()
+        self.graph.replay()
+
+    @torch.no_grad()
+    def reset(self) -> None:
+        """back to the empty state (a new utterance); the captured graph stays valid: it only refers to the buffers"""
+        for b in self._buffers():
+            b.zero_()
+
+
+class OnlineStreamer(GraphedStep):
     """Fixed-shape streaming step of an OnlineSpatialNet ('mhsa(N)' with finite N, 'ret(..)' without rotary positions, or 'mamba(..)'): every call
-    consumes `chunk` frames.  The whole state lives in pre-allocated device buffers that a step updates in place, so a step is a
-    static kernel sequence; on a HIP device it is captured once into a HIP graph (torch.cuda.CUDAGraph) and replayed — BASELINE
+    consumes `chunk` frames.  The whole state lives in pre-allocated device buffers that a step updates in place (GraphedStep) — BASELINE
     config 5's "causal chunked inference with hipGraph-captured steps"."""
 
     def __init__(self, net: OnlineSpatialNet, batch: int, chunk: int, device=None, use_graph: Optional[bool] = None):
@@ -385,7 +420,6 @@ class OnlineStreamer:
         self.x = torch.zeros(batch, self.Fq, chunk, self.din, device=self.dev)
         self.y = torch.zeros(batch, self.Fq, chunk, net.decoder.out_features, device=self.dev)
         self.state = net.init_stream(batch, device=self.dev)
-        self.graph = None
 
     def _buffers(self):
         out = list(self.state["conv"].values())
@@ -405,33 +439,8 @@ class OnlineStreamer:
                 buf[k2].copy_(new[k2])
         self.y.copy_(y)
 
-    def _capture(self) -> None:
-        saved = [b.clone() for b in self._buffers()]
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._run()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._run()
-        for b, s0 in zip(self._buffers(), saved):  # warm-up and capture advanced the state: rewind
-            b.copy_(s0)
-
-    @torch.no_grad()
-    def reset(self) -> None:
-        """back to the empty state (a new utterance); the captured graph stays valid: it only refers to the buffers"""
-        for b in self._buffers():
-            b.zero_()
-
     @torch.no_grad()
     def step(self, x_chunk: Tensor) -> Tensor:
         self.x.copy_(x_chunk)
-        if self.use_graph:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
-        else:
-            self._run()
+        self._replay()
         return self.y.clone()

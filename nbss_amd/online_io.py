@@ -184,12 +184,7 @@ class NativeWaveStreamer(NativeOnlineStreamer, _WaveIO):
 
     def _step(self, xs: Tensor) -> Tensor:
         self.xw.copy_(xs)
-        if self.use_graph:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
-        else:
-            self._run()
+        self._replay()
         return self.yw.clone()
 
     def step(self, x_chunk: Tensor) -> Tensor:

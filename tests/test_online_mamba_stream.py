@@ -72,8 +72,11 @@ def test_native_streaming_step_matches_module(monkeypatch, backend, attention, c
         st = net.init_stream(2, device=backend.device)
         ys = torch.cat([net.forward_stream(x[:, :, c:c + chunk], st) for c in range(0, T, chunk)], 2)
     s = NativeOnlineStreamer(net, 2, chunk, device=backend.device, lib=backend.lib, use_graph=backend.name == "hip")
-    assert s.mamba and s.ffn_mamba == ("not_replace_ffn" not in attention)
-    assert ("s" in s.state) == (not s.ffn_mamba) and hasattr(s, "a3") == (not s.ffn_mamba)  # no T-ConvFFN buffers behind a replaced FFN
+    from nbss_amd.online import MAMBA, TCONVFFN
+    ffn_mamba = "not_replace_ffn" not in attention
+    assert s.kinds == (MAMBA, MAMBA if ffn_mamba else TCONVFFN) and all([k for k, _, _ in steps] == list(s.kinds) for steps in s.steps)
+    assert ("ffn_s1" in s.state) == (not ffn_mamba) and ("a3" in s.shared) == ("gn_sums" in s.shared) == (not ffn_mamba)  # no T-ConvFFN buffers behind a replaced FFN
+    assert ("ffn_conv" in s.state) == ("ffn_ssm" in s.state) == ffn_mamba and not hasattr(s, "a3")
     yn = torch.cat([s.step(x[:, :, c:c + chunk]) for c in range(0, T, chunk)], 2)
     e = (rel_l2(yn, ys), rel_l2(yn, y))
     print(f"{backend.name} {attention} chunk {chunk}: vs forward_stream {e[0]:.2e}, vs forward {e[1]:.2e}")
