@@ -296,8 +296,25 @@ def test_training_blocks_random_shapes(emu_lib):
         (o * do.double()).sum().backward()
         assert rel_l2(dqkv, q64.grad) < 5e-5, (nseq, T, dh, heads)
 
+    @settings(max_examples=15, deadline=None)
+    @given(rows=st.integers(1, 70), Cc=st.sampled_from([8, 40, 96, 192, 384]), seed=st.integers(0, 99))
+    def ln(rows, Cc, seed):
+        g = torch.Generator().manual_seed(seed)
+        x = torch.randn(rows, Cc, generator=g) * 2 + 0.5
+        gam = torch.rand(Cc, generator=g) + 0.5
+        dy, dres = torch.randn(rows, Cc, generator=g), torch.randn(rows, Cc, generator=g)
+        x64, g64 = x.double().requires_grad_(True), gam.double().requires_grad_(True)
+        b64 = torch.zeros(Cc, dtype=torch.float64, requires_grad=True)
+        (Fn.layer_norm(x64, (Cc,), g64, b64, 1e-5) * dy.double()).sum().backward()
+        var, mean = torch.var_mean(x.double(), dim=-1, unbiased=False)
+        stats = torch.stack([mean, torch.rsqrt(var + 1e-5)], dim=-1).float().contiguous()
+        dx, dg, dbt = torch.full((rows, Cc), float("nan")), torch.zeros(Cc), torch.zeros(Cc)
+        lib.call("nbss_nb_layernorm_bwd", NBSS_F32, rows, Cc, P(x), P(stats), P(gam), P(dy), P(dres), P(dx), P(dg), P(dbt), None)
+        assert rel_l2(dx, x64.grad + dres.double()) < 5e-5 and rel_l2(dg, g64.grad) < 5e-5 and rel_l2(dbt, b64.grad) < 5e-5, (rows, Cc)
+
     conv()
     gbn()
+    ln()
     attn()
 
 
