@@ -28,6 +28,50 @@ def max_abs(a, b):
     return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
 
 
+def _sliced_sums(t, dims, blocks):
+    """sum of t over every axis not in dims, the kept axes cut into blocks of blocks[axis] entries (a ragged last block) -> sums, element counts"""
+    t = _t(t)
+    dims = tuple(d % t.dim() for d in dims)
+    drop = [d for d in range(t.dim()) if d not in dims]
+    s = t.sum(dim=drop) if drop else t.clone()
+    n = torch.full_like(s, float(t.numel() // max(s.numel(), 1)))
+    blocks = {d % t.dim(): b for d, b in (blocks or {}).items()}
+    for i, d in enumerate(sorted(dims)):
+        blk = blocks.get(d, 1)
+        if blk > 1:
+            idx = torch.arange(s.shape[i]) // blk
+            shape = list(s.shape)
+            shape[i] = int(idx[-1]) + 1
+            s = torch.zeros(shape, dtype=s.dtype).index_add_(i, idx, s)
+            n = torch.zeros(shape, dtype=n.dtype).index_add_(i, idx, n)
+    return s, n
+
+
+SLICE_MIN = 64  # fewer elements than this is a sample, not a slice: its rms fluctuates by more than 1 / sqrt(2 x 64) = 9 %
+
+
+def sliced_err(got, want, dims, blocks=None):
+    """the error of `got` (a kernel's tensor) against `want` (the fp64 oracle's) slice by slice: the axes `dims` are kept — `blocks` {axis: n} cuts a kept
+    axis into blocks of n entries, the last one ragged — and every other axis is reduced.  Per slice s: rms(got - want over s) / max(rms(want over s),
+    rms(want over everything)), so a slice that is legitimately near zero does not divide by nothing and a slice larger than the average is judged against
+    itself.  fp64 on the host.  A slice holds at least SLICE_MIN elements (asserted: the caller coarsens `blocks`)."""
+    got, want = _t(got), _t(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    e2, n = _sliced_sums((got - want) ** 2, dims, blocks)
+    w2, _ = _sliced_sums(want ** 2, dims, blocks)
+    assert float(n.min()) >= SLICE_MIN, f"slices of {int(n.min())} elements: coarsen (shape {tuple(want.shape)}, dims {dims}, blocks {blocks})"
+    whole = (want ** 2).mean()
+    return torch.sqrt(e2 / n) / torch.sqrt(torch.maximum(w2 / n, whole)).clamp_min(1e-300)
+
+
+def worst_slice(got, want, dims, blocks=None):
+    """-> (index tuple along the kept axes, in blocks; value) of the largest sliced_err"""
+    err = sliced_err(got, want, dims, blocks)
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)  # a NaN from the kernel is the worst slice, not an ignored one
+    i = int(err.argmax())
+    return tuple(int(v) for v in torch.unravel_index(torch.tensor(i), err.shape)) if err.dim() else (), float(err.reshape(-1)[i])
+
+
 # ---- the native blocks inside models.arch.OnlineSpatialNet (tests/test_online_*_train_module.py) ---------------------------------------------------------
 ONLINE_SWITCHES = ("NBSS_ONLINE_NATIVE_XBAND", "NBSS_ONLINE_NATIVE_TRAIN", "NBSS_ONLINE_NATIVE_RET")
 
