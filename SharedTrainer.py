@@ -692,7 +692,8 @@ def evaluate(cfg: dict, stage: int) -> Dict[str, Any]:
     """`validate` (stage 1) / `test` (stage 2): the configured uPIT loss (neg-SI-SDR as shipped) of the separated signals and its improvement over the
     unprocessed reference-channel mixture, through the forward-only path (SharedTrainer.py:151-205 without the PESQ/STOI pools).  `validate` adds
     val/sdr, val/neg_si_sdr (when the loss is another one) and val/metric (`val_metric`); `test` recovers the scale of a scale-invariant model's
-    estimates and adds test/<m>, test/input_<m>, test/<m>_i for the metrics of `model.metrics` that the device pass serves (SDR, SI_SDR, SI_SNR, SNR),
+    estimates and adds test/<m>, test/input_<m>, test/<m>_i for the metrics of `model.metrics` that the device pass serves (SDR, SI_SDR, SI_SNR, SNR;
+    with NBSS_NATIVE_STOI=1 also STOI and ESTOI: models/utils/metrics.py),
     and writes one row per utterance to <trainer.default_root_dir>/test_results.json (reference :221-273)."""
     if not _is_fused_arch(cfg):
         return _evaluate_generic(cfg, stage)

@@ -235,6 +235,36 @@ int nbss_sdr(int B, int S, int N, int filter_length, int flags, const float* pre
 int64_t nbss_recover_scale_ws_bytes(int B, int S);
 int nbss_recover_scale(int B, int S, int N, int flags, const float* preds, const float* mixture, float* out, void* ws, void* stream);
 
+/* ---- STOI and extended STOI (csrc/stoi.hip) --------------------------------------------------------------------------------------------------
+ * Short-time objective intelligibility (Taal et al., 2011) and extended STOI (Jensen & Taal, 2016), what the reference's test step takes from
+ * torchmetrics -> pystoi (a package this port does not use; parity with it is not pinned, this comment is the definition).
+ * Per pair (estimate y, clean x), both of N samples at rate fs.  EPS = 2^-52.
+ * 1. Resample to 10 kHz.  fs in {8000, 10000, 16000} (NBSS_EUNSUPPORTED otherwise); p/q = 5/4 for 8000, 5/8 for 16000, none for 10000.
+ *    Taps: fc = 1 / (2 max(p, q)), L = ceil((60 - 8) / (28.714 fc / 10)), t = -L .. L,
+ *    h = kaiser(2 L + 1, beta = 0.1102 (60 - 8.7)) 2 p fc sinc(2 fc t), then h <- p h / sum(h): 365 taps for 5/4, 581 for 5/8.
+ *    Output sample m = sum_k h[m q - k p + L] x[k], zeros outside the signal; ceil(N p / q) output samples
+ *    (scipy.signal.resample_poly(x, p, q, window=h / p)).
+ * 2. Silent-frame removal.  w = hanning(258)[1:-1]; frames of 256 samples starting at 0, 128, ... < len - 256 (the last candidate start is excluded
+ *    when len - 256 is a multiple of 128).  E_k = 20 log10(|w x_k| + EPS) of clean frame k; frame k is kept iff E_k > max_k E - 40.  The windowed
+ *    kept frames of x are overlap-added at hop 128, in order; the frames of y use the same mask, from x alone.  K kept frames leave signals of
+ *    128 (K - 1) + 256 samples.
+ * 3. Spectra.  Frames of the compacted signals: 256 samples at hop 128, starts < len - 256 again: K - 1 frames.  Each is multiplied by w, then a
+ *    real DFT of 512 points (zero-padded) gives 257 bins.
+ * 4. One-third-octave bands.  15 bands, centres 150 2^(k/3), edges 150 2^((2 k -+ 1) / 6); bin grid f_j = j 10000 / 512.  Band k sums |X_j|^2 over
+ *    j in [argmin_j (f_j - low_k)^2, argmin_j (f_j - high_k)^2); the band value is the square root of that sum: X, Y [15, K - 1].
+ * 5. Segments.  All runs of 30 consecutive frames: M = K - 30 segments.  If K - 1 < 30 the result is 1e-5 and the call does not fail.
+ * 6. STOI (flag clear).  Per segment and band: alpha = |X| / (|Y| + EPS), norms over the 30 frames; Y' = min(alpha Y, X (1 + 10^(15/20)));
+ *    d = <X - mean(X), Y' - mean(Y')> / ((|X - mean(X)| + EPS) (|Y' - mean(Y')| + EPS)).  The result is the mean of d over segments and bands.
+ * 7. eSTOI (NBSS_STOI_EXTENDED).  Per segment, each band row of X and Y has its mean over time subtracted and is divided by (its norm + EPS); each
+ *    frame column then has its mean over bands subtracted and is divided by (its norm + EPS).  The result is sum(X~ Y~) / (30 M).
+ * preds / target [B,S,N] fp32, estimate s paired with target s -> out [B][S] fp32.  S <= 4, B <= 1024, N <= 2^24 and at least 257 resampled samples,
+ * else NBSS_EUNSUPPORTED.  The resampler accumulates in fp64, the spectra are fp32 (matrix cores), steps 2 and 5 - 7 are fp64.  No atomics, every
+ * element of out is written once, two calls give the same bits, an item's value does not depend on the other items of the batch.
+ * ws: nbss_stoi_ws_bytes() bytes (negative: the error code); its first 2 L + 1 doubles hold the taps h after the call. */
+#define NBSS_STOI_EXTENDED 1
+int64_t nbss_stoi_ws_bytes(int B, int S, int N, int fs);
+int nbss_stoi(int B, int S, int N, int fs, int flags, const float* preds, const float* target, float* out /*[B][S]*/, void* ws, void* stream);
+
 /* ---- Room impulse responses by the image-source method (csrc/rir.hip; nbss_amd/rir.py: simulate_rir) -----------------------------------------
  * What the reference's generate_rirs.py takes from gpuRIR (a CUDA-only package; parity with it is not pinned, this comment is the definition):
  * Allen & Berkley's image sources of a shoebox room with the Hann-windowed sinc of fractional delay.  Per room b of the batch:

@@ -2,8 +2,13 @@
 SDR, SI_SDR, SI_SNR and SNR — what the reference's device pass computes through torchmetrics — run on the MI355X kernels (nbss_amd/csrc/metrics.hip:
 nbss_sdr, nbss_signal_ratios, nbss_recover_scale) for tensors on a HIP device and through the same closed forms in torch for host tensors (fp64 for SDR
 and for the scales), as models/io/loss.py does for the CPU accelerator.  NB_PESQ, WB_PESQ, STOI, ESTOI, DNSMOS and pDNSMOS need the packages pesq, pystoi
-and onnxruntime, which are not ported: the device pass (`device_only='gpu'`) skips them, every other pass raises NotImplementedError naming the package."""
+and onnxruntime, which are not ported: the device pass (`device_only='gpu'`) skips them, every other pass raises NotImplementedError naming the package.
+
+Opt-in: NBSS_NATIVE_STOI=1 (read on every call, on only for exactly '1') serves STOI and ESTOI natively, as include/nbss_hip.h defines them
+(nbss_amd/csrc/stoi.hip: nbss_stoi on a HIP device, the same definition in fp64 numpy / scipy on the host), under the reference's keys, in the
+None, 'gpu' and 'cpu' passes.  pystoi was never run against it: parity with pystoi is not pinned, which is why the switch is off by default."""
 import math
+import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -14,13 +19,19 @@ NATIVE_METRICS = ('SDR', 'SI_SDR', 'SI_SNR', 'SNR')
 _PACKAGE = {'NB_PESQ': 'pesq', 'WB_PESQ': 'pesq', 'STOI': 'pystoi', 'ESTOI': 'pystoi', 'DNSMOS': 'onnxruntime', 'PDNSMOS': 'onnxruntime'}
 _RATIO_COLUMN = {'SNR': 0, 'SI_SDR': 1, 'SI_SNR': 2}  # nbss_signal_ratios: out[..., 3]
 SDR_FILTER_LENGTH = 512  # torchmetrics' default
+STOI_METRICS = ('STOI', 'ESTOI')
+STOI_RATIO = {8000: (5, 4), 16000: (5, 8), 10000: (1, 1)}  # p / q to 10 kHz
+
+
+def native_stoi_enabled() -> bool:
+    return os.environ.get('NBSS_NATIVE_STOI') == '1'
 
 
 def get_metric_list_on_device(device: Optional[str]):
     """the metrics a pass with `device_only=device` evaluates (metrics.py:17-23, without the ones that are not ported on the device pass)"""
     return {None: ['SDR', 'SI_SDR', 'SNR', 'SI_SNR', 'NB_PESQ', 'WB_PESQ', 'STOI', 'ESTOI', 'DNSMOS', 'PDNSMOS'],
             'cpu': ['NB_PESQ', 'WB_PESQ', 'STOI', 'ESTOI'],
-            'gpu': ['SDR', 'SI_SDR', 'SNR', 'SI_SNR']}[device]
+            'gpu': ['SDR', 'SI_SDR', 'SNR', 'SI_SNR'] + (list(STOI_METRICS) if native_stoi_enabled() else [])}[device]
 
 
 # ---- host closed forms (torchmetrics restated) ------------------------------------------------------------------------------------------------------
@@ -92,6 +103,92 @@ def native_metrics(preds: Tensor, target: Tensor, names) -> Dict[str, Tensor]:
     return out
 
 
+# ---- STOI / eSTOI: the definition of include/nbss_hip.h in fp64 (host) ------------------------------------------------------------------------------
+def _stoi_taps(p: int, q: int):
+    import numpy as np
+    fc = 1.0 / (2 * max(p, q))
+    L = int(math.ceil((60 - 8) / (28.714 * fc / 10)))
+    h = np.kaiser(2 * L + 1, 0.1102 * (60 - 8.7)) * 2 * p * fc * np.sinc(2 * fc * np.arange(-L, L + 1))
+    return p * h / h.sum(), L
+
+
+def _stoi_resample(x, p: int, q: int):
+    """out[m] = sum_k h[m q - k p + L] x[k], m < ceil(N p / q): the zero-stuffed signal through h, every q-th sample from L on"""
+    import numpy as np
+    if p == q:
+        return x
+    h, L = _stoi_taps(p, q)
+    up = np.zeros(len(x) * p + 2 * L)
+    up[:len(x) * p:p] = x
+    return np.convolve(up, h)[L + q * np.arange(-(-len(x) * p // q))]
+
+
+def _stoi_frames(x):
+    import numpy as np
+    n = max(-(-(len(x) - 256) // 128), 0)  # starts 0, 128, ... < len - 256
+    return x[128 * np.arange(n)[:, None] + np.arange(256)[None, :]]
+
+
+def _host_stoi(x, y, fs: int, extended: bool) -> float:
+    """one pair in fp64 numpy: clean x, estimate y"""
+    import numpy as np
+    eps = 2.0 ** -52
+    p, q = STOI_RATIO[fs]
+    x, y = _stoi_resample(np.asarray(x, np.float64), p, q), _stoi_resample(np.asarray(y, np.float64), p, q)
+    if len(x) < 257:
+        raise ValueError(f"STOI needs at least 257 samples at 10 kHz, got {len(x)}")
+    w = np.hanning(258)[1:-1]
+    xf, yf = _stoi_frames(x) * w, _stoi_frames(y) * w
+    energy = 20 * np.log10(np.sqrt((xf * xf).sum(1)) + eps)
+    keep = energy > energy.max() - 40
+    xf, yf = xf[keep], yf[keep]
+    K = len(xf)
+    if K - 1 < 30:
+        return 1e-5
+    xs, ys = np.zeros(128 * (K + 1)), np.zeros(128 * (K + 1))
+    for half in (0, 1):  # overlap-add at hop 128: the first halves of the frames, then the second halves one hop later
+        xs[128 * half:128 * (K + half)] += xf[:, 128 * half:128 * (half + 1)].reshape(-1)
+        ys[128 * half:128 * (K + half)] += yf[:, 128 * half:128 * (half + 1)].reshape(-1)
+    f = np.arange(257) * (10000 / 512)
+    sel = np.zeros((15, 257))
+    for k in range(15):
+        sel[k, np.argmin((f - 150 * 2 ** ((2 * k - 1) / 6)) ** 2):np.argmin((f - 150 * 2 ** ((2 * k + 1) / 6)) ** 2)] = 1
+    X = np.sqrt(sel @ (np.abs(np.fft.rfft(_stoi_frames(xs) * w, 512, axis=1)) ** 2).T)
+    Y = np.sqrt(sel @ (np.abs(np.fft.rfft(_stoi_frames(ys) * w, 512, axis=1)) ** 2).T)
+    M = X.shape[1] - 29
+    idx = np.arange(M)[:, None] + np.arange(30)[None, :]
+    Xs, Ys = X[:, idx].transpose(1, 0, 2), Y[:, idx].transpose(1, 0, 2)  # [M, 15, 30]
+    if extended:
+        def normed(a):
+            a = a - a.mean(2, keepdims=True)
+            a = a / (np.sqrt((a * a).sum(2, keepdims=True)) + eps)
+            a = a - a.mean(1, keepdims=True)
+            return a / (np.sqrt((a * a).sum(1, keepdims=True)) + eps)
+        return float((normed(Xs) * normed(Ys)).sum() / (30 * M))
+    alpha = np.sqrt((Xs * Xs).sum(2, keepdims=True)) / (np.sqrt((Ys * Ys).sum(2, keepdims=True)) + eps)
+    Yp = np.minimum(alpha * Ys, Xs * (1 + 10 ** (15 / 20)))
+    xc, yc = Xs - Xs.mean(2, keepdims=True), Yp - Yp.mean(2, keepdims=True)
+    return float(((xc * yc).sum(2) / ((np.sqrt((xc * xc).sum(2)) + eps) * (np.sqrt((yc * yc).sum(2)) + eps))).mean())
+
+
+def native_stoi(preds: Tensor, target: Tensor, fs: int, extended: bool) -> Tensor:
+    """STOI (extended: eSTOI) as include/nbss_hip.h defines it: preds / target [..., N] at fs Hz -> fp32 [...]: one nbss_stoi call per 1024 items on a
+    HIP device, the fp64 closed form on the host.  Parity with pystoi is not pinned."""
+    if preds.shape != target.shape or preds.dim() < 1:
+        raise ValueError(f"metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} must have the same shape [..., time]")
+    if int(fs) not in STOI_RATIO:
+        raise ValueError(f"STOI: the sampling rate must be one of {sorted(STOI_RATIO)}, got {fs}")
+    lead, N = preds.shape[:-1], preds.shape[-1]
+    p, t = preds.detach().reshape(-1, 1, N), target.detach().reshape(-1, 1, N)
+    if p.is_cuda:
+        from nbss_amd import ops
+        from nbss_amd._lib import hip
+        p, t = p.float().contiguous(), t.float().contiguous()
+        return torch.cat([ops.stoi(hip(), p[i:i + 1024], t[i:i + 1024], int(fs), extended) for i in range(0, p.shape[0], 1024)]).reshape(lead)
+    pn, tn = p[:, 0].double().numpy(), t[:, 0].double().numpy()
+    return torch.tensor([_host_stoi(tn[i], pn[i], int(fs), extended) for i in range(pn.shape[0])], dtype=torch.float32).reshape(lead)
+
+
 def pit_reorder(yr_hat: Tensor, perm: Optional[Tensor]) -> Tensor:
     """the estimates in the order of the targets they were paired with (perm [B,S]: estimate paired with target s; torchmetrics pit_permutate)"""
     if perm is None:
@@ -125,20 +222,33 @@ def cal_metrics_functional(metric_list: List[str], preds: Tensor, target: Tensor
     for m in metric_list:
         if m.upper() not in NATIVE_METRICS and m.upper() not in _PACKAGE:
             raise ValueError('Unkown audio metric ' + m)
+        if m.upper() in STOI_METRICS and native_stoi_enabled():
+            served.append(m)  # in every pass: the 'cpu' pass evaluates them on host tensors
+            continue
         if m.upper() in _PACKAGE:
             if device_only == 'gpu':
                 continue  # the device pass leaves them to the host pass, as the reference's does
             if m.upper() == 'WB_PESQ' and fs == 8000:
                 continue  # there is narrow band (nb) mode only when the sampling rate is 8000 Hz
             raise NotImplementedError(f"{m} needs the package {_PACKAGE[m.upper()]}, which this port does not use: SDR, SI_SDR, SI_SNR and SNR are "
-                                      "computed natively (device_only='gpu' skips the rest)")
+                                      "computed natively (device_only='gpu' skips the rest)"
+                                      + ("; NBSS_NATIVE_STOI=1 serves STOI and ESTOI by this port's own definition (include/nbss_hip.h), whose parity with "
+                                         "pystoi is not pinned" if m.upper() in STOI_METRICS else ""))
         if m.upper() not in get_metric_list_on_device(device_only):
             continue  # the host pass leaves the native ones to the device pass
         served.append(m)
     if not served:
         return metrics, input_metrics, imp_metrics
-    vals = native_metrics(preds, target, served)
-    in_vals = native_metrics(original, target, served) if original is not None else None
+    def evaluate(p: Tensor) -> Dict[str, Tensor]:
+        out = native_metrics(p, target, [m for m in served if m.upper() in NATIVE_METRICS])
+        for m in served:
+            if m.upper() in STOI_METRICS:
+                on_host = device_only == 'cpu'
+                out[m.upper()] = native_stoi(p.cpu() if on_host else p, target.cpu() if on_host else target, fs, m.upper() == 'ESTOI')
+        return out
+
+    vals = evaluate(preds)
+    in_vals = evaluate(original) if original is not None else None
     for m in served:
         mname = m.lower() + suffix
         v = vals[m.upper()].double().cpu()

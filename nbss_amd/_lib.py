@@ -16,6 +16,7 @@ NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR, NBSS_LOSS_SA_SDR, NBSS_LOSS_MSE = 0, 1, 2, 3
 NBSS_LOSS_PIT, NBSS_LOSS_SCALE_INVARIANT = 1, 2
 # nbss_sdr / nbss_recover_scale: flags
 NBSS_SDR_ZERO_MEAN = 1
+NBSS_STOI_EXTENDED = 1
 NBSS_SCALE_TOGETHER, NBSS_SCALE_NORM_IF_EXCEED_1 = 1, 2
 # nbss_online_stft_step / nbss_online_istft_step: norm
 NBSS_ONLINE_NORM_NONE, NBSS_ONLINE_NORM_FREQUENCY, NBSS_ONLINE_NORM_UTTERANCE = 0, 1, 2
@@ -89,6 +90,8 @@ SIGNATURES = {
     "nbss_sdr": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nbss_recover_scale_ws_bytes": (C.c_int64, [_I, _I]),
     "nbss_recover_scale": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "nbss_stoi_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),
+    "nbss_stoi": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nbss_rir_ism_ws_bytes": (C.c_int64, [_I, _P]),
     "nbss_rir_ism": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "nbss_rir_tail": (_I, [_I, _I, _I, _I, C.c_double, C.c_double, _I, _P, C.c_int64, _P, _P]),

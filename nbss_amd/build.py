@@ -44,6 +44,8 @@ PER_FILE_FLAGS["tailw"] = _SCHED("max-ilp")
 PER_FILE_FLAGS["metrics"] = ["-fno-fast-math"]
 # rir.hip splits a delay of up to 65 536 samples into integer and fraction in fp64 and is held to a few fp32 ulp per image: accurate sinf / cosf, no reassociation
 PER_FILE_FLAGS["rir"] = ["-fno-fast-math"]
+# stoi.hip: a keep-or-drop threshold on fp64 frame energies and fp64 correlation statistics held against an fp64 restatement
+PER_FILE_FLAGS["stoi"] = ["-fno-fast-math"]
 
 
 def _sources():

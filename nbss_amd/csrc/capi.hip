@@ -45,6 +45,8 @@ size_t sdr_ws_bytes_impl(int B, int S, int N, int L);
 int sdr_impl(int B, int S, int N, int L, int flags, const float* p, const float* t, float* sdr, void* ws, hipStream_t st);
 size_t recover_scale_ws_bytes_impl(int B, int S);
 int recover_scale_impl(int B, int S, int N, int flags, const float* p, const float* x, float* out, void* ws, hipStream_t st);
+int64_t stoi_ws_bytes_impl(int B, int S, int N, int fs);
+int stoi_impl(int B, int S, int N, int fs, int flags, const float* preds, const float* target, float* out, void* ws, hipStream_t st);
 int64_t rir_ism_ws_bytes_impl(int B, const int32_t* nb_img);
 int rir_ism_impl(int B, int S, int M, int n_samples, double fs, double c, double tw, const int32_t* k_d, bool broadcast, const double* room_sz,
                  const double* beta, const double* pos_src, const double* pos_rcv, const int32_t* nb_img, float* h, void* ws, int64_t ws_bytes, hipStream_t st);
@@ -508,6 +510,13 @@ int64_t nbss_recover_scale_ws_bytes(int B, int S) {
 int nbss_recover_scale(int B, int S, int N, int flags, const float* preds, const float* mixture, float* out, void* ws, void* stream) {
     if (!preds || !mixture || !out || !ws) return NBSS_EINVAL;
     return recover_scale_impl(B, S, N, flags, preds, mixture, out, ws, (hipStream_t)stream);
+}
+
+int64_t nbss_stoi_ws_bytes(int B, int S, int N, int fs) { return stoi_ws_bytes_impl(B, S, N, fs); }
+
+int nbss_stoi(int B, int S, int N, int fs, int flags, const float* preds, const float* target, float* out, void* ws, void* stream) {
+    if (!preds || !target || !out || !ws) return NBSS_EINVAL;
+    return stoi_impl(B, S, N, fs, flags, preds, target, out, ws, (hipStream_t)stream);
 }
 
 int64_t nbss_rir_ism_ws_bytes(int B, const int32_t* nb_img) {

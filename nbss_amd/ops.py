@@ -15,7 +15,7 @@ import torch
 from torch import Tensor
 
 from ._lib import (NBSS_BF16, NBSS_F32, NBSS_LOSS_MSE, NBSS_LOSS_PIT, NBSS_LOSS_SA_SDR, NBSS_LOSS_SCALE_INVARIANT, NBSS_LOSS_SI_SDR, NBSS_LOSS_SNR,
-                   NBSS_SCALE_NORM_IF_EXCEED_1, NBSS_SCALE_TOGETHER, NBSS_SDR_ZERO_MEAN, _ERR, Cfg, Lib, NbssError)
+                   NBSS_SCALE_NORM_IF_EXCEED_1, NBSS_SCALE_TOGETHER, NBSS_SDR_ZERO_MEAN, NBSS_STOI_EXTENDED, _ERR, Cfg, Lib, NbssError)
 from .params import param_table
 
 
@@ -312,6 +312,21 @@ def sdr(lib, preds, target, filter_length: int = 512, zero_mean: bool = False, w
         ws = scratch(nws, preds.device)
     out = torch.empty(B, S, dtype=torch.float32, device=preds.device)
     lib.call("nbss_sdr", B, S, N, int(filter_length), NBSS_SDR_ZERO_MEAN if zero_mean else 0, _ptr(lib, preds, torch.float32), _ptr(lib, target, torch.float32),
+             _ptr(lib, out), _ptr(lib, ws, torch.uint8), _stream(lib, preds))
+    return out
+
+
+def stoi(lib, preds, target, fs: int, extended: bool = False, ws=None):
+    """STOI (extended: eSTOI) of every (estimate s, target s) as include/nbss_hip.h defines it: preds / target [B,S,N] fp32 at fs Hz -> [B,S] fp32"""
+    B, S, N = _metric_pair("stoi", preds, target)
+    if ws is None:
+        nws = lib.nbss_stoi_ws_bytes(B, S, N, int(fs))
+        if nws <= 0:
+            raise NbssError(f"nbss_stoi_ws_bytes(B={B}, S={S}, N={N}, fs={fs}): {_ERR.get(int(nws), nws)} (fs in 8000 | 10000 | 16000, S <= 4, B <= 1024, "
+                            "at least 257 samples at 10 kHz)")
+        ws = scratch(nws, preds.device)
+    out = torch.empty(B, S, dtype=torch.float32, device=preds.device)
+    lib.call("nbss_stoi", B, S, N, int(fs), NBSS_STOI_EXTENDED if extended else 0, _ptr(lib, preds, torch.float32), _ptr(lib, target, torch.float32),
              _ptr(lib, out), _ptr(lib, ws, torch.uint8), _stream(lib, preds))
     return out
 
